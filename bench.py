@@ -9,9 +9,14 @@ c.invntt_pow_invphi() (poly.hpp:167-168, 350) as ONE fused HIP kernel.
 Inputs are generated on the device (seeded counter stream) and are resident in
 HBM before the timed region starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 N>1 is launched by torch.distributed.run, one rank per GPU: batch split with no
 data-path collective (weak scaling: per-GPU batch fixed).
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes a fixed, seeded sample of the last timed step's
+product to DIR (product_hi32.npy / product_lo32.npy, float64).  --full adds
+everything else the line used to carry: the in-run self-checks, CPU baseline,
+counter traffic, sustained rate, per-kernel extras and the side configs.
 """
 import argparse
 import json
@@ -183,7 +188,7 @@ def measure_traffic(workload, batch):
         try:
             cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", d, "--", sys.executable,
                    os.path.join(ROOT, "bench.py"), "--workload", workload, "--batch", str(batch), "--steps", str(steps),
-                   "--warmup", str(warmup), "--no-extras", "--no-cpu-baseline", "--no-traffic", "--no-rccl", "--no-side-configs", "--prewarm", "0"]
+                   "--warmup", str(warmup), "--full", "--no-extras", "--no-cpu-baseline", "--no-traffic", "--no-rccl", "--no-side-configs", "--prewarm", "0"]
             env = dict(os.environ, TMPDIR="/tmp")
             for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
                 env.pop(k, None)
@@ -412,6 +417,27 @@ def shard_config_d(torch, eng, rank, world, steps, barrier, gather_u64, max_over
             "how": "value = world x shard x steps / max-over-ranks wall time between barriers; no data-path collective"}
 
 
+DUMP_POLYS = 64            # at most this many polynomials of the product ...
+DUMP_BYTES = 48 << 20      # ... and at most this many bytes written
+
+
+def dump_outputs(eng, c, first_poly, outdir):
+    """Write a fixed, seeded sample of the polynomials of `c` (the last timed step's product) as float64 .npy files.
+    Every word is split into its high and low 32 bits, which float64 holds exactly: product_hi32.npy and
+    product_lo32.npy, shape [sample][nmoduli][degree].  The sample depends only on the batch, not on the run."""
+    import numpy as np
+    import torch
+    batch = c.shape[0]
+    per_poly = 2 * eng.nmoduli * eng.degree * 8
+    k = max(1, min(batch, DUMP_POLYS, DUMP_BYTES // per_poly))
+    idx = np.sort(np.random.default_rng(SEED).choice(batch, size=k, replace=False))
+    words = eng.to_host(c[torch.as_tensor(idx, device=c.device)]).astype(np.uint64)
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "product_hi32.npy"), (words >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(outdir, "product_lo32.npy"), (words & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    return [int(first_poly + i) for i in idx]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -426,6 +452,11 @@ def main():
     ap.add_argument("--no-traffic", action="store_true", help="skip the in-run rocprofv3 counter passes (roofline.traffic)")
     ap.add_argument("--no-rccl", action="store_true", help="N = 1 only: skip the world-size-1 RCCL initialisation")
     ap.add_argument("--no-side-configs", action="store_true", help="workload B only: skip extras.configs (configs A, C, D, E and the reference's largest test shape F timed in the same run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: self-checks, CPU baseline, counter traffic, sustained rate, "
+                         "extras and side configs (the --no-* options then switch single parts off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's product to DIR as float64 .npy files")
     ap.add_argument("--scatter-gather", action="store_true",
                     help="N > 1 only: also time one step whose operands start on rank 0 and whose product returns there "
                          "(grouped RCCL send/recv of contiguous shards, SURVEY.md 8(e)); reported beside `value`, never in it")
@@ -433,6 +464,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched plainly (`python bench.py --gpus N`): become the driver's launch line -- N ranks, one per GPU, under
         # torch.distributed.run on 127.0.0.1 -- instead of quietly running one rank.  Refuses when the node has fewer devices.
@@ -462,7 +495,7 @@ def main():
     # RCCL is initialised at EVERY world size, 1 included (a 1-GPU box then exercises the same init / barrier / all-reduce
     # calls the N-GPU launch line makes; --no-rccl keeps the profiler's inner re-runs of this script light)
     rccl = {"initialised": False, "world_size": world, "backend": backend}
-    use_dist = world > 1 or not args.no_rccl
+    use_dist = world > 1 or (args.full and not args.no_rccl)
     if use_dist:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if world == 1:
@@ -498,7 +531,7 @@ def main():
     # the engine's own communicator (include/nflhip.h nflhip_comm_*: ncclCommInitRank through the C ABI; the id travels
     # over torch.distributed) -- what a C++ caller with one process per GPU uses; here it carries the digests
     comm = None
-    if use_dist and backend == "nccl":
+    if args.full and use_dist and backend == "nccl":
         try:
             from nfllib_amd import Comm
             box = [Comm.unique_id() if rank == 0 else None]
@@ -542,37 +575,43 @@ def main():
         dt = sharding.allreduce_max(dt, dist, device=red_dev)
         kernel_ms = sharding.allreduce_max(kernel_ms, dist, device=red_dev)
 
-    # cheap in-run sanity: one sampled poly against nothing but itself commuting (parity lives in tests/)
-    ok = not eng.any_neq(c, eng.polymul(b, a))
-    # ... and host copies of a few polynomials of the timed product for the CPU checker (cpu_baseline leg below)
-    check = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        import numpy as np
-        idx = sorted({0, batch // 3, batch // 2, batch - 1})
-        check = tuple(np.concatenate([eng.to_host(t[i:i + 1]) for i in idx]) for t in (a, b, c))
+    # what the timed path computed in its last step, before anything below reuses the tensors
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, c, first_poly, args.dump_outputs)
 
-    # checksum of checksums: every rank digests ITS shard of the product (positions counted in the
-    # logical global batch, so the digests add up to the digest of the whole batch) and then recomputes its NEIGHBOUR's
-    # shard from the shared counter stream on its own GPU; the two sets of digests -- shard r computed on GPU r, and on
-    # GPU r - 1 -- must be identical, rank by rank and in the sum.
     def gather_u64(v):
         if comm is not None:
             return comm.allgather_u64(v)
         if use_dist:
             return sharding.allgather_digests(v, dist, world, device=red_dev)
         return [v]
-    own = gather_u64(eng.digest(c, first_poly=first_poly))
-    nxt = (rank + 1) % world
-    eng.fill_uniform(a, SEED, 0, first_poly=nxt * batch)
-    eng.fill_uniform(b, SEED, 1, first_poly=nxt * batch)
-    eng.polymul(a, b, out=c)
-    cross = gather_u64(eng.digest(c, first_poly=nxt * batch))      # entry r = shard (r + 1) mod world
-    cross = [cross[(r - 1) % world] for r in range(world)]          # ... reordered: entry r = shard r
-    sums_ok = own == cross
-    checksum = {"ok": bool(sums_ok), "sum_of_shard_digests": "%016x" % sharding.combine_digests(own),
-                "recomputed_on_the_neighbouring_gpu": "%016x" % sharding.combine_digests(cross), "shards": world,
-                "via": "nflhip_comm_allgather_u64 (RCCL)" if comm is not None else ("torch.distributed" if use_dist else "local")}
-    ok = ok and sums_ok
+
+    ok, check, checksum = True, None, None
+    if args.full:
+        # cheap in-run sanity: one sampled poly against nothing but itself commuting (parity lives in tests/)
+        ok = not eng.any_neq(c, eng.polymul(b, a))
+        # ... and host copies of a few polynomials of the timed product for the CPU checker (cpu_baseline leg below)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            import numpy as np
+            idx = sorted({0, batch // 3, batch // 2, batch - 1})
+            check = tuple(np.concatenate([eng.to_host(t[i:i + 1]) for i in idx]) for t in (a, b, c))
+
+        # checksum of checksums: every rank digests ITS shard of the product (positions counted in the
+        # logical global batch, so the digests add up to the digest of the whole batch) and then recomputes its NEIGHBOUR's
+        # shard from the shared counter stream on its own GPU; the two sets of digests -- shard r computed on GPU r, and on
+        # GPU r - 1 -- must be identical, rank by rank and in the sum.
+        own = gather_u64(eng.digest(c, first_poly=first_poly))
+        nxt = (rank + 1) % world
+        eng.fill_uniform(a, SEED, 0, first_poly=nxt * batch)
+        eng.fill_uniform(b, SEED, 1, first_poly=nxt * batch)
+        eng.polymul(a, b, out=c)
+        cross = gather_u64(eng.digest(c, first_poly=nxt * batch))      # entry r = shard (r + 1) mod world
+        cross = [cross[(r - 1) % world] for r in range(world)]          # ... reordered: entry r = shard r
+        sums_ok = own == cross
+        checksum = {"ok": bool(sums_ok), "sum_of_shard_digests": "%016x" % sharding.combine_digests(own),
+                    "recomputed_on_the_neighbouring_gpu": "%016x" % sharding.combine_digests(cross), "shards": world,
+                    "via": "nflhip_comm_allgather_u64 (RCCL)" if comm is not None else ("torch.distributed" if use_dist else "local")}
+        ok = ok and sums_ok
 
     alg_bytes_per_poly = 3 * nm * n * (lb // 8)       # read a, read b, write c
     launch_bytes = alg_bytes_per_poly * batch
@@ -581,7 +620,7 @@ def main():
 
     kwl = "B" if args.workload == "D" else args.workload   # D runs B's kernel on a larger batch
     traffic, traffic_src = None, None
-    if rank == 0 and world == 1 and not args.no_traffic:
+    if args.full and rank == 0 and world == 1 and not args.no_traffic:
         # (bytes per polynomial do not depend on the batch: the counter passes use at most the kernel's default batch)
         tb = min(batch, WORKLOADS[kwl][3])
         traffic, traffic_src = measure_traffic(kwl, tb)
@@ -643,7 +682,7 @@ def main():
     extras = None
     power = None
     sustained = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # package power and shader clock UNDER the product kernel (the product kernels run at the package
         # power limit, so their clock -- not their schedule -- is what separates them from the issue bound): ~2.5 s of
         # products queued on the stream, rocm-smi sampled beside them.  Outside the timed region.
@@ -682,7 +721,7 @@ def main():
         except Exception as ex:  # reported, never fatal
             torch.cuda.synchronize()
             power = {"error": repr(ex)}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # secondary rates of SURVEY.md 8(d): per-kernel transforms, point-wise ops, the
         # "one operand pre-transformed" product and CRT lift/project (same batch, same stream)
         from nfllib_amd import OP_ADD, OP_MUL
@@ -846,7 +885,7 @@ def main():
     # workload B's per-GPU batch; the N = 1 line carries the same block for ONE shard (3 x 16 GiB resident).  Collective: every
     # rank runs it, same barriers and max-over-ranks clock as the headline, its own checksum of checksums.
     config_d = None
-    if args.workload == "B" and not args.no_side_configs:
+    if args.full and args.workload == "B" and not args.no_side_configs:
         a = b = c = None
         torch.cuda.empty_cache()
         try:
@@ -867,8 +906,7 @@ def main():
         "vs_baseline": None, "dtype": "u%d" % lb, "data": "synthetic",
         "config": {"workload": "nfl::poly<uint%d_t,%d,%d> batched polymul (BASELINE configs %s)" % (lb, n, nm, args.workload),
                    "degree": n, "nmoduli": nm, "limb_bits": lb, "batch_per_gpu": batch, "global_batch": batch * world,
-                   "parallelism": "batch-split x%d, no data-path collective" % world, "self_check": bool(ok),
-                   "checksum_of_checksums": checksum, "rccl": rccl},
+                   "parallelism": "batch-split x%d, no data-path collective" % world, "rccl": rccl},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
                      "kernel": {"A": "nflhip_row1024_i2_u32_asm", "B": "nflhip_polymul4096i2_asm (2 stages dropped each way, base multiplication mod X^4 -+ zeta)",
@@ -929,13 +967,16 @@ def main():
                         "source": model + ", profiles/r03_ubench_issue.txt, profiles/r03_power_clock.txt, profiles/r03_operand_ab.txt"}
         sec["power"] = power
         result["roofline"]["secondary"] = sec
+    if args.full:
+        result["config"]["self_check"] = bool(ok)
+        result["config"]["checksum_of_checksums"] = checksum
     if sustained is not None:
         result["sustained"] = sustained
     if extras is not None:
         result["extras"] = extras
     if scatter is not None:
         result["scatter_gather"] = scatter
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(lb, n, nm, args.cpu_budget, check=check)
         except Exception as e:  # the checker must never take the bench down

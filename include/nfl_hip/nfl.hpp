@@ -4,7 +4,7 @@
 // (include/nfl/poly.hpp:82-352), nfl::poly_p (include/nfl/poly_p.hpp:11-204) and their
 // expression-template operators (include/nfl/ops.hpp:18-97, 249-277) so existing callers compile
 // unchanged -- the reference's own test programs build against this header as they are
-// (tests/reftests/Makefile) -- but every whole-polynomial operation is forwarded through the C ABI of
+// (tests/test_reference_programs.py) -- but every whole-polynomial operation is forwarded through the C ABI of
 // include/nflhip.h to hand-written HIP kernels.  There is no CPU arithmetic on the hot path in this
 // header: without libnflhip.so + a GPU every operation throws std::runtime_error (the reference's error
 // convention: core.hpp:111-115).  Reached as <nfl.hpp>, <nfl/poly.hpp>, <nfl/poly_p.hpp>, ... through the

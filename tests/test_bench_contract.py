@@ -1,5 +1,6 @@
 """The bench.py / __graft_entry__ contract: one JSON line with the agreed keys (metric of BASELINE.json, whole-job
-value, roofline, cpu_baseline), CLI defaults, and -- without a GPU -- a loud failure instead of a CPU fallback."""
+value, roofline; cpu_baseline and the rest under --full), CLI defaults, --dump-outputs, and -- without a GPU -- a loud
+failure instead of a CPU fallback."""
 import json
 import os
 import subprocess
@@ -25,6 +26,11 @@ def test_metric_string_is_the_baselines():
     assert want in src
 
 
+def test_bench_options_full_and_dump_outputs():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
 @pytest.mark.skipif(_gpu(), reason="CPU-only behaviour")
 def test_bench_refuses_to_run_without_a_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0"],
@@ -36,7 +42,7 @@ def test_bench_refuses_to_run_without_a_gpu():
 @pytest.mark.parametrize("workload,batch", [("B", 512), ("C", 16), ("A", 4096)])
 def test_bench_line_contract(workload, batch):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload",
-                        workload, "--batch", str(batch), "--cpu-budget", "1.0"], capture_output=True, text=True,
+                        workload, "--batch", str(batch), "--cpu-budget", "1.0", "--full"], capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(r.stdout.strip().splitlines()) == 1, "stdout is exactly one line: " + r.stdout[:300]
@@ -77,7 +83,7 @@ def test_two_rank_launch_line_of_the_driver():
     env = dict(os.environ, NFLHIP_BENCH_BACKEND="gloo", NFLHIP_BENCH_ONE_DEVICE="1", NFLHIP_BENCH_D_SHARD="1024")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-                        "--warmup", "1", "--batch", "512", "--scatter-gather"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "1", "--batch", "512", "--scatter-gather", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "rank 0 alone prints the JSON line"
@@ -111,7 +117,7 @@ def test_eight_rank_rehearsal_of_the_scale_line():
     env = dict(os.environ, NFLHIP_BENCH_BACKEND="gloo", NFLHIP_BENCH_ONE_DEVICE="1", NFLHIP_BENCH_D_SHARD="256")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3",
-                        "--warmup", "1", "--batch", "256", "--prewarm", "0.1"], capture_output=True, text=True, timeout=1500, env=env)
+                        "--warmup", "1", "--batch", "256", "--prewarm", "0.1", "--full"], capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "rank 0 alone prints the JSON line"
@@ -136,7 +142,7 @@ def test_config_d_preflight_refuses_a_shard_that_does_not_fit():
     with a reason in the block (the headline still prints), instead of an out-of-memory fault mid-run"""
     env = dict(os.environ, NFLHIP_BENCH_D_SHARD=str(1 << 22))      # 3 x 512 GiB
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "256", "--no-extras",
-                        "--no-cpu-baseline", "--no-traffic", "--prewarm", "0"], capture_output=True, text=True, timeout=600, env=env)
+                        "--no-cpu-baseline", "--no-traffic", "--prewarm", "0", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout)
     dd = d["extras"]["configs"]["D"]
@@ -152,8 +158,8 @@ def test_plain_gpus_n_launches_n_ranks_itself_or_refuses():
     env = dict(os.environ, NFLHIP_BENCH_BACKEND="gloo", NFLHIP_BENCH_ONE_DEVICE="1", NFLHIP_BENCH_D_SHARD="1024")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "512"],
-                       capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "512",
+                        "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -173,7 +179,7 @@ def test_headline_line_carries_sustained_independent_secondary_and_side_configs(
     """workload B's line (what the driver records): `sustained` (the same launch held for seconds), `roofline.secondary`
     priced at the hardware issue rate with the fitted figure labelled as such, and extras.configs with configs C and E
     (polymul and CRT lift) timed and counter-measured inside the same run"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--cpu-budget", "1.0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--cpu-budget", "1.0", "--full"],
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout)
@@ -214,3 +220,38 @@ def test_headline_line_carries_sustained_independent_secondary_and_side_configs(
     one = cfg["E"]["polymul_plus_crt_lift"]     # BASELINE configs[4] as ONE figure: slower than either part, faster than their serial sum allows
     assert one["unit"] == "polys/s" and 0 < one["value"] < min(cfg["E"]["value"], cfg["E"]["crt_lift"]["value"])
     assert one["ms_per_step"] < 1.15 * (cfg["E"]["ms_per_step"] + cfg["E"]["crt_lift"]["ms_per_step"])
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_the_last_product(tmp_path, oracle_factory):
+    """a plain run carries the headline keys only (no checks, baselines or extras: those are --full), times exactly --steps
+    steps, and --dump-outputs writes a seeded sample of the last timed product, split into exact 32-bit halves"""
+    import numpy as np
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "512",
+           "--prewarm", "0", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout)
+    assert KEYS <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["metric"].startswith("poly-mults/sec (NTT+pointwise+INTT), n=4096, 4x62-bit moduli") and d["dtype"] == "u64"
+    assert not {"cpu_baseline", "extras", "sustained"} & set(d) and "self_check" not in d["config"]
+    hi, lo = np.load(out / "product_hi32.npy"), np.load(out / "product_lo32.npy")
+    assert hi.dtype == lo.dtype == np.float64 and hi.shape == lo.shape == (64, 4, 4096)
+    got = (hi.astype(np.uint64) << np.uint64(32)) | lo.astype(np.uint64)
+    # the same seeded sample of the same inputs, recomputed here: on the device, and the first polynomials by the CPU oracle
+    from nfllib_amd import Engine
+    sys.path.insert(0, ROOT)
+    import bench
+    eng = Engine(64, 4096, 4, device=0)
+    try:
+        a = eng.fill_uniform(eng.empty(512), bench.SEED, 0)
+        b = eng.fill_uniform(eng.empty(512), bench.SEED, 1)
+        c = eng.polymul(a, b)
+        want = tmp_path / "want"
+        idx = bench.dump_outputs(eng, c, 0, str(want))
+        assert np.array_equal(np.load(want / "product_hi32.npy"), hi) and np.array_equal(np.load(want / "product_lo32.npy"), lo)
+        ha, hb = (np.concatenate([eng.to_host(t[i:i + 1]) for i in idx[:4]]) for t in (a, b))
+    finally:
+        eng.close()
+    assert np.array_equal(oracle_factory(64, 4096, 4).polymul(ha, hb), got[:4])

@@ -1,12 +1,12 @@
 """The drop-in gate: the REFERENCE's own test programs, unchanged, against this repository's headers and library.
 
 north_star: "keeps the nfl::poly<T, Degree, NbModuli> template surface and expression-template operators so it drops
-into existing callers".  tests/reftests/Makefile generates the `#define CONFIG ...` + `#include "<test>.cpp"` wrappers
+into existing callers".  oracle/reftests/Makefile generates the `#define CONFIG ...` + `#include "<test>.cpp"` wrappers
 of /root/reference/tests/CMakeLists.txt:1-77 for every test source x the reference's five configs (plus prng_demo,
 ntt_perfs and the two-TU ntt_multi), compiles them with `-I include` only and links them against libnflhip.so.
 
   * build container (has /root/reference): all 63 programs must compile and link   -- `-m "not gpu"`
-  * GPU box (no /root/reference; the binaries travel under tests/_reftests/, git-ignored): every program must
+  * GPU host (no reference sources; the binaries go there with the git-ignored oracle/_ref/reftests/): every program must
     exit 0 -- the reference's own pass criterion (tests/CMakeLists.txt add_test run_*)        -- `-m gpu`
 Nothing of the reference is copied into the repository: the wrappers only #include it where it lies.
 """
@@ -16,8 +16,8 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MK = os.path.join(ROOT, "tests", "reftests")
-OUT = os.path.join(ROOT, "tests", "_reftests")
+MK = os.path.join(ROOT, "oracle", "reftests")
+OUT = os.path.join(ROOT, "oracle", "_ref", "reftests")
 REF = "/root/reference/tests"
 CONFIGS = ["8_60_uint32_t", "128_14_uint16_t", "1024_60_uint32_t", "8192_124_uint64_t", "32768_124_uint64_t"]
 PERCFG = ["nfllib_demo_main_op", "nfllib_demo_main_func", "nfl_add", "nfl_sub", "nfl_mul", "nfl_eq", "nfl_neq", "nfl_stream",
@@ -55,7 +55,7 @@ def test_reference_program_fails_loudly_without_a_gpu():
 def test_reference_program_passes_on_the_device(prog):
     exe = os.path.join(OUT, prog)
     if not os.path.exists(exe):
-        pytest.fail("tests/_reftests/%s is missing: run __graft_entry__.build() in the build container" % prog)
+        pytest.fail("oracle/_ref/reftests/%s is missing: run __graft_entry__.build() where the reference sources are" % prog)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=1200, cwd=OUT)
     assert r.returncode == 0, "%s exited %d\n%s\n%s" % (prog, r.returncode, r.stdout[-1500:], r.stderr[-1500:])
     if prog.startswith("nfllib_demo"):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """What an UNCHANGED caller of the reference gains: the reference's own timing programs (tests/nfllib_demo_main_op.cpp,
 nfllib_demo_main_func.cpp per CONFIG, tests/ntt_perfs.cpp) built twice from the SAME sources --
-  cpu : against the real reference (tests/reftests/Makefile `cpu` -> oracle/_ref/progs/, NFL_OPTIMIZED + NTT_AVX2), on this host's CPU
-  gpu : against this repository's drop-in headers + libnflhip.so (tests/reftests/Makefile -> tests/_reftests/), on the MI355X
+  cpu : against the real reference (oracle/reftests/Makefile `cpu` -> oracle/_ref/progs/, NFL_OPTIMIZED + NTT_AVX2), on this host's CPU
+  gpu : against this repository's drop-in headers + libnflhip.so (oracle/reftests/Makefile -> oracle/_ref/reftests/), on the MI355X
 -- run side by side on the GPU box; their "Time per ...: V us" lines are paired into one table.
 The programs time per-polynomial calls on nfl::poly (the reference's literal host-array type), so every device call carries
 its PCIe round trip: this is the floor of the drop-in, not the resident rate (nfl::poly_p).
@@ -17,7 +17,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GPU_DIR = os.path.join(ROOT, "tests", "_reftests")
+GPU_DIR = os.path.join(ROOT, "oracle", "_ref", "reftests")
 CPU_DIR = os.path.join(ROOT, "oracle", "_ref", "progs")
 LINE = re.compile(r"^Time per (.+?):\s*([0-9.eE+-]+)\s*us\s*$")
 
@@ -59,7 +59,7 @@ def main():
     args = ap.parse_args()
     progs = [p for p in programs() if args.only in p]
     if not progs:
-        raise SystemExit("no program pairs found (build: make -C tests/reftests all cpu)")
+        raise SystemExit("no program pairs found (build: make -C oracle/reftests all cpu)")
     rows, out = [], {}
     for p in progs:
         cpu, wc = run(os.path.join(CPU_DIR, p), args.reps)
