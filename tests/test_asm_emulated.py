@@ -39,8 +39,7 @@ def generated():
 
 
 def operands(o, limb_bits, n, nm, batch, seed):
-    from nfllib_amd.params import params
-    prm = params(limb_bits)
+    prm = o.params     # (the oracle's table: the head of params<T>, or a window of it -- table_window)
     rng = np.random.default_rng(seed)
     P = np.asarray(prm.P[:nm], dtype=np.uint64)
     a = (rng.integers(0, 1 << 62, size=(batch, nm, n), dtype=np.uint64) % P[None, :, None]).astype(prm.dtype)
@@ -717,3 +716,167 @@ def test_strict_mode_models_the_measured_visibility_rules(generated, oracle_fact
     mutant.write_text(re.sub(r"(global_load_dword .*) sc1\n", r"\1\n", text))
     with pytest.raises(asm_emu.StrictError, match="stale cache line"):
         asm_emu.run_xcd_product(str(mutant), 32768, 1, prm, a, b, 0, 1, 0, 16, _picker("random"))
+
+
+# ------------------------------------------------------------------ the top of each modulus table
+# The tests above run the generated kernels on the first one to three moduli, where delta is smallest.  The range arguments
+# of the 62-bit and 30-bit arithmetic have their smallest margins at the END of each table: u64 #90 / #91
+# (delta ~ 2^32, the last delta-form moduli) and u32 #289 / #290 (p ~ 0.81 * 2^30).  Each listing family runs once more here on
+# that window (u16 has two moduli, both covered above).
+TOP = {64: (90, 2), 32: (289, 2)}
+
+
+def table_window(limb_bits, first, count):
+    """params<T> restricted to moduli first .. first + count - 1: the object asm_emu.device_tables and the oracle read their
+    moduli from (P, Pn, primitive_roots, invkmax; kmax and kmax_log2 are the table's)"""
+    import types
+    from nfllib_amd.params import params
+    prm = params(limb_bits)
+    assert first + count <= prm.max_moduli
+    w = types.SimpleNamespace(**vars(prm))
+    for name in ("P", "Pn", "primitive_roots", "invkmax"):
+        setattr(w, name, np.ascontiguousarray(getattr(prm, name)[first:first + count]))
+    w.max_moduli = count
+    return w
+
+
+def top_operands(limb_bits, n, batch, seed, nm=None):
+    """(oracle, window, a, b) on the top window: operands() plus the edge rows -- element 1: all p-1 times alternating 0 / p-1
+    on the first modulus of the window, X^(n-1) * X = -1 on the last; element 2: all p-1 times all p-1 on the last modulus"""
+    from oracle import oracle as O
+    first, count = TOP[limb_bits]
+    if nm is not None:
+        first, count = first + count - nm, nm
+    prm = table_window(limb_bits, first, count)
+    o = O.Oracle(limb_bits, n, count, prm)
+    _, a, b = operands(o, limb_bits, n, count, batch, seed)
+    Pw = np.asarray(prm.P, dtype=np.uint64).astype(prm.dtype)
+    alt = np.arange(n) % 2 == 1
+    if batch > 1:
+        a[1, 0], b[1, 0] = Pw[0] - 1, np.where(alt, Pw[0] - 1, 0)
+        a[1, -1], b[1, -1] = 0, 0
+        a[1, -1, n - 1], b[1, -1, 1] = 1, 1
+    if batch > 2:
+        a[2, -1], b[2, -1] = Pw[-1] - 1, Pw[-1] - 1
+    return o, prm, a, b
+
+
+def test_table_window_is_the_table():
+    from nfllib_amd.params import params
+    w, prm = table_window(64, 90, 2), params(64)
+    assert [int(x) for x in w.P] == [int(prm.P[90]), int(prm.P[91])] and w.max_moduli == 2 and w.kmax == prm.kmax
+    assert (1 << 62) - int(w.P[1]) < (1 << 32) <= (1 << 62) - int(prm.P[92]), "#91 is the last delta-form modulus"
+    assert int(table_window(32, 289, 2).P[1]) == int(params(32).P[290])
+
+
+def test_emulated_u32_top_moduli(generated):
+    """row8 (lane per row), row1024 / 2048 / 4096 (product, transforms), the incomplete product and the fused pipelines"""
+    o, prm, a, b = top_operands(32, 8, 3, 51)
+    fa, fb, want = o.ntt(a), o.ntt(b), o.polymul(a, b)
+    assert np.array_equal(asm_emu.run_row_kernel(generated("row8_u32"), 32, 8, 2, prm, a, b, 256, True), want)
+    assert np.array_equal(asm_emu.run_row_kernel(generated("row8_fwd_u32"), 32, 8, 2, prm, a, a, 256, True), fa)
+    assert np.array_equal(asm_emu.run_row_kernel(generated("row8_inv_u32"), 32, 8, 2, prm, fa, fa, 256, True), a)
+    assert np.array_equal(asm_emu.run_row_kernel(generated("row8_ntt_u32"), 32, 8, 2, prm, a, fb, 256, True), want)
+    for n, stems in ((1024, ("product", "i2")), (2048, ("transforms", "i2")), (4096, ("product", "transforms"))):
+        o, prm, a, b = top_operands(32, n, 3, 52 + n)
+        run = lambda stem, x, y, **kw: asm_emu.run_row_kernel(generated("row%d_%s" % (n, stem)), 32, n, 2, prm, x, y, 4096 // n, True, **kw)
+        want = o.polymul(a, b)
+        if "product" in stems:
+            assert np.array_equal(run("u32", a, b), want), n
+        if "i2" in stems:
+            assert np.array_equal(run("i2_u32", a, b, incomplete=2), want), n
+        if "transforms" in stems:
+            fa = o.ntt(a)
+            assert np.array_equal(run("fwd_u32", a, a), fa) and np.array_equal(run("inv_u32", fa, fa), a), n
+    # the fused pipelines (one wave per 1024-word row): out0 = NTT(x) k0 + NTT(e0), out1 = NTT(x) k1 + NTT(e1); INTT(b - a k)
+    n, batch = 1024, 3
+    o, prm, a, b = top_operands(32, n, batch, 60)
+    _, _, k, x = top_operands(32, n, batch, 61)
+    k0, k1 = k[:1], k
+    K0 = np.ascontiguousarray(np.broadcast_to(k0, a.shape))
+    got = asm_emu.run_row_fused(generated("row1024_fmsinv_u32"), n, 2, prm, 4, "inv", limb_bits=32, a=a, b=b, key=k0)
+    assert np.array_equal(got, o.intt(o.pointwise(1, b, o.pointwise(2, a, K0))))
+    r = asm_emu.run_row_fused(generated("row1024_enc2w_u32"), n, 2, prm, 4, "fwd", limb_bits=32, incomplete=2, x=x, e0=a, k0=k0,
+                              e1=b, k1=k1, batch=batch)
+    fx = o.ntt(x)
+    assert np.array_equal(r[0], o.pointwise(0, o.pointwise(2, fx, K0), o.ntt(a)))
+    assert np.array_equal(r[1], o.pointwise(0, o.pointwise(2, fx, k1), o.ntt(b)))
+
+
+def test_emulated_u64_top_moduli_4096(generated):
+    """the metric kernel, its incomplete-transform twins, the stand-alone 4096-word transforms and the fused pipelines"""
+    n = 4096
+    o, prm, a, b = top_operands(64, n, 3, 71)
+    fa, fb, want = o.ntt(a), o.ntt(b), o.polymul(a, b)
+    blk = lambda stem, x, y, **kw: asm_emu.run_block_kernel(generated(stem), n, 2, prm, x, y, 12, **kw)
+    assert np.array_equal(blk("polymul4096nt", a, b), want)
+    for lv in (1, 2):
+        assert np.array_equal(blk("polymul4096i%d" % lv, a, b, incomplete=lv), want), lv
+    assert np.array_equal(blk("ntt_fwd4096", a, a), fa)
+    assert np.array_equal(blk("ntt_inv4096", fa, fa), a)
+    assert np.array_equal(blk("polymul_ntt4096", a, fb), want)
+    assert np.array_equal(blk("ntt_inv_mul4096", fa, fb), want)
+    _, _, k, x = top_operands(64, n, 3, 72)
+    K = np.ascontiguousarray(np.broadcast_to(k[:1], a.shape))
+    f = [o.ntt(x), fa, fb]
+    want0 = o.pointwise(0, o.pointwise(2, f[0], K), f[1])
+    want1 = o.pointwise(0, o.pointwise(2, f[0], k), f[2])
+    got = asm_emu.run_fused_kernel(generated("fused_enc2_4096"), n, 2, prm, [x, a, b], [k[:1], k], 3, 2)
+    assert np.array_equal(got[0], want0) and np.array_equal(got[1], want1)
+    prod = o.pointwise(2, a, K)
+    got = asm_emu.run_fused_kernel(generated("fused_fms_inv4096"), n, 2, prm, [a, b], [k[:1]], 3, 1)
+    assert np.array_equal(got[0], o.intt(o.pointwise(1, b, prod)))
+    got = asm_emu.run_fused_kernel(generated("fused_fma_inv4096r"), n, 2, prm, [a, b], [k[:1]], 3, 1, lane_major=True)
+    assert np.array_equal(got[0], o.intt(o.pointwise(0, b, prod)))
+
+
+def test_emulated_u64_top_moduli_wave_per_row(generated):
+    """rows of 1024 / 2048 words (tools/asmgen/rows1k.py): the products at level 2 and 0, the transforms, the fused pipelines"""
+    for n in (1024, 2048):
+        o, prm, a, b = top_operands(64, n, 3, 80 + n)
+        rpw = 4096 // n
+        run = lambda stem, x, y, **kw: asm_emu.run_row_kernel(generated("row%d_%s" % (n, stem)), 64, n, 2, prm, x, y, rpw, True, **kw)
+        want, fa = o.polymul(a, b), o.ntt(a)
+        assert np.array_equal(run("u64", a, b, incomplete=2), want), n
+        assert np.array_equal(run("l0_u64", a, b), want), n
+        assert np.array_equal(run("fwd_u64", a, a), fa) and np.array_equal(run("inv_u64", fa, fa), a), n
+    n = 1024
+    o, prm, a, b = top_operands(64, n, 3, 90)
+    _, _, k, x = top_operands(64, n, 3, 91)
+    K = np.ascontiguousarray(np.broadcast_to(k[:1], a.shape))
+    got = asm_emu.run_row_fused(generated("row1024_fmsinv_u64"), n, 2, prm, 4, "inv", a=a, b=b, key=k[:1])
+    assert np.array_equal(got, o.intt(o.pointwise(1, b, o.pointwise(2, a, K))))
+    r = asm_emu.run_row_fused(generated("row1024_enc2w_u64"), n, 2, prm, 4, "fwd", x=x, e0=a, k0=k[:1], e1=b, k1=k, batch=3)
+    fx = o.ntt(x)
+    assert np.array_equal(r[0], o.pointwise(0, o.pointwise(2, fx, K), o.ntt(a)))
+    assert np.array_equal(r[1], o.pointwise(0, o.pointwise(2, fx, k), o.ntt(b)))
+
+
+def test_emulated_u64_top_moduli_row_resident(generated):
+    """rows of 8192 / 16384 words (ring-mode register map): products on complete and incomplete transforms, the two-rows-per-
+    workgroup forward transform, the fused pipelines; and the register-resident 32768-word pair on the last modulus alone"""
+    for n, bl, nm in ((8192, 13, 2), (16384, 14, 1)):
+        o, prm, a, b = top_operands(64, n, 2, 100 + bl, nm=nm)
+        if nm == 1:   # (#91 alone: element 1 holds the largest products, all p-1 times all p-1)
+            a[1, 0], b[1, 0] = int(prm.P[0]) - 1, int(prm.P[0]) - 1
+        want = o.polymul(a, b)
+        assert np.array_equal(asm_emu.run_block_kernel(generated("polymul%d" % n), n, nm, prm, a, b, bl), want), n
+        assert np.array_equal(asm_emu.run_block_kernel(generated("polymul%di2" % n), n, nm, prm, a, b, bl, incomplete=2), want), n
+    n = 8192
+    o, prm, a, b = top_operands(64, n, 2, 110)
+    fa, fb = o.ntt(a), o.ntt(b)
+    assert np.array_equal(asm_emu.run_block_kernel(generated("ntt_fwd8192x2"), n, 2, prm, a, a, 13, count=2), fa)
+    assert np.array_equal(asm_emu.run_block_kernel(generated("ntt_inv8192"), n, 2, prm, fa, fa, 13), a)
+    K = np.ascontiguousarray(np.broadcast_to(b[:1], a.shape))
+    got = asm_emu.run_fused_kernel(generated("fused_enc2_8192"), n, 2, prm, [a, b, a], [b[:1], b], 2, 2, groups=2)
+    assert np.array_equal(got[0], o.pointwise(0, o.pointwise(2, fa, K), fb))
+    assert np.array_equal(got[1], o.pointwise(0, o.pointwise(2, fa, b), fa))
+    got = asm_emu.run_fused_kernel(generated("fused_fms_inv8192"), n, 2, prm, [a, b], [b[:1]], 2, 1, groups=2)
+    assert np.array_equal(got[0], o.intt(o.pointwise(1, b, o.pointwise(2, a, K))))
+    n = 32768
+    o, prm, a, b = top_operands(64, n, 1, 120, nm=1)
+    a[0, 0, :8], b[0, 0, :8] = int(prm.P[0]) - 1, int(prm.P[0]) - 1     # (one element: the edge words go into it)
+    fa, fb = o.ntt(a), o.ntt(b)
+    run = lambda stem, x, y: asm_emu.run_block_kernel(generated(stem), n, 1, prm, x, y, 15, words_per_thread=32)
+    assert np.array_equal(run("ntt_fwd32768", a, a), fa)
+    assert np.array_equal(run("polymul_ntt32768", a, fb), o.polymul(a, b))
