@@ -112,6 +112,26 @@ template <class P> class device_batch {
     same_size(a); same_size(b_ntt);
     detail::check(ctx(), nflhip_polymul_ntt_dev(ctx(), d_, a.d_, b_ntt.d_, n_, queue()), "polymul_ntt");
   }
+  // Galois automorphisms (include/nflhip.h): *this = sigma_k(src), coefficient or NTT form; src must be another batch
+  void assign_automorphism(const device_batch &src, uint64_t k, bool ntt_form = false) {
+    same_size(src);
+    detail::check(ctx(), nflhip_automorphism_dev(ctx(), d_, src.d_, n_, k, ntt_form ? NFLHIP_FORM_NTT : NFLHIP_FORM_COEFF, queue()),
+                  "automorphism");
+  }
+  // *outs[m] = sigma_{ks[m]}(src) for m < count <= NFLHIP_AUTOMORPHISM_MAX_OUTPUTS, one launch that reads src once
+  static void assign_automorphisms(device_batch *const *outs, const uint64_t *ks, size_t count, const device_batch &src,
+                                   bool ntt_form = false) {
+    if (count > NFLHIP_AUTOMORPHISM_MAX_OUTPUTS) throw std::runtime_error("nfl(hip): too many automorphism outputs");
+    void *d[NFLHIP_AUTOMORPHISM_MAX_OUTPUTS];
+    for (size_t m = 0; m < count; ++m) {
+      src.same_size(*outs[m]);
+      if (outs[m]->ctx() != src.ctx()) throw std::runtime_error("nfl(hip): automorphism outputs on another device");
+      d[m] = outs[m]->d_;
+    }
+    detail::check(src.ctx(), nflhip_automorphism_multi_dev(src.ctx(), d, ks, count, src.d_, src.n_,
+                                                           ntt_form ? NFLHIP_FORM_NTT : NFLHIP_FORM_COEFF, src.queue()),
+                  "automorphisms");
+  }
   // CRT lift / project of the whole resident batch (gmp.hpp:183-219): out[(b*degree + i)*L .. +L) = little-endian limbs
   // of X_{b,i} in [0, Q), L = P::crt_limbs(); limbs2poly takes L_in limbs per coefficient
   void poly2limbs(std::vector<uint64_t> &out) const {
@@ -414,6 +434,21 @@ template <class P> class sharded_batch {
   void assign_polymul_ntt(const sharded_batch &a, const sharded_batch &b_ntt) {
     same_split(a); same_split(b_ntt);
     for (size_t r = 0; r < shards(); ++r) if (count(r)) shards_[r].assign_polymul_ntt(a.shards_[r], b_ntt.shards_[r]);
+  }
+  void assign_automorphism(const sharded_batch &src, uint64_t k, bool ntt_form = false) {
+    same_split(src);
+    for (size_t r = 0; r < shards(); ++r) if (count(r)) shards_[r].assign_automorphism(src.shards_[r], k, ntt_form);
+  }
+  static void assign_automorphisms(sharded_batch *const *outs, const uint64_t *ks, size_t count, const sharded_batch &src,
+                                   bool ntt_form = false) {
+    if (count > NFLHIP_AUTOMORPHISM_MAX_OUTPUTS) throw std::runtime_error("nfl(hip): too many automorphism outputs");
+    for (size_t m = 0; m < count; ++m) src.same_split(*outs[m]);
+    for (size_t r = 0; r < src.shards(); ++r) {
+      if (!src.count(r)) continue;
+      shard_type *d[NFLHIP_AUTOMORPHISM_MAX_OUTPUTS];
+      for (size_t m = 0; m < count; ++m) d[m] = &outs[m]->shards_[r];
+      shard_type::assign_automorphisms(d, ks, count, src.shards_[r], ntt_form);
+    }
   }
   void assign_program(const unsigned char *program, size_t len, const sharded_batch *const *operands, size_t nops) {
     if (nops > NFLHIP_EXPR_MAX_OPERANDS) throw std::runtime_error("nfl(hip): too many operands");

@@ -234,6 +234,19 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
   template <class M> auto load(size_t cm, size_t i) const -> decltype(M::load(&(this->operator()(cm, i)))) { return M::load(&(*this)(cm, i)); }
   static constexpr value_type get_modulus(size_t n) { return poly_type::get_modulus(n); }
 
+  // Galois automorphism sigma_k (nfl::automorphism / nfl::automorphism_ntt below): the deferred queue of this ring type runs
+  // first (on the caller), then one launch on the queue's stream.  The result gets a payload of its own, so `out` may be
+  // `in` and copy-on-write sharers of out's old value keep it.
+  static void automorphism_into(poly_p &out, poly_p const &in, uint64_t k, int form) {
+    lazy_t::inst().flush();
+    ptr_type src = in._p;  // (holds the input while the launch is enqueued)
+    ptr_type dst = fresh();
+    const void *s = src->dev_ro();
+    detail::check(ctx_t::get(), nflhip_automorphism_dev(ctx_t::get(), dst->dev_wo(), s, 1, k, form, ctx_t::queue()),
+                  form == NFLHIP_FORM_NTT ? "automorphism_ntt" : "automorphism");
+    out._p = dst;
+  }
+
   /* ntt stuff - public API (poly_p.hpp:141-142): in place in HBM */
   void ntt_pow_phi() { transform(lazy_t::K_NTT_FWD); }
   void invntt_pow_invphi() { transform(lazy_t::K_NTT_INV); }
@@ -311,6 +324,23 @@ using poly_p_from_modulus = poly_p<T, Degree, AggregatedModulusBitSize / params<
 
 template <class T, size_t D, size_t M> std::ostream &operator<<(std::ostream &os, poly_p<T, D, M> const &p) {
   return os << p.poly_obj();
+}
+
+/* Galois automorphisms sigma_k : a(X) -> a(X^k) mod (X^n + 1), k odd (include/nflhip.h): coefficient form, and the NTT form
+ * ntt_pow_phi() produces.  `out` may be `in`. */
+template <class T, size_t D, size_t M> void automorphism(poly<T, D, M> &out, poly<T, D, M> const &in, uint64_t k) {
+  typedef poly<T, D, M> P;
+  detail::check(P::ctx(), nflhip_automorphism(P::ctx(), out.data(), in.cdata(), 1, k, NFLHIP_FORM_COEFF), "automorphism");
+}
+template <class T, size_t D, size_t M> void automorphism_ntt(poly<T, D, M> &out, poly<T, D, M> const &in, uint64_t k) {
+  typedef poly<T, D, M> P;
+  detail::check(P::ctx(), nflhip_automorphism(P::ctx(), out.data(), in.cdata(), 1, k, NFLHIP_FORM_NTT), "automorphism_ntt");
+}
+template <class T, size_t D, size_t M> void automorphism(poly_p<T, D, M> &out, poly_p<T, D, M> const &in, uint64_t k) {
+  poly_p<T, D, M>::automorphism_into(out, in, k, NFLHIP_FORM_COEFF);
+}
+template <class T, size_t D, size_t M> void automorphism_ntt(poly_p<T, D, M> &out, poly_p<T, D, M> const &in, uint64_t k) {
+  poly_p<T, D, M>::automorphism_into(out, in, k, NFLHIP_FORM_NTT);
 }
 
 /* high level wrappers (poly.hpp:314-332) */

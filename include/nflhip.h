@@ -139,6 +139,28 @@ int nflhip_ntt_inv(nflhip_ctx *ctx, void *h_data, size_t batch);
 int nflhip_ntt_row_dev(nflhip_ctx *ctx, void *d_rows, size_t cm, int mode, size_t rows, void *stream);
 int nflhip_ntt_row(nflhip_ctx *ctx, void *h_rows, size_t cm, int mode, size_t rows);
 
+/* ---- Galois automorphisms ------------------------------------------------------------
+ * sigma_k : a(X) -> a(X^k) mod (X^n + 1) for odd k, taken mod 2n, on every row of [batch][nmoduli][degree] (the primitive
+ * behind slot rotations, conjugation (k = 2n - 1), traces and key switching to a Galois key).  n = degree, p = the row's modulus.
+ *   NFLHIP_FORM_COEFF  coefficient form, canonical words in [0,p) in and out: for i in [0,n), e = i k mod 2n,
+ *                      out[e] = in[i] when e < n, else out[e - n] = (p - in[i]) mod p (0 stays 0).
+ *   NFLHIP_FORM_NTT    the order nflhip_ntt_fwd_dev produces (slot j holds a(phi^(2 rev(j) + 1)), rev = the log2(n)-bit
+ *                      reversal): out[j] = in[j'] where 2 rev(j') + 1 = k (2 rev(j) + 1) mod 2n.  The stored words move
+ *                      unchanged, so ntt_inv(sigma_ntt(ntt_fwd(x))) == sigma_coeff(x) word for word.
+ * The multi form writes d_outs[m] = sigma_{ks[m]}(d_in) for m < count <= NFLHIP_AUTOMORPHISM_MAX_OUTPUTS and reads d_in
+ * once (hoisted rotations).  NFLHIP_ERR_INVALID: an even k, an unknown form, a count of 0 or above the maximum, a NULL
+ * pointer, or an output that overlaps the input or another output (the device entries never work in place).  The host
+ * variant stages both sides and accepts h_out == h_in (but no other overlap).  The _dev entries allocate nothing and do
+ * not synchronise: they can be captured into a hipGraph (the multi form's pointers and multipliers travel as kernel
+ * arguments). */
+#define NFLHIP_FORM_COEFF 0
+#define NFLHIP_FORM_NTT 1
+#define NFLHIP_AUTOMORPHISM_MAX_OUTPUTS 16
+int nflhip_automorphism_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, uint64_t k, int form, void *stream);
+int nflhip_automorphism(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, uint64_t k, int form);
+int nflhip_automorphism_multi_dev(nflhip_ctx *ctx, void *const *d_outs, const uint64_t *ks, size_t count, const void *d_in,
+                                  size_t batch, int form, void *stream);
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

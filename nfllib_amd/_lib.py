@@ -19,6 +19,8 @@ DIST_REFERENCE_WORDS = 0x100
 DIST_NARROW = 0x200
 ABI_VERSION = 6
 FMT_WORDS, FMT_I8, FMT_I16, FMT_I32 = range(4)
+FORM_COEFF, FORM_NTT = 0, 1
+AUTOMORPHISM_MAX_OUTPUTS = 16
 
 # every symbol include/nflhip.h declares: (name, restype, argtypes)
 _vp, _sz, _i, _u64 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint64
@@ -40,6 +42,9 @@ SYMBOLS = [
     ("nflhip_ntt_inv", _i, [_vp, _vp, _sz]),
     ("nflhip_ntt_row_dev", _i, [_vp, _vp, _sz, _i, _sz, _vp]),
     ("nflhip_ntt_row", _i, [_vp, _vp, _sz, _i, _sz]),
+    ("nflhip_automorphism_dev", _i, [_vp, _vp, _vp, _sz, _u64, _i, _vp]),
+    ("nflhip_automorphism", _i, [_vp, _vp, _vp, _sz, _u64, _i]),
+    ("nflhip_automorphism_multi_dev", _i, [_vp, _vp, C.POINTER(_u64), _sz, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     ("nflhip_eval_dev", _i, [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp]),

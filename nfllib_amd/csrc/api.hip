@@ -814,7 +814,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1093,6 +1093,46 @@ int nflhip_ntt_inv_dev(nflhip_ctx *ctx, void *d, size_t batch, void *stream) {
                  launch_ntt_inv<uint64_t>(ctx->shape, ctx->tabs, (const uint64_t *)d, nullptr, (uint64_t *)d, batch, st));
   if (e != hipSuccess) return hipfail(ctx, e, "ntt_inv");
   return NFLHIP_OK;
+}
+
+// Galois automorphisms (kernels_automorph.hip).  The arguments are checked in full before anything is enqueued.
+static bool bytes_overlap(const void *a, const void *b, size_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
+}
+static int automorphism_multi(nflhip_ctx *ctx, void *const *outs, const uint64_t *ks, size_t count, const void *in, size_t batch,
+                              int form, hipStream_t st) {
+  if (form != NFLHIP_FORM_COEFF && form != NFLHIP_FORM_NTT) return fail(ctx, NFLHIP_ERR_INVALID, "unknown polynomial form");
+  if (count == 0 || count > NFLHIP_AUTOMORPHISM_MAX_OUTPUTS) return fail(ctx, NFLHIP_ERR_INVALID, "output count out of range (1 to 16)");
+  if (!outs || !ks) return fail(ctx, NFLHIP_ERR_INVALID, "NULL output or multiplier array");
+  for (size_t m = 0; m < count; ++m)
+    if ((ks[m] & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism exponent k must be odd");
+  if (batch == 0) return NFLHIP_OK;
+  if (!in) return fail(ctx, NFLHIP_ERR_INVALID, "NULL input");
+  const size_t bytes = poly_bytes(ctx, batch);
+  for (size_t m = 0; m < count; ++m) {
+    if (!outs[m]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL output");
+    if (bytes_overlap(outs[m], in, bytes)) return fail(ctx, NFLHIP_ERR_INVALID, "an output overlaps the input");
+    for (size_t l = 0; l < m; ++l)
+      if (bytes_overlap(outs[m], outs[l], bytes)) return fail(ctx, NFLHIP_ERR_INVALID, "two outputs overlap");
+  }
+  const int ntt = form == NFLHIP_FORM_NTT, c = (int)count;
+  hipError_t e = DISPATCH_T(ctx,
+                            launch_automorphism<uint16_t>(ctx->shape, ctx->tabs, (uint16_t *const *)outs, ks, c, (const uint16_t *)in, ntt, batch, st),
+                            launch_automorphism<uint32_t>(ctx->shape, ctx->tabs, (uint32_t *const *)outs, ks, c, (const uint32_t *)in, ntt, batch, st),
+                            launch_automorphism<uint64_t>(ctx->shape, ctx->tabs, (uint64_t *const *)outs, ks, c, (const uint64_t *)in, ntt, batch, st));
+  if (e != hipSuccess) return hipfail(ctx, e, "automorphism");
+  return NFLHIP_OK;
+}
+int nflhip_automorphism_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, uint64_t k, int form, void *stream) {
+  CHECK_CTX(ctx);
+  void *outs[1] = {d_out};
+  return automorphism_multi(ctx, outs, &k, 1, d_in, batch, form, (hipStream_t)stream);
+}
+int nflhip_automorphism_multi_dev(nflhip_ctx *ctx, void *const *d_outs, const uint64_t *ks, size_t count, const void *d_in,
+                                  size_t batch, int form, void *stream) {
+  CHECK_CTX(ctx);
+  return automorphism_multi(ctx, d_outs, ks, count, d_in, batch, form, (hipStream_t)stream);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,
@@ -2296,6 +2336,27 @@ int nflhip_ntt_inv(nflhip_ctx *ctx, void *h, size_t batch) {
   rc = nflhip_ntt_inv_dev(ctx, ctx->stage[0], batch, ctx->hstream);
   if (rc) return rc;
   return s.out(h, 0, bytes);
+}
+int nflhip_automorphism(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, uint64_t k, int form) {
+  CHECK_CTX(ctx);
+  if (form != NFLHIP_FORM_COEFF && form != NFLHIP_FORM_NTT) return fail(ctx, NFLHIP_ERR_INVALID, "unknown polynomial form");
+  if ((k & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism exponent k must be odd");
+  if (batch == 0) return NFLHIP_OK;
+  if (!h_out || !h_in) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t bytes = poly_bytes(ctx, batch);
+  if (h_out != h_in && bytes_overlap(h_out, h_in, bytes)) return fail(ctx, NFLHIP_ERR_INVALID, "the output overlaps the input");
+  Staged s(ctx);
+  const void *ins[1] = {h_in};
+  int rc = run_pipelined(ctx, batch, ins, 1, h_out, [&](const void *const *d, void *o, size_t cnt, void *st) {
+    return nflhip_automorphism_dev(ctx, o, d[0], cnt, k, form, st);
+  });
+  if (rc != NFLHIP_ERR_UNSUPPORTED) return rc;
+  rc = s.in(0, h_in, bytes);
+  if (rc) return rc;
+  if ((rc = s.in(1, nullptr, bytes))) return rc;
+  rc = nflhip_automorphism_dev(ctx, ctx->stage[1], ctx->stage[0], batch, k, form, ctx->hstream);
+  if (rc) return rc;
+  return s.out(h_out, 1, bytes);
 }
 int nflhip_ntt_row(nflhip_ctx *ctx, void *h_rows, size_t cm, int mode, size_t rows) {
   CHECK_CTX(ctx);

@@ -96,6 +96,12 @@ hipError_t launch_check_range(const Shape &s, const DevTables &t, const T *d, si
 template <typename T>
 hipError_t launch_fill_uniform(const Shape &s, const DevTables &t, T *d, size_t first_poly, size_t batch, uint64_t seed,
                                int operand, hipStream_t st);
+// Galois automorphisms (kernels_automorph.hip): outs[m] = sigma_{ks[m]}(in) for m < count <= 16, every k odd; ntt_form selects the
+// NTT-form map (a permutation of the stored words) over the coefficient-form one (a signed permutation).  No output may overlap
+// the input or another output (api.hip checks).  hipErrorInvalidValue for an even k or a count out of range
+template <typename T>
+hipError_t launch_automorphism(const Shape &s, const DevTables &t, T *const *outs, const uint64_t *ks, int count, const T *in,
+                               int ntt_form, size_t batch, hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);
@@ -241,6 +247,7 @@ hipError_t warm_crt(hipStream_t st);
 hipError_t warm_crt_mfma(hipStream_t st);
 hipError_t warm_sample(hipStream_t st);
 hipError_t warm_wave(hipStream_t st);
+hipError_t warm_automorph(hipStream_t st);
 int polymul_level();   // 0 / 1 / 2: transforms of the coefficient-form products complete / incomplete (kernels_fast.hip, nflhip_debug_polymul_level)
 hipError_t launch_polymul_pipe64k_u64(const Shape &s, const DevTables &t, uint64_t *c_v, const uint64_t *a_v,
                                       const uint64_t *b_v, int cnt_v, const uint64_t *fa_src, uint64_t *fa_dst,

@@ -10,7 +10,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
+from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, FORM_COEFF, FORM_NTT,  # noqa: F401
+                   FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
                    TAB_SHOUPPHIS)
@@ -127,6 +128,38 @@ class Engine:
         out = np.ascontiguousarray(rows, dtype=self.np_dtype).copy()
         mode = (ROW_INVERSE_TABLES if inverse_tables else 0) | (ROW_BITREV_IO if bitrev_io else 0)
         self._chk(self.lib.nflhip_ntt_row(self.ctx, _vp(out), cm, mode, out.size // self.degree))
+        return out
+
+    # ---- Galois automorphisms sigma_k : a(X) -> a(X^k) mod (X^n + 1), k odd (include/nflhip.h "Galois automorphisms") ----
+    def _k(self, k):
+        """k reduced mod 2n (a negative k names the same automorphism as k mod 2n)"""
+        return int(k) % (2 * self.degree)
+
+    def automorphism(self, d, k, ntt=False, out=None, stream=None):
+        """sigma_k of every polynomial of d (coefficient form, or NTT form with ntt=True) into a new tensor or `out`,
+        which must not overlap d"""
+        out = out if out is not None else _torch().empty_like(d)
+        form = FORM_NTT if ntt else FORM_COEFF
+        self._chk(self.lib.nflhip_automorphism_dev(self.ctx, _vp(out), _vp(d), self._batch(d), self._k(k), form,
+                                                   self._stream(stream)))
+        return out
+
+    def automorphism_multi(self, d, ks, ntt=False, outs=None, stream=None):
+        """[sigma_k(d) for k in ks] in ONE launch that reads d once (at most 16 multipliers)"""
+        ks = [self._k(k) for k in ks]
+        outs = list(outs) if outs is not None else [_torch().empty_like(d) for _ in ks]
+        ptrs = (C.c_void_p * max(len(outs), 1))(*[o.data_ptr() for o in outs])
+        kv = (C.c_uint64 * max(len(ks), 1))(*ks)
+        form = FORM_NTT if ntt else FORM_COEFF
+        self._chk(self.lib.nflhip_automorphism_multi_dev(self.ctx, ptrs, kv, len(ks), _vp(d), self._batch(d), form,
+                                                         self._stream(stream)))
+        return outs
+
+    def h_automorphism(self, a, k, ntt=False):
+        """host-pointer variant: sigma_k of a numpy batch, staged through the context (nflhip_automorphism)"""
+        out = np.empty_like(a)
+        form = FORM_NTT if ntt else FORM_COEFF
+        self._chk(self.lib.nflhip_automorphism(self.ctx, _vp(out), _vp(a), self._hb(a), self._k(k), form))
         return out
 
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
