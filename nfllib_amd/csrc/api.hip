@@ -1,14 +1,11 @@
 // api.hip -- the C ABI of include/nflhip.h: context + device-table provisioning
-// and the host/device entry points.  No CPU compute path exists here: every
-// operation is a launch of a gfx950 kernel (kernels_generic.hip / kernels_fast.hip).
+// and the device-pointer entry points (the host-pointer ones stage through them: api_host.hip).  No CPU compute path exists
+// here: every operation is a launch of a gfx950 kernel (kernels_generic.hip / kernels_fast.hip).
 #include "../../include/nflhip.h"
 #include "../../include/nflhip_debug.h"
 
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -18,9 +15,9 @@
 #include <new>
 #include <stdexcept>
 #include <string>
-#include <thread>
 #include <vector>
 
+#include "ctx.h"
 #include "gauss_table.h"
 #include "kernels.h"
 
@@ -31,76 +28,12 @@ typedef unsigned __int128 u128;
 // errno-style: one message per calling thread, so concurrent callers of one context never race on it
 static thread_local std::string g_last_error = "";
 
-struct nflhip_ctx {
-  int device = 0;
-  Shape shape{};
-  DevTables tabs{};
-  size_t word = 8;  // bytes per limb
-  // host-pointer path: staging buffers + private stream, serialised by a mutex
-  std::mutex mu;
-  hipStream_t hstream = nullptr;
-  void *stage[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t stage_bytes[4] = {0, 0, 0, 0};
-  // a staging buffer of up to kStageHostMax bytes is PINNED HOST memory the kernels read and write directly (one polynomial per call, the
-  // nfl::poly surface: a 128 KiB operand crosses PCIe inside the kernel in less time than a copy engine needs to start); larger ones are device
-  // memory filled by copies
-  bool stage_host[4] = {false, false, false, false};
-  bool flag_host = false;          // tabs.flag is pinned host memory
-  // large host-pointer calls: a three-slot pipeline of pinned staging chunks (HostPipe below), created on first use
-  struct HostPipe *pipe = nullptr;
-  // scratch for the composed (non-fused) polymul path, per stream use is serialised by the caller
-  void *scratch = nullptr;
-  size_t scratch_bytes = 0;
-  std::mutex scratch_mu;
-  // large-row polymul pipeline: two helper streams so that the HBM-bound streaming passes of one
-  // chunk overlap the VALU-bound fused kernel of another; ev_prev orders successive calls on the scratch
-  hipStream_t aux[2] = {nullptr, nullptr};
-  hipEvent_t ev_start = nullptr, ev_done[2] = {nullptr, nullptr};
-  bool ev_prev_valid = false;
-  hipEvent_t ev_scratch = nullptr;  // end of the last single-stream pipeline that used the scratch
-  bool ev_scratch_valid = false;
-  // any_eq / any_neq: every call owns one result slot (device int) for its memset + kernel + readback, so host
-  // threads comparing on distinct streams never share a flag
-  static constexpr int kCmpSlots = 32;
-  std::mutex cmp_mu[kCmpSlots];
-  int cmp_token[kCmpSlots] = {};   // the token of the slot's latest comparison (under its mutex)
-  std::atomic<unsigned> cmp_next{0};
-  // host copies for introspection
-  std::vector<uint64_t> h_Q;                     // moduli_product limbs
-  std::vector<std::vector<uint64_t>> h_lifting;  // lifting_integers[cm]
-  std::vector<uint64_t> h_P;
-  std::vector<uint64_t> h_roots, h_invk, h_phi;  // params<T>::primitive_roots / invkMaxPolyDegree, phi = 2n-th root per modulus
-  int kmax_log2 = 0;
-  // core::ntt(x, wtab, winvtab, p) (core.hpp:455-532) on the device: one single-modulus child context per
-  // (modulus, table set) whose twiddle table is the CYCLIC one, created on first use -- see nflhip_ntt_row_dev
-  int cyclic = 0;  // 0: negacyclic tables (the normal context); 1 / 2: cyclic over omega / omega^-1 (child contexts)
-  std::mutex row_mu;
-  std::vector<nflhip_ctx *> row_ctx;  // [2 * cm + inverse_tables]
-};
-
 namespace nflhip {
-int set_error(int code, const std::string &msg) {  // for the library's other translation units (comm.hip)
+int set_error(int code, const std::string &msg) {  // (ctx.h fail, comm.hip)
   g_last_error = msg;
   return code;
 }
 }  // namespace nflhip
-
-static void pipe_destroy(nflhip_ctx *ctx);  // (HostPipe is defined with the host-pointer entry points)
-
-static int fail(const nflhip_ctx *ctx, int code, const std::string &msg) {
-  (void)ctx;
-  g_last_error = msg;
-  return code;
-}
-static int hipfail(const nflhip_ctx *ctx, hipError_t e, const char *where) {
-  return fail(ctx, e == hipErrorNoDevice || e == hipErrorInvalidDevice ? NFLHIP_ERR_NO_DEVICE : NFLHIP_ERR_HIP,
-              std::string(where) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(ctx, call)                                   \
-  do {                                                      \
-    hipError_t _e = (call);                                 \
-    if (_e != hipSuccess) return hipfail(ctx, _e, #call);   \
-  } while (0)
 
 // ---------------------------------------------------------------------------
 // host-side modular helpers used only to BUILD tables (once per context)
@@ -527,37 +460,15 @@ static int build_tables(nflhip_ctx *c, const void *Pv, const void *rootsv, const
 }
 
 // ---------------------------------------------------------------------------
-// dispatch on the limb type
+// dispatch on the limb type: f(T()) for the context's T = uint16_t / uint32_t / uint64_t
 // ---------------------------------------------------------------------------
-#define DISPATCH_T(ctx, EXPR16, EXPR32, EXPR64) \
-  ((ctx)->shape.limb_bits == 16 ? (EXPR16) : (ctx)->shape.limb_bits == 32 ? (EXPR32) : (EXPR64))
+template <typename F>
+static auto with_limb(const nflhip_ctx *ctx, F f) {
+  if (ctx->shape.limb_bits == 16) return f(uint16_t());
+  if (ctx->shape.limb_bits == 32) return f(uint32_t());
+  return f(uint64_t());
+}
 
-static int set_device(const nflhip_ctx *ctx) {
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  return NFLHIP_OK;
-}
-static size_t poly_bytes(const nflhip_ctx *ctx, size_t batch) { return batch * ctx->shape.nm * ctx->shape.n * ctx->word; }
-
-static constexpr size_t kStageHostMax = (size_t)1 << 20;
-static void free_stage(nflhip_ctx *ctx, int slot) {
-  if (ctx->stage[slot]) (void)(ctx->stage_host[slot] ? hipHostFree(ctx->stage[slot]) : hipFree(ctx->stage[slot]));
-  ctx->stage[slot] = nullptr;
-  ctx->stage_bytes[slot] = 0;
-  ctx->stage_host[slot] = false;
-}
-static int ensure_stage(nflhip_ctx *ctx, int slot, size_t bytes) {
-  if (ctx->stage_bytes[slot] >= bytes) return NFLHIP_OK;
-  free_stage(ctx, slot);
-  if (bytes <= kStageHostMax && hipHostMalloc(&ctx->stage[slot], bytes, hipHostMallocDefault) == hipSuccess) {
-    ctx->stage_host[slot] = true;
-  } else {   // (also when the pinned allocation is refused -- a locked-memory limit: the copies take over)
-    (void)hipGetLastError();
-    ctx->stage[slot] = nullptr;
-    HIPCHK(ctx, hipMalloc(&ctx->stage[slot], bytes));
-  }
-  ctx->stage_bytes[slot] = bytes;
-  return NFLHIP_OK;
-}
 static int ensure_scratch(nflhip_ctx *ctx, size_t bytes) {
   if (ctx->scratch_bytes >= bytes) return NFLHIP_OK;
   if (ctx->scratch) HIPCHK(ctx, hipFree(ctx->scratch));
@@ -776,14 +687,35 @@ static int polymul_composed(nflhip_ctx *ctx, T *c, const T *a, const T *b, int b
   return NFLHIP_OK;
 }
 
+// A comparison that ends in one flag: launch(z, flag, token) -- z the limb type's zero -- on a result slot of its own, then the
+// flag read back.  A hit stores the call's token, 1, 2, ... per slot: never the value the flag holds from an earlier call.
+template <typename F>
+static int flag_call(nflhip_ctx *ctx, hipStream_t st, const char *where, int *hit, F launch) {
+  const unsigned slot = ctx->cmp_next.fetch_add(1, std::memory_order_relaxed) % nflhip_ctx::kCmpSlots;
+  std::lock_guard<std::mutex> lk(ctx->cmp_mu[slot]);  // held until the readback below has completed
+  int *dflag = ctx->tabs.flag + slot, &last = ctx->cmp_token[slot];
+  if (last == 0x7fffffff) {   // wrap: clear the flag once, start over
+    last = 0;
+    if (ctx->flag_host) *dflag = 0;
+    else (void)hipMemsetAsync(dflag, 0, sizeof(int), st);
+  }
+  const int token = ++last;
+  hipError_t e = with_limb(ctx, [&](auto z) { return launch(z, dflag, token); });
+  if (e != hipSuccess) return hipfail(ctx, e, where);
+  int flag = 0;
+  if (!ctx->flag_host) HIPCHK(ctx, hipMemcpyAsync(&flag, ctx->tabs.flag + slot, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  if (ctx->flag_host) flag = *(volatile int *)dflag;
+  *hit = flag == token ? 1 : 0;
+  return NFLHIP_OK;
+}
+
 extern "C" {
 
 int nflhip_abi_version(void) { return NFLHIP_ABI_VERSION; }
 
 // include/nflhip_debug.h: test hooks, not part of the product boundary
 void nflhip_debug_gauss_tie_shift(int shift) { set_gauss_tie_shift(shift); }
-static void pipe_stats(const nflhip_ctx *ctx, double out[4]);
-void nflhip_debug_host_pipe_seconds(const nflhip_ctx *ctx, double out[4]) { pipe_stats(ctx, out); }
 
 const char *nflhip_last_error(const nflhip_ctx *ctx) {
   (void)ctx;
@@ -867,9 +799,7 @@ static int ctx_create_mode(nflhip_ctx **out, int device, int limb_bits, size_t d
   while ((((size_t)1) << c->shape.logn) < degree) c->shape.logn++;
   int rc;
   try {  // (host containers: no exception may cross the C boundary)
-    rc = limb_bits == 16   ? build_tables<uint16_t>(c, P, primitive_roots, invkmax, kmax_log2)
-         : limb_bits == 32 ? build_tables<uint32_t>(c, P, primitive_roots, invkmax, kmax_log2)
-                           : build_tables<uint64_t>(c, P, primitive_roots, invkmax, kmax_log2);
+    rc = with_limb(c, [&](auto z) { return build_tables<decltype(z)>(c, P, primitive_roots, invkmax, kmax_log2); });
   } catch (const std::bad_alloc &) {
     rc = fail(nullptr, NFLHIP_ERR_NOMEM, "out of host memory while building the tables");
   } catch (const std::exception &ex) {
@@ -1029,77 +959,47 @@ int nflhip_get_crt_constant(const nflhip_ctx *ctx, int what, size_t cm, uint64_t
 // ---------------------------------------------------------------------------
 // device-pointer entry points
 // ---------------------------------------------------------------------------
-#define CHECK_CTX(ctx)                                                \
-  do {                                                                \
-    if (!(ctx)) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL"); \
-    int _rc = set_device(ctx);                                        \
-    if (_rc) return _rc;                                              \
-  } while (0)
+// The generated fast kernels of a row family -- for 64-bit limbs the fast plans, then the 1024 / 2048-word rows; the rows of
+// 32-bit and of 16-bit limbs -- in mode 0: c = a b, 1: c = a b with b in NTT form, 2: c = NTT(a), 3: c = INTT(a).
+// NFLHIP_ERR_UNSUPPORTED: none serves the shape, the caller takes the generic path.
+static int fast_family(nflhip_ctx *ctx, int mode, void *c, const void *a, const void *b, size_t batch, hipStream_t st) {
+  const Shape &s = ctx->shape;
+  const DevTables &t = ctx->tabs;
+  hipError_t e;
+  if (s.limb_bits == 64) {
+    e = mode == 2 ? launch_ntt_fwd_fast_u64(s, t, (const uint64_t *)a, (uint64_t *)c, batch, st)
+      : mode == 3 ? launch_ntt_inv_fast_u64(s, t, (const uint64_t *)a, (uint64_t *)c, batch, st)
+                  : launch_polymul_fast_u64(s, t, (uint64_t *)c, (const uint64_t *)a, (const uint64_t *)b, mode, batch, st);
+    if (e == hipErrorNotSupported) e = launch_row1024_u64(s, t, mode, (uint64_t *)c, (const uint64_t *)a, (const uint64_t *)b, batch, st);
+  } else if (s.limb_bits == 32) {
+    e = launch_row1024_u32(s, t, mode, (uint32_t *)c, (const uint32_t *)a, (const uint32_t *)b, batch, st);
+  } else {
+    e = launch_row128_u16_asm(s, t, mode, (uint16_t *)c, (const uint16_t *)a, (const uint16_t *)b, batch, st);
+  }
+  if (e == hipSuccess) return NFLHIP_OK;
+  if (e == hipErrorNotSupported) return NFLHIP_ERR_UNSUPPORTED;
+  static const char *const op[4] = {"polymul", "polymul", "ntt_fwd", "ntt_inv"};
+  return hipfail(ctx, e, (std::string(op[mode]) + (s.limb_bits == 64 ? "(fast)" : s.limb_bits == 32 ? "(u32)" : "(u16)")).c_str());
+}
 
-int nflhip_ntt_fwd_dev(nflhip_ctx *ctx, void *d, size_t batch, void *stream) {
+static int ntt_dev(nflhip_ctx *ctx, int inverse, void *d, size_t batch, void *stream) {
   CHECK_CTX(ctx);
   if (!d && batch) return fail(ctx, NFLHIP_ERR_INVALID, "NULL data pointer");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  if (ctx->shape.limb_bits == 64) {
-    e = launch_ntt_fwd_fast_u64(ctx->shape, ctx->tabs, (const uint64_t *)d, (uint64_t *)d, batch, st);
-    if (e == hipErrorNotSupported)
-      e = launch_row1024_u64(ctx->shape, ctx->tabs, 2, (uint64_t *)d, (const uint64_t *)d, nullptr, batch, st);
-    if (e == hipSuccess) return NFLHIP_OK;
-    if (e != hipErrorNotSupported) return hipfail(ctx, e, "ntt_fwd(fast)");
-  }
-  if (ctx->shape.limb_bits == 32) {
-    e = launch_row1024_u32(ctx->shape, ctx->tabs, 2, (uint32_t *)d, (const uint32_t *)d, nullptr, batch, st);
-    if (e == hipSuccess) return NFLHIP_OK;
-    if (e != hipErrorNotSupported) return hipfail(ctx, e, "ntt_fwd(u32)");
-  }
-  if (ctx->shape.limb_bits == 16) {
-    e = launch_row128_u16_asm(ctx->shape, ctx->tabs, 2, (uint16_t *)d, (const uint16_t *)d, nullptr, batch, st);
-    if (e == hipSuccess) return NFLHIP_OK;
-    if (e != hipErrorNotSupported) return hipfail(ctx, e, "ntt_fwd(u16)");
-  }
-  e = DISPATCH_T(ctx, launch_ntt_fwd<uint16_t>(ctx->shape, ctx->tabs, (const uint16_t *)d, (uint16_t *)d, batch, st),
-                 launch_ntt_fwd<uint32_t>(ctx->shape, ctx->tabs, (const uint32_t *)d, (uint32_t *)d, batch, st),
-                 launch_ntt_fwd<uint64_t>(ctx->shape, ctx->tabs, (const uint64_t *)d, (uint64_t *)d, batch, st));
-  if (e != hipSuccess) return hipfail(ctx, e, "ntt_fwd");
+  const int rc = fast_family(ctx, inverse ? 3 : 2, d, d, nullptr, batch, st);
+  if (rc != NFLHIP_ERR_UNSUPPORTED) return rc;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return inverse ? launch_ntt_inv<T>(ctx->shape, ctx->tabs, (const T *)d, nullptr, (T *)d, batch, st)
+                   : launch_ntt_fwd<T>(ctx->shape, ctx->tabs, (const T *)d, (T *)d, batch, st);
+  });
+  if (e != hipSuccess) return hipfail(ctx, e, inverse ? "ntt_inv" : "ntt_fwd");
   return NFLHIP_OK;
 }
-
-int nflhip_ntt_inv_dev(nflhip_ctx *ctx, void *d, size_t batch, void *stream) {
-  CHECK_CTX(ctx);
-  if (!d && batch) return fail(ctx, NFLHIP_ERR_INVALID, "NULL data pointer");
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  if (ctx->shape.limb_bits == 64) {
-    e = launch_ntt_inv_fast_u64(ctx->shape, ctx->tabs, (const uint64_t *)d, (uint64_t *)d, batch, st);
-    if (e == hipErrorNotSupported)
-      e = launch_row1024_u64(ctx->shape, ctx->tabs, 3, (uint64_t *)d, (const uint64_t *)d, nullptr, batch, st);
-    if (e == hipSuccess) return NFLHIP_OK;
-    if (e != hipErrorNotSupported) return hipfail(ctx, e, "ntt_inv(fast)");
-  }
-  if (ctx->shape.limb_bits == 32) {
-    e = launch_row1024_u32(ctx->shape, ctx->tabs, 3, (uint32_t *)d, (const uint32_t *)d, nullptr, batch, st);
-    if (e == hipSuccess) return NFLHIP_OK;
-    if (e != hipErrorNotSupported) return hipfail(ctx, e, "ntt_inv(u32)");
-  }
-  if (ctx->shape.limb_bits == 16) {
-    e = launch_row128_u16_asm(ctx->shape, ctx->tabs, 3, (uint16_t *)d, (const uint16_t *)d, nullptr, batch, st);
-    if (e == hipSuccess) return NFLHIP_OK;
-    if (e != hipErrorNotSupported) return hipfail(ctx, e, "ntt_inv(u16)");
-  }
-  e = DISPATCH_T(ctx,
-                 launch_ntt_inv<uint16_t>(ctx->shape, ctx->tabs, (const uint16_t *)d, nullptr, (uint16_t *)d, batch, st),
-                 launch_ntt_inv<uint32_t>(ctx->shape, ctx->tabs, (const uint32_t *)d, nullptr, (uint32_t *)d, batch, st),
-                 launch_ntt_inv<uint64_t>(ctx->shape, ctx->tabs, (const uint64_t *)d, nullptr, (uint64_t *)d, batch, st));
-  if (e != hipSuccess) return hipfail(ctx, e, "ntt_inv");
-  return NFLHIP_OK;
-}
+int nflhip_ntt_fwd_dev(nflhip_ctx *ctx, void *d, size_t batch, void *stream) { return ntt_dev(ctx, 0, d, batch, stream); }
+int nflhip_ntt_inv_dev(nflhip_ctx *ctx, void *d, size_t batch, void *stream) { return ntt_dev(ctx, 1, d, batch, stream); }
 
 // Galois automorphisms (kernels_automorph.hip).  The arguments are checked in full before anything is enqueued.
-static bool bytes_overlap(const void *a, const void *b, size_t bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bytes && y < x + bytes;
-}
 static int automorphism_multi(nflhip_ctx *ctx, void *const *outs, const uint64_t *ks, size_t count, const void *in, size_t batch,
                               int form, hipStream_t st) {
   if (form != NFLHIP_FORM_COEFF && form != NFLHIP_FORM_NTT) return fail(ctx, NFLHIP_ERR_INVALID, "unknown polynomial form");
@@ -1117,10 +1017,10 @@ static int automorphism_multi(nflhip_ctx *ctx, void *const *outs, const uint64_t
       if (bytes_overlap(outs[m], outs[l], bytes)) return fail(ctx, NFLHIP_ERR_INVALID, "two outputs overlap");
   }
   const int ntt = form == NFLHIP_FORM_NTT, c = (int)count;
-  hipError_t e = DISPATCH_T(ctx,
-                            launch_automorphism<uint16_t>(ctx->shape, ctx->tabs, (uint16_t *const *)outs, ks, c, (const uint16_t *)in, ntt, batch, st),
-                            launch_automorphism<uint32_t>(ctx->shape, ctx->tabs, (uint32_t *const *)outs, ks, c, (const uint32_t *)in, ntt, batch, st),
-                            launch_automorphism<uint64_t>(ctx->shape, ctx->tabs, (uint64_t *const *)outs, ks, c, (const uint64_t *)in, ntt, batch, st));
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_automorphism<T>(ctx->shape, ctx->tabs, (T *const *)outs, ks, c, (const T *)in, ntt, batch, st);
+  });
   if (e != hipSuccess) return hipfail(ctx, e, "automorphism");
   return NFLHIP_OK;
 }
@@ -1142,14 +1042,10 @@ int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const 
   if (batch && (!o || !a || (op != NFLHIP_OP_COMPUTE_SHOUP && !b) || (op == NFLHIP_OP_MUL_SHOUP && !bp)))
     return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = DISPATCH_T(
-      ctx,
-      launch_pointwise<uint16_t>(ctx->shape, ctx->tabs, op, (uint16_t *)o, (const uint16_t *)a, (const uint16_t *)b,
-                                 (const uint16_t *)bp, batch, st),
-      launch_pointwise<uint32_t>(ctx->shape, ctx->tabs, op, (uint32_t *)o, (const uint32_t *)a, (const uint32_t *)b,
-                                 (const uint32_t *)bp, batch, st),
-      launch_pointwise<uint64_t>(ctx->shape, ctx->tabs, op, (uint64_t *)o, (const uint64_t *)a, (const uint64_t *)b,
-                                 (const uint64_t *)bp, batch, st));
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_pointwise<T>(ctx->shape, ctx->tabs, op, (T *)o, (const T *)a, (const T *)b, (const T *)bp, batch, st);
+  });
   if (e != hipSuccess) return hipfail(ctx, e, "pointwise");
   return NFLHIP_OK;
 }
@@ -1157,10 +1053,10 @@ int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const 
 static int eval_dev(nflhip_ctx *ctx, void *out, const void *const *ops, size_t nops, const unsigned char *prog, size_t len,
                     size_t batch, void *stream, const unsigned *strides = nullptr, unsigned out_stride = 1) {
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = DISPATCH_T(
-      ctx, launch_eval_expr<uint16_t>(ctx->shape, ctx->tabs, (uint16_t *)out, ops, (int)nops, prog, (int)len, batch, st, strides, out_stride),
-      launch_eval_expr<uint32_t>(ctx->shape, ctx->tabs, (uint32_t *)out, ops, (int)nops, prog, (int)len, batch, st, strides, out_stride),
-      launch_eval_expr<uint64_t>(ctx->shape, ctx->tabs, (uint64_t *)out, ops, (int)nops, prog, (int)len, batch, st, strides, out_stride));
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_eval_expr<T>(ctx->shape, ctx->tabs, (T *)out, ops, (int)nops, prog, (int)len, batch, st, strides, out_stride);
+  });
   if (e == hipErrorInvalidValue) return fail(ctx, NFLHIP_ERR_INVALID, "malformed expression program");
   if (e == hipErrorNotSupported) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "row shorter than one 16-byte vector");
   if (e != hipSuccess) return hipfail(ctx, e, "eval");
@@ -1172,29 +1068,12 @@ static int polymul_any(nflhip_ctx *ctx, void *c, const void *a, const void *b, i
   if (batch && (!c || !a || !b)) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
   if (batch == 0) return NFLHIP_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (ctx->shape.limb_bits == 64) {
-    hipError_t e = launch_polymul_fast_u64(ctx->shape, ctx->tabs, (uint64_t *)c, (const uint64_t *)a, (const uint64_t *)b,
-                                           b_is_ntt, batch, st);
-    if (e == hipErrorNotSupported)
-      e = launch_row1024_u64(ctx->shape, ctx->tabs, b_is_ntt ? 1 : 0, (uint64_t *)c, (const uint64_t *)a, (const uint64_t *)b,
-                             batch, st);
-    if (e == hipSuccess) return NFLHIP_OK;
-    if (e != hipErrorNotSupported) return hipfail(ctx, e, "polymul(fast)");
-  }
-  if (ctx->shape.limb_bits == 32) {
-    hipError_t e = launch_row1024_u32(ctx->shape, ctx->tabs, b_is_ntt ? 1 : 0, (uint32_t *)c, (const uint32_t *)a,
-                                      (const uint32_t *)b, batch, st);
-    if (e == hipSuccess) return NFLHIP_OK;
-    if (e != hipErrorNotSupported) return hipfail(ctx, e, "polymul(u32)");
-  }
-  if (ctx->shape.limb_bits == 16) {
-    hipError_t e = launch_row128_u16_asm(ctx->shape, ctx->tabs, b_is_ntt ? 1 : 0, (uint16_t *)c, (const uint16_t *)a, (const uint16_t *)b, batch, st);
-    if (e == hipSuccess) return NFLHIP_OK;
-    if (e != hipErrorNotSupported) return hipfail(ctx, e, "polymul(u16)");
-  }
-  return DISPATCH_T(ctx, polymul_composed<uint16_t>(ctx, (uint16_t *)c, (const uint16_t *)a, (const uint16_t *)b, b_is_ntt, batch, st),
-                    polymul_composed<uint32_t>(ctx, (uint32_t *)c, (const uint32_t *)a, (const uint32_t *)b, b_is_ntt, batch, st),
-                    polymul_composed<uint64_t>(ctx, (uint64_t *)c, (const uint64_t *)a, (const uint64_t *)b, b_is_ntt, batch, st));
+  const int rc = fast_family(ctx, b_is_ntt ? 1 : 0, c, a, b, batch, st);
+  if (rc != NFLHIP_ERR_UNSUPPORTED) return rc;
+  return with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return polymul_composed<T>(ctx, (T *)c, (const T *)a, (const T *)b, b_is_ntt, batch, st);
+  });
 }
 
 int nflhip_eval_dev(nflhip_ctx *ctx, void *d_out, const void *const *d_operands, size_t noperands,
@@ -1245,9 +1124,10 @@ static int check_operand(const nflhip_ctx *ctx, const nflhip_operand *o, size_t 
 }
 
 static hipError_t expand_any(nflhip_ctx *ctx, void *dst, const nflhip_operand *src, size_t batch, hipStream_t st) {
-  return DISPATCH_T(ctx, launch_expand_small<uint16_t>(ctx->shape, ctx->tabs, (uint16_t *)dst, src->ptr, src->format, (unsigned)src->stride, batch, st),
-                    launch_expand_small<uint32_t>(ctx->shape, ctx->tabs, (uint32_t *)dst, src->ptr, src->format, (unsigned)src->stride, batch, st),
-                    launch_expand_small<uint64_t>(ctx->shape, ctx->tabs, (uint64_t *)dst, src->ptr, src->format, (unsigned)src->stride, batch, st));
+  return with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_expand_small<T>(ctx->shape, ctx->tabs, (T *)dst, src->ptr, src->format, (unsigned)src->stride, batch, st);
+  });
 }
 
 // out0 of a two-result call lies over (part of) an input of the SECOND result (k1 or e1): the one aliasing in which a plan that
@@ -1477,69 +1357,23 @@ int nflhip_expand_small_dev(nflhip_ctx *ctx, void *d_data, const nflhip_operand 
   return NFLHIP_OK;
 }
 
-// the token of the next comparison on a slot (its mutex held): 1, 2, ... -- never the value the flag holds from an earlier call
-static int next_cmp_token(nflhip_ctx *ctx, unsigned slot, hipStream_t st) {
-  int &tok = ctx->cmp_token[slot];
-  if (tok == 0x7fffffff) {   // wrap: clear the flag once, start over
-    tok = 0;
-    if (ctx->flag_host) ctx->tabs.flag[slot] = 0;
-    else (void)hipMemsetAsync(ctx->tabs.flag + slot, 0, sizeof(int), st);
-  }
-  return ++tok;
-}
-static int read_cmp_flag(nflhip_ctx *ctx, unsigned slot, int token, hipStream_t st, int *hit) {
-  int flag = 0;
-  if (!ctx->flag_host) HIPCHK(ctx, hipMemcpyAsync(&flag, ctx->tabs.flag + slot, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  if (ctx->flag_host) flag = *(volatile int *)(ctx->tabs.flag + slot);
-  *hit = flag == token ? 1 : 0;
-  return NFLHIP_OK;
-}
-
 static int any_cmp_dev(nflhip_ctx *ctx, const void *a, const void *b, size_t batch, int want_eq, int *result, void *stream) {
   CHECK_CTX(ctx);
   if (!result || (batch && (!a || !b))) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
   hipStream_t st = (hipStream_t)stream;
-  const unsigned slot = ctx->cmp_next.fetch_add(1, std::memory_order_relaxed) % nflhip_ctx::kCmpSlots;
-  std::lock_guard<std::mutex> lk(ctx->cmp_mu[slot]);  // held until the readback below has completed
-  int *dflag = ctx->tabs.flag + slot;
-  const int token = next_cmp_token(ctx, slot, st);
-  hipError_t e = DISPATCH_T(
-      ctx, launch_any_cmp<uint16_t>(ctx->shape, ctx->tabs, (const uint16_t *)a, (const uint16_t *)b, batch, want_eq, dflag, token, st),
-      launch_any_cmp<uint32_t>(ctx->shape, ctx->tabs, (const uint32_t *)a, (const uint32_t *)b, batch, want_eq, dflag, token, st),
-      launch_any_cmp<uint64_t>(ctx->shape, ctx->tabs, (const uint64_t *)a, (const uint64_t *)b, batch, want_eq, dflag, token, st));
-  if (e != hipSuccess) return hipfail(ctx, e, "any_cmp");
-  return read_cmp_flag(ctx, slot, token, st, result);
+  return flag_call(ctx, st, "any_cmp", result, [&](auto z, int *flag, int token) {
+    typedef decltype(z) T;
+    return launch_any_cmp<T>(ctx->shape, ctx->tabs, (const T *)a, (const T *)b, batch, want_eq, flag, token, st);
+  });
 }
 int nflhip_check_range_dev(nflhip_ctx *ctx, const void *d_data, size_t batch, int *bad, void *stream) {
   CHECK_CTX(ctx);
   if (!bad || (batch && !d_data)) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
   hipStream_t st = (hipStream_t)stream;
-  const unsigned slot = ctx->cmp_next.fetch_add(1, std::memory_order_relaxed) % nflhip_ctx::kCmpSlots;
-  std::lock_guard<std::mutex> lk(ctx->cmp_mu[slot]);  // held until the readback below has completed
-  int *dflag = ctx->tabs.flag + slot;
-  const int token = next_cmp_token(ctx, slot, st);
-  hipError_t e = DISPATCH_T(ctx, launch_check_range<uint16_t>(ctx->shape, ctx->tabs, (const uint16_t *)d_data, batch, dflag, token, st),
-                            launch_check_range<uint32_t>(ctx->shape, ctx->tabs, (const uint32_t *)d_data, batch, dflag, token, st),
-                            launch_check_range<uint64_t>(ctx->shape, ctx->tabs, (const uint64_t *)d_data, batch, dflag, token, st));
-  if (e != hipSuccess) return hipfail(ctx, e, "check_range");
-  return read_cmp_flag(ctx, slot, token, st, bad);
-}
-
-int nflhip_check_range(const nflhip_ctx *ctx, const void *h_data, size_t batch, int *bad) {
-  // host words against the host copy of the moduli: an assertion about the CALLER's data, nothing is computed
-  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
-  if (!bad || (batch && !h_data)) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
-  const size_t n = ctx->shape.n, nm = ctx->shape.nm;
-  int hit = 0;
-  for (size_t r = 0; r < batch * nm && !hit; ++r) {
-    const uint64_t p = ctx->h_P[r % nm];
-    if (ctx->word == 8) { const uint64_t *w = (const uint64_t *)h_data + r * n; for (size_t i = 0; i < n; ++i) hit |= w[i] >= p; }
-    else if (ctx->word == 4) { const uint32_t *w = (const uint32_t *)h_data + r * n; for (size_t i = 0; i < n; ++i) hit |= w[i] >= p; }
-    else { const uint16_t *w = (const uint16_t *)h_data + r * n; for (size_t i = 0; i < n; ++i) hit |= w[i] >= p; }
-  }
-  *bad = hit ? 1 : 0;
-  return NFLHIP_OK;
+  return flag_call(ctx, st, "check_range", bad, [&](auto z, int *flag, int token) {
+    typedef decltype(z) T;
+    return launch_check_range<T>(ctx->shape, ctx->tabs, (const T *)d_data, batch, flag, token, st);
+  });
 }
 
 int nflhip_any_eq_dev(nflhip_ctx *ctx, const void *a, const void *b, size_t batch, int *result, void *stream) {
@@ -1558,16 +1392,18 @@ int nflhip_crt_lift_dev(nflhip_ctx *ctx, uint64_t *limbs, const void *d, size_t 
     uint64_t *scr = nullptr;
     const size_t words = batch * ctx->shape.n * (size_t)ctx->tabs.crt_Lw;
     HIPCHK(ctx, hipMallocAsync((void **)&scr, words * sizeof(uint64_t), st));
-    hipError_t we = DISPATCH_T(ctx, launch_crt_lift_wide<uint16_t>(ctx->shape, ctx->tabs, limbs, (const uint16_t *)d, batch, scr, st),
-                               launch_crt_lift_wide<uint32_t>(ctx->shape, ctx->tabs, limbs, (const uint32_t *)d, batch, scr, st),
-                               launch_crt_lift_wide<uint64_t>(ctx->shape, ctx->tabs, limbs, (const uint64_t *)d, batch, scr, st));
+    hipError_t we = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_crt_lift_wide<T>(ctx->shape, ctx->tabs, limbs, (const T *)d, batch, scr, st);
+    });
     (void)hipFreeAsync(scr, st);
     if (we != hipSuccess) return hipfail(ctx, we, "crt_lift (wide)");
     return NFLHIP_OK;
   }
-  hipError_t e = DISPATCH_T(ctx, launch_crt_lift<uint16_t>(ctx->shape, ctx->tabs, limbs, (const uint16_t *)d, batch, st),
-                            launch_crt_lift<uint32_t>(ctx->shape, ctx->tabs, limbs, (const uint32_t *)d, batch, st),
-                            launch_crt_lift<uint64_t>(ctx->shape, ctx->tabs, limbs, (const uint64_t *)d, batch, st));
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_crt_lift<T>(ctx->shape, ctx->tabs, limbs, (const T *)d, batch, st);
+  });
   if (e == hipErrorNotSupported) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "crt_lift: more than 32 moduli");
   if (e != hipSuccess) return hipfail(ctx, e, "crt_lift");
   return NFLHIP_OK;
@@ -1578,9 +1414,10 @@ int nflhip_crt_project_dev(nflhip_ctx *ctx, void *d, const uint64_t *limbs, size
   if (batch && (!limbs || !d)) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
   if (L_in == 0 || L_in > (1u << 20)) return fail(ctx, NFLHIP_ERR_INVALID, "L_in out of range");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = DISPATCH_T(ctx, launch_crt_project<uint16_t>(ctx->shape, ctx->tabs, (uint16_t *)d, limbs, L_in, batch, st),
-                            launch_crt_project<uint32_t>(ctx->shape, ctx->tabs, (uint32_t *)d, limbs, L_in, batch, st),
-                            launch_crt_project<uint64_t>(ctx->shape, ctx->tabs, (uint64_t *)d, limbs, L_in, batch, st));
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_crt_project<T>(ctx->shape, ctx->tabs, (T *)d, limbs, L_in, batch, st);
+  });
   if (e != hipSuccess) return hipfail(ctx, e, "crt_project");
   return NFLHIP_OK;
 }
@@ -1590,9 +1427,10 @@ int nflhip_fill_uniform_dev(nflhip_ctx *ctx, void *d, size_t first_poly, size_t 
   CHECK_CTX(ctx);
   if (batch && !d) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = DISPATCH_T(ctx, launch_fill_uniform<uint16_t>(ctx->shape, ctx->tabs, (uint16_t *)d, first_poly, batch, seed, operand, st),
-                            launch_fill_uniform<uint32_t>(ctx->shape, ctx->tabs, (uint32_t *)d, first_poly, batch, seed, operand, st),
-                            launch_fill_uniform<uint64_t>(ctx->shape, ctx->tabs, (uint64_t *)d, first_poly, batch, seed, operand, st));
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_fill_uniform<T>(ctx->shape, ctx->tabs, (T *)d, first_poly, batch, seed, operand, st);
+  });
   if (e != hipSuccess) return hipfail(ctx, e, "fill_uniform");
   return NFLHIP_OK;
 }
@@ -1637,10 +1475,10 @@ int nflhip_sample_dev(nflhip_ctx *ctx, void *d, size_t first_poly, size_t batch,
   if (dist == NFLHIP_DIST_HWT && (p0 == 0 || p0 > ctx->shape.n))  // assert at core.hpp:349
     return fail(ctx, NFLHIP_ERR_INVALID, "hamming weight must be in [1, degree]");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = DISPATCH_T(
-      ctx, launch_sample<uint16_t>(ctx->shape, ctx->tabs, (uint16_t *)d, first_poly, batch, dist_in, p0, p1, key, stream_id, st),
-      launch_sample<uint32_t>(ctx->shape, ctx->tabs, (uint32_t *)d, first_poly, batch, dist_in, p0, p1, key, stream_id, st),
-      launch_sample<uint64_t>(ctx->shape, ctx->tabs, (uint64_t *)d, first_poly, batch, dist_in, p0, p1, key, stream_id, st));
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_sample<T>(ctx->shape, ctx->tabs, (T *)d, first_poly, batch, dist_in, p0, p1, key, stream_id, st);
+  });
   if (e != hipSuccess) return hipfail(ctx, e, "sample");
   return NFLHIP_OK;
 }
@@ -1652,10 +1490,10 @@ int nflhip_sample_seq_dev(nflhip_ctx *ctx, void *d, size_t batch, int dist, uint
   if (rc) return rc;
   if (batch && !d) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = DISPATCH_T(
-      ctx, launch_sample<uint16_t>(ctx->shape, ctx->tabs, (uint16_t *)d, 0, batch, dist, p0, p1, key, first_stream_id, st, 1, stream_id_stride),
-      launch_sample<uint32_t>(ctx->shape, ctx->tabs, (uint32_t *)d, 0, batch, dist, p0, p1, key, first_stream_id, st, 1, stream_id_stride),
-      launch_sample<uint64_t>(ctx->shape, ctx->tabs, (uint64_t *)d, 0, batch, dist, p0, p1, key, first_stream_id, st, 1, stream_id_stride));
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_sample<T>(ctx->shape, ctx->tabs, (T *)d, 0, batch, dist, p0, p1, key, first_stream_id, st, 1, stream_id_stride);
+  });
   if (e == hipErrorNotSupported) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "sequence mode needs degree >= 8");
   if (e != hipSuccess) return hipfail(ctx, e, "sample_seq");
   return NFLHIP_OK;
@@ -1670,11 +1508,10 @@ int nflhip_sample_gauss_seq_dev(nflhip_ctx *ctx, void *d, size_t batch, const nf
   hipStream_t st = (hipStream_t)stream;
   const int w = g->tab.words, en = (int)g->tab.entries;
   const long long x0 = g->tab.x_min;
-  hipError_t e = DISPATCH_T(
-      ctx,
-      launch_sample_gauss<uint16_t>(ctx->shape, ctx->tabs, (uint16_t *)d, 0, batch, g->d_cdt, w, en, x0, amplifier, key, first_stream_id, st, 1, stream_id_stride, gauss_narrow(g), g->d_lut),
-      launch_sample_gauss<uint32_t>(ctx->shape, ctx->tabs, (uint32_t *)d, 0, batch, g->d_cdt, w, en, x0, amplifier, key, first_stream_id, st, 1, stream_id_stride, gauss_narrow(g), g->d_lut),
-      launch_sample_gauss<uint64_t>(ctx->shape, ctx->tabs, (uint64_t *)d, 0, batch, g->d_cdt, w, en, x0, amplifier, key, first_stream_id, st, 1, stream_id_stride, gauss_narrow(g), g->d_lut));
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_sample_gauss<T>(ctx->shape, ctx->tabs, (T *)d, 0, batch, g->d_cdt, w, en, x0, amplifier, key, first_stream_id, st, 1, stream_id_stride, gauss_narrow(g), g->d_lut);
+  });
   if (e == hipErrorNotSupported) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "sequence mode needs degree >= 8 (>= 16 under the 32-bit draw)");
   if (e != hipSuccess) return hipfail(ctx, e, "sample_gauss_seq");
   return NFLHIP_OK;
@@ -1684,6 +1521,8 @@ int nflhip_sample_gauss_seq_dev(nflhip_ctx *ctx, void *d, size_t batch, const nf
 // generator: the header's FastGaussianNoise asks for it when it is CONSTRUCTED (nflhip_gauss_table with no output buffer) -- where the
 // reference builds its MPFR table -- so that the first polynomial drawn from it does not carry the construction
 static int cached_gauss_table(double sigma, unsigned security, unsigned samples, double center, GaussTable *out, std::string *err) {
+  // (checked before the lookup: a NaN compares equivalent to every key)
+  if (check_gauss_params(sigma, security, samples, center, err)) return 1;
   typedef std::tuple<double, unsigned, unsigned, double> Key;
   static std::mutex mu;
   static std::map<Key, std::shared_ptr<const GaussTable>> cache;
@@ -1793,11 +1632,10 @@ int nflhip_sample_gauss_dev(nflhip_ctx *ctx, void *d, size_t first_poly, size_t 
   hipStream_t st = (hipStream_t)stream;
   const int w = g->tab.words, en = (int)g->tab.entries;
   const long long x0 = g->tab.x_min;
-  hipError_t e = DISPATCH_T(
-      ctx,
-      launch_sample_gauss<uint16_t>(ctx->shape, ctx->tabs, (uint16_t *)d, first_poly, batch, g->d_cdt, w, en, x0, amplifier, key, stream_id, st, 0, 0, gauss_narrow(g), g->d_lut),
-      launch_sample_gauss<uint32_t>(ctx->shape, ctx->tabs, (uint32_t *)d, first_poly, batch, g->d_cdt, w, en, x0, amplifier, key, stream_id, st, 0, 0, gauss_narrow(g), g->d_lut),
-      launch_sample_gauss<uint64_t>(ctx->shape, ctx->tabs, (uint64_t *)d, first_poly, batch, g->d_cdt, w, en, x0, amplifier, key, stream_id, st, 0, 0, gauss_narrow(g), g->d_lut));
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_sample_gauss<T>(ctx->shape, ctx->tabs, (T *)d, first_poly, batch, g->d_cdt, w, en, x0, amplifier, key, stream_id, st, 0, 0, gauss_narrow(g), g->d_lut);
+  });
   if (e != hipSuccess) return hipfail(ctx, e, "sample_gauss");
   return NFLHIP_OK;
 }
@@ -1880,15 +1718,12 @@ static int row_child(nflhip_ctx *ctx, size_t cm, int inverse_tables, nflhip_ctx 
   if (ctx->row_ctx.empty()) ctx->row_ctx.assign(2 * ctx->shape.nm, nullptr);
   nflhip_ctx *&slot = ctx->row_ctx[2 * cm + (inverse_tables ? 1 : 0)];
   if (!slot) {
-    // one word of each parameter table, in the limb type's own width
-    uint64_t P8 = ctx->h_P[cm], R8 = ctx->h_roots[cm], I8 = ctx->h_invk[cm];
-    uint32_t P4 = (uint32_t)P8, R4 = (uint32_t)R8, I4 = (uint32_t)I8;
-    uint16_t P2 = (uint16_t)P8, R2 = (uint16_t)R8, I2 = (uint16_t)I8;
-    const void *pp = ctx->word == 8 ? (const void *)&P8 : ctx->word == 4 ? (const void *)&P4 : (const void *)&P2;
-    const void *rr = ctx->word == 8 ? (const void *)&R8 : ctx->word == 4 ? (const void *)&R4 : (const void *)&R2;
-    const void *ii = ctx->word == 8 ? (const void *)&I8 : ctx->word == 4 ? (const void *)&I4 : (const void *)&I2;
-    int rc = ctx_create_mode(&slot, ctx->device, ctx->shape.limb_bits, ctx->shape.n, 1, pp, rr, ii, ctx->kmax_log2,
+    const int rc = with_limb(ctx, [&](auto z) {   // one word of each parameter table, in the limb type's own width
+      typedef decltype(z) T;
+      const T p = (T)ctx->h_P[cm], root = (T)ctx->h_roots[cm], invk = (T)ctx->h_invk[cm];
+      return ctx_create_mode(&slot, ctx->device, ctx->shape.limb_bits, ctx->shape.n, 1, &p, &root, &invk, ctx->kmax_log2,
                              inverse_tables ? 2 : 1);
+    });
     if (rc) return rc;
   }
   *out = slot;
@@ -1904,22 +1739,18 @@ int nflhip_ntt_row_dev(nflhip_ctx *ctx, void *d_rows, size_t cm, int mode, size_
   nflhip_ctx *child = nullptr;
   int rc = row_child(ctx, cm, mode & NFLHIP_ROW_INVERSE_TABLES, &child);
   if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (mode & NFLHIP_ROW_BITREV_IO) {  // core::inv_ntt: permut, ntt, permut (core.hpp:549-554)
-    hipError_t e = DISPATCH_T(ctx, launch_bitrev_rows<uint16_t>(ctx->shape, (uint16_t *)d_rows, rows, st),
-                              launch_bitrev_rows<uint32_t>(ctx->shape, (uint32_t *)d_rows, rows, st),
-                              launch_bitrev_rows<uint64_t>(ctx->shape, (uint64_t *)d_rows, rows, st));
-    if (e != hipSuccess) return hipfail(ctx, e, "ntt_row: bit reversal");
-  }
-  rc = nflhip_ntt_fwd_dev(child, d_rows, rows, stream);
-  if (rc) return rc;
-  if (mode & NFLHIP_ROW_BITREV_IO) {
-    hipError_t e = DISPATCH_T(ctx, launch_bitrev_rows<uint16_t>(ctx->shape, (uint16_t *)d_rows, rows, st),
-                              launch_bitrev_rows<uint32_t>(ctx->shape, (uint32_t *)d_rows, rows, st),
-                              launch_bitrev_rows<uint64_t>(ctx->shape, (uint64_t *)d_rows, rows, st));
-    if (e != hipSuccess) return hipfail(ctx, e, "ntt_row: bit reversal");
-  }
-  return NFLHIP_OK;
+  auto bitrev = [&]() -> int {   // core::inv_ntt: permut, ntt, permut (core.hpp:549-554)
+    if (!(mode & NFLHIP_ROW_BITREV_IO)) return NFLHIP_OK;
+    hipError_t e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_bitrev_rows<T>(ctx->shape, (T *)d_rows, rows, (hipStream_t)stream);
+    });
+    return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "ntt_row: bit reversal");
+  };
+  rc = bitrev();
+  if (!rc) rc = nflhip_ntt_fwd_dev(child, d_rows, rows, stream);
+  if (!rc) rc = bitrev();
+  return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -2015,523 +1846,6 @@ int nflhip_stream_idle(nflhip_ctx *ctx, void *stream, int *idle) {
   else if (e != hipSuccess) HIPCHK(ctx, e);
   *idle = e == hipSuccess ? 1 : 0;
   return NFLHIP_OK;
-}
-
-// ---------------------------------------------------------------------------
-// host-pointer entry points: stage through context-owned device buffers
-// ---------------------------------------------------------------------------
-}  // extern "C"
-
-// Large batches through the host-pointer entry points (what an unchanged caller holding arrays of inline-storage
-// nfl::poly gets: poly.hpp:87-88, tests/tools.h:6-17).  hipMemcpy from pageable memory tops out at ~12 GB/s on this
-// platform (the runtime's single staging thread), 5x below PCIe.  Here the batch is cut into chunks that flow through
-// three slots of PINNED staging buffers: several host threads copy chunk k + 1 into its slot while chunk k crosses PCIe
-// (H2D stream), chunk k - 1 is computed (compute stream) and chunk k - 2 returns (D2H stream) and is copied out.
-// Results are what one call over the whole batch gives (every operation here is per-polynomial).
-namespace {
-class CopyPool {  // a few host threads that memcpy slices; process-wide, started on first use
- public:
-  static CopyPool &get() {
-    static CopyPool *p = new CopyPool();  // (leaked on purpose: worker threads must not be joined from a static destructor)
-    return *p;
-  }
-  void copy(void *dst, const void *src, size_t bytes) {
-    const size_t slice = 512 << 10;
-    const size_t parts = (bytes + slice - 1) / slice;
-    if (parts <= 1 || workers_.empty()) {
-      std::memcpy(dst, src, bytes);
-      return;
-    }
-    // ONE job at a time: the pool is process-wide and keeps a single job's state, while callers on different contexts
-    // (one host thread per GPU, two ring types) hold only their own context's lock
-    std::lock_guard<std::mutex> call(call_mu_);
-    std::unique_lock<std::mutex> lk(mu_);
-    dst_ = (char *)dst;
-    src_ = (const char *)src;
-    bytes_ = bytes;
-    slice_ = slice;
-    next_ = 0;
-    parts_ = parts;
-    done_ = 0;
-    ++generation_;
-    gen_hint_.store(generation_, std::memory_order_release);
-    cv_.notify_all();
-    lk.unlock();
-    work();  // the calling thread copies too
-    lk.lock();
-    cv_done_.wait(lk, [&] { return done_ == parts_; });
-  }
-
- private:
-  CopyPool() {
-    unsigned n = std::thread::hardware_concurrency();
-    n = n >= 64 ? 15 : (n > 16 ? 7 : (n > 2 ? n / 2 - 1 : 0));  // + the caller: 16 copying threads on a server host
-    for (unsigned i = 0; i < n; ++i) workers_.emplace_back([this] { loop(); }), workers_.back().detach();
-  }
-  void work() {
-    for (;;) {
-      size_t k;
-      {
-        std::lock_guard<std::mutex> lk(mu_);
-        if (next_ >= parts_) return;
-        k = next_++;
-      }
-      const size_t off = k * slice_, len = bytes_ - off < slice_ ? bytes_ - off : slice_;
-      std::memcpy(dst_ + off, src_ + off, len);
-      std::lock_guard<std::mutex> lk(mu_);
-      if (++done_ == parts_) cv_done_.notify_all();
-    }
-  }
-  void loop() {
-    unsigned long long seen = 0;
-    for (;;) {
-      // a chunk is ~0.3 ms of copying for one thread: a sleeping worker wakes too late to help, so workers spin for a
-      // while after every job (the next chunk follows within microseconds while a call is in flight) and only then sleep
-      bool got = false;
-      for (int spin = 0; spin < 20000 && !got; ++spin) {
-        if (gen_hint_.load(std::memory_order_acquire) != seen) got = true;
-        else __builtin_ia32_pause();
-      }
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        if (!got) cv_.wait(lk, [&] { return generation_ != seen; });
-        seen = generation_;
-      }
-      work();
-    }
-  }
-  std::atomic<unsigned long long> gen_hint_{0};
-  std::mutex mu_, call_mu_;
-  std::condition_variable cv_, cv_done_;
-  std::vector<std::thread> workers_;
-  char *dst_ = nullptr;
-  const char *src_ = nullptr;
-  size_t bytes_ = 0, slice_ = 0, next_ = 0, parts_ = 0, done_ = 0;
-  unsigned long long generation_ = 0;
-};
-}  // namespace
-
-struct HostPipe {
-  static constexpr int kSlots = 3, kBufs = 4;            // per slot: up to 3 inputs + 1 output
-  static constexpr size_t kChunkBytes = size_t(8) << 20;  // per operand and slot
-  void *pinned[kSlots][kBufs] = {};
-  void *dev[kSlots][kBufs] = {};
-  hipStream_t s_h2d = nullptr, s_d2h = nullptr;
-  hipEvent_t ev_h2d[kSlots] = {}, ev_k[kSlots] = {}, ev_d2h[kSlots] = {};
-  double t_in = 0, t_out = 0, t_wait = 0, t_total = 0;   // seconds spent copying in / out, waiting for the device, in calls
-  ~HostPipe() {
-    for (int s = 0; s < kSlots; ++s) {
-      for (int b = 0; b < kBufs; ++b) {
-        if (pinned[s][b]) (void)hipHostFree(pinned[s][b]);
-        if (dev[s][b]) (void)hipFree(dev[s][b]);
-      }
-      if (ev_h2d[s]) (void)hipEventDestroy(ev_h2d[s]);
-      if (ev_k[s]) (void)hipEventDestroy(ev_k[s]);
-      if (ev_d2h[s]) (void)hipEventDestroy(ev_d2h[s]);
-    }
-    if (s_h2d) (void)hipStreamDestroy(s_h2d);
-    if (s_d2h) (void)hipStreamDestroy(s_d2h);
-  }
-};
-
-static void pipe_stats(const nflhip_ctx *ctx, double out[4]) {
-  const HostPipe *p = ctx ? ctx->pipe : nullptr;
-  out[0] = p ? p->t_in : 0;
-  out[1] = p ? p->t_out : 0;
-  out[2] = p ? p->t_wait : 0;
-  out[3] = p ? p->t_total : 0;
-}
-static void pipe_destroy(nflhip_ctx *ctx) {
-  delete ctx->pipe;
-  ctx->pipe = nullptr;
-}
-
-static int pipe_get(nflhip_ctx *ctx, HostPipe **out) {
-  if (!ctx->pipe) {
-    std::unique_ptr<HostPipe> p(new (std::nothrow) HostPipe());
-    if (!p) return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
-    HIPCHK(ctx, hipStreamCreateWithFlags(&p->s_h2d, hipStreamNonBlocking));
-    HIPCHK(ctx, hipStreamCreateWithFlags(&p->s_d2h, hipStreamNonBlocking));
-    for (int s = 0; s < HostPipe::kSlots; ++s) {
-      for (int b = 0; b < HostPipe::kBufs; ++b) {
-        HIPCHK(ctx, hipHostMalloc(&p->pinned[s][b], HostPipe::kChunkBytes, hipHostMallocDefault));
-        HIPCHK(ctx, hipMalloc(&p->dev[s][b], HostPipe::kChunkBytes));
-      }
-      HIPCHK(ctx, hipEventCreateWithFlags(&p->ev_h2d[s], hipEventDisableTiming));
-      HIPCHK(ctx, hipEventCreateWithFlags(&p->ev_k[s], hipEventDisableTiming));
-      HIPCHK(ctx, hipEventCreateWithFlags(&p->ev_d2h[s], hipEventDisableTiming));
-    }
-    ctx->pipe = p.release();
-  }
-  *out = ctx->pipe;
-  return NFLHIP_OK;
-}
-
-// in[j] (nin <= 3 host arrays of `batch` polynomials) -> out (host array); launch(d_in[], d_out, count, stream) enqueues
-// the per-polynomial operation on a chunk.  Caller holds ctx->mu.  Returns NFLHIP_ERR_UNSUPPORTED when the batch is too
-// small to pipeline (the simple staged path then serves it).
-template <typename F>
-static int run_pipelined(nflhip_ctx *ctx, size_t batch, const void *const *in, int nin, void *out, F launch) {
-  const size_t pb = poly_bytes(ctx, 1);
-  const size_t per = HostPipe::kChunkBytes / pb;  // polynomials per chunk
-  if (per == 0 || batch < 2 * per) return NFLHIP_ERR_UNSUPPORTED;
-  HostPipe *p = nullptr;
-  int rc = pipe_get(ctx, &p);
-  if (rc) return rc;
-  CopyPool &pool = CopyPool::get();
-  const size_t nchunks = (batch + per - 1) / per;
-  auto count_of = [&](size_t k) { return k + 1 < nchunks ? per : batch - k * per; };
-  typedef std::chrono::steady_clock clk;
-  auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-  const clk::time_point t_begin = clk::now();
-  // chunk k is back in its pinned slot: hand it to the caller.  Done by a SECOND host thread, so that results leave while
-  // the calling thread (and the pool) copies the next chunks in: the two directions overlap on the host as they do on PCIe
-  std::atomic<size_t> issued{0}, drained{0};
-  std::atomic<int> drain_rc{NFLHIP_OK};
-  std::atomic<bool> stop{false};
-  std::string drain_err;
-  auto drain_one = [&](size_t k) -> int {
-    const int s = int(k % HostPipe::kSlots);
-    const clk::time_point t0 = clk::now();
-    hipError_t he = hipEventSynchronize(p->ev_d2h[s]);
-    if (he != hipSuccess) {
-      drain_err = std::string("hipEventSynchronize: ") + hipGetErrorString(he);
-      return NFLHIP_ERR_HIP;
-    }
-    const clk::time_point t1 = clk::now();
-    std::memcpy((char *)out + k * per * pb, p->pinned[s][3], count_of(k) * pb);
-    p->t_wait += secs(t0, t1);
-    p->t_out += secs(t1, clk::now());
-    return NFLHIP_OK;
-  };
-  std::thread drainer;
-  try {
-    drainer = std::thread([&] {
-      (void)hipSetDevice(ctx->device);
-      for (size_t k = 0; k < nchunks; ++k) {
-        while (issued.load(std::memory_order_acquire) <= k) {
-          if (stop.load(std::memory_order_acquire)) return;
-          __builtin_ia32_pause();
-        }
-        const int r = drain_one(k);
-        if (r) { drain_rc.store(r); return; }
-        drained.store(k + 1, std::memory_order_release);
-      }
-    });
-  } catch (...) {  // (no exception crosses the C boundary)
-    return fail(ctx, NFLHIP_ERR_NOMEM, "cannot start the host thread that copies results out");
-  }
-  // Whatever way this function is left: the drainer is joined, and -- on an error path, where copies and kernels may still
-  // be in flight on the three streams against the pinned and device slots -- the streams are drained before the slots
-  // can be reused by the next call on this context
-  bool completed = false;
-  struct joiner {
-    std::thread &t; std::atomic<bool> &stop; bool &completed; HostPipe *p; nflhip_ctx *ctx;
-    ~joiner() {
-      stop.store(true);
-      if (t.joinable()) t.join();
-      if (!completed) {
-        (void)hipStreamSynchronize(p->s_h2d);
-        (void)hipStreamSynchronize(ctx->hstream);
-        (void)hipStreamSynchronize(p->s_d2h);
-        (void)hipGetLastError();
-      }
-    }
-  } join_guard{drainer, stop, completed, p, ctx};
-  for (size_t k = 0; k < nchunks; ++k) {
-    const int s = int(k % HostPipe::kSlots);
-    while (k >= size_t(HostPipe::kSlots) && drained.load(std::memory_order_acquire) + HostPipe::kSlots <= k) {  // the slot's previous tenant
-      if (drain_rc.load()) return fail(ctx, drain_rc.load(), drain_err);
-      __builtin_ia32_pause();
-    }
-    const size_t cnt = count_of(k), bytes = cnt * pb;
-    const void *d_in[3] = {nullptr, nullptr, nullptr};
-    for (int j = 0; j < nin; ++j) {
-      // (aliased operands -- polymul(a, a) -- are staged once)
-      int same = -1;
-      for (int i = 0; i < j; ++i)
-        if (in[i] == in[j]) same = i;
-      if (same >= 0) { d_in[j] = d_in[same]; continue; }
-      const clk::time_point t0 = clk::now();
-      pool.copy(p->pinned[s][j], (const char *)in[j] + k * per * pb, bytes);
-      p->t_in += secs(t0, clk::now());
-      HIPCHK(ctx, hipMemcpyAsync(p->dev[s][j], p->pinned[s][j], bytes, hipMemcpyHostToDevice, p->s_h2d));
-      d_in[j] = p->dev[s][j];
-    }
-    HIPCHK(ctx, hipEventRecord(p->ev_h2d[s], p->s_h2d));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->hstream, p->ev_h2d[s], 0));
-    rc = launch(d_in, p->dev[s][3], cnt, (void *)ctx->hstream);
-    if (rc) return rc;
-    HIPCHK(ctx, hipEventRecord(p->ev_k[s], ctx->hstream));
-    HIPCHK(ctx, hipStreamWaitEvent(p->s_d2h, p->ev_k[s], 0));
-    HIPCHK(ctx, hipMemcpyAsync(p->pinned[s][3], p->dev[s][3], bytes, hipMemcpyDeviceToHost, p->s_d2h));
-    HIPCHK(ctx, hipEventRecord(p->ev_d2h[s], p->s_d2h));
-    // (the next H2D into this slot's device inputs cannot overtake this chunk's kernel: the host reuses a slot only after
-    // its result has been drained.  No wait on the in-order H2D stream here -- it would hold chunk k + 1's copy, which
-    // goes to ANOTHER slot, behind kernel k, and copies would never overlap compute)
-    issued.store(k + 1, std::memory_order_release);
-  }
-  while (drained.load(std::memory_order_acquire) < nchunks) {
-    if (drain_rc.load()) return fail(ctx, drain_rc.load(), drain_err);
-    __builtin_ia32_pause();
-  }
-  p->t_total += secs(t_begin, clk::now());
-  completed = true;
-  return NFLHIP_OK;
-}
-
-extern "C" {
-
-struct Staged {
-  nflhip_ctx *ctx;
-  std::unique_lock<std::mutex> lk;
-  explicit Staged(nflhip_ctx *c) : ctx(c), lk(c->mu) {}
-  int in(int slot, const void *h, size_t bytes) {
-    int rc = ensure_stage(ctx, slot, bytes);
-    if (rc) return rc;
-    if (h && ctx->stage_host[slot]) std::memcpy(ctx->stage[slot], h, bytes);   // (the stream is idle: every host-pointer call ends synchronised)
-    else if (h) HIPCHK(ctx, hipMemcpyAsync(ctx->stage[slot], h, bytes, hipMemcpyHostToDevice, ctx->hstream));
-    return NFLHIP_OK;
-  }
-  int out(void *h, int slot, size_t bytes) {
-    if (!ctx->stage_host[slot]) HIPCHK(ctx, hipMemcpyAsync(h, ctx->stage[slot], bytes, hipMemcpyDeviceToHost, ctx->hstream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
-    if (ctx->stage_host[slot]) std::memcpy(h, ctx->stage[slot], bytes);
-    return NFLHIP_OK;
-  }
-};
-
-int nflhip_ntt_fwd(nflhip_ctx *ctx, void *h, size_t batch) {
-  CHECK_CTX(ctx);
-  if (batch == 0) return NFLHIP_OK;
-  if (!h) return fail(ctx, NFLHIP_ERR_INVALID, "NULL data pointer");
-  Staged s(ctx);
-  const size_t bytes = poly_bytes(ctx, batch);
-  const void *ins[1] = {h};
-  int rc = run_pipelined(ctx, batch, ins, 1, h, [&](const void *const *d, void *o, size_t cnt, void *st) {
-    HIPCHK(ctx, hipMemcpyAsync(o, d[0], poly_bytes(ctx, cnt), hipMemcpyDeviceToDevice, (hipStream_t)st));
-    return nflhip_ntt_fwd_dev(ctx, o, cnt, st);
-  });
-  if (rc != NFLHIP_ERR_UNSUPPORTED) return rc;
-  rc = s.in(0, h, bytes);
-  if (rc) return rc;
-  rc = nflhip_ntt_fwd_dev(ctx, ctx->stage[0], batch, ctx->hstream);
-  if (rc) return rc;
-  return s.out(h, 0, bytes);
-}
-int nflhip_ntt_inv(nflhip_ctx *ctx, void *h, size_t batch) {
-  CHECK_CTX(ctx);
-  if (batch == 0) return NFLHIP_OK;
-  if (!h) return fail(ctx, NFLHIP_ERR_INVALID, "NULL data pointer");
-  Staged s(ctx);
-  const size_t bytes = poly_bytes(ctx, batch);
-  const void *ins[1] = {h};
-  int rc = run_pipelined(ctx, batch, ins, 1, h, [&](const void *const *d, void *o, size_t cnt, void *st) {
-    HIPCHK(ctx, hipMemcpyAsync(o, d[0], poly_bytes(ctx, cnt), hipMemcpyDeviceToDevice, (hipStream_t)st));
-    return nflhip_ntt_inv_dev(ctx, o, cnt, st);
-  });
-  if (rc != NFLHIP_ERR_UNSUPPORTED) return rc;
-  rc = s.in(0, h, bytes);
-  if (rc) return rc;
-  rc = nflhip_ntt_inv_dev(ctx, ctx->stage[0], batch, ctx->hstream);
-  if (rc) return rc;
-  return s.out(h, 0, bytes);
-}
-int nflhip_automorphism(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, uint64_t k, int form) {
-  CHECK_CTX(ctx);
-  if (form != NFLHIP_FORM_COEFF && form != NFLHIP_FORM_NTT) return fail(ctx, NFLHIP_ERR_INVALID, "unknown polynomial form");
-  if ((k & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism exponent k must be odd");
-  if (batch == 0) return NFLHIP_OK;
-  if (!h_out || !h_in) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
-  const size_t bytes = poly_bytes(ctx, batch);
-  if (h_out != h_in && bytes_overlap(h_out, h_in, bytes)) return fail(ctx, NFLHIP_ERR_INVALID, "the output overlaps the input");
-  Staged s(ctx);
-  const void *ins[1] = {h_in};
-  int rc = run_pipelined(ctx, batch, ins, 1, h_out, [&](const void *const *d, void *o, size_t cnt, void *st) {
-    return nflhip_automorphism_dev(ctx, o, d[0], cnt, k, form, st);
-  });
-  if (rc != NFLHIP_ERR_UNSUPPORTED) return rc;
-  rc = s.in(0, h_in, bytes);
-  if (rc) return rc;
-  if ((rc = s.in(1, nullptr, bytes))) return rc;
-  rc = nflhip_automorphism_dev(ctx, ctx->stage[1], ctx->stage[0], batch, k, form, ctx->hstream);
-  if (rc) return rc;
-  return s.out(h_out, 1, bytes);
-}
-int nflhip_ntt_row(nflhip_ctx *ctx, void *h_rows, size_t cm, int mode, size_t rows) {
-  CHECK_CTX(ctx);
-  if (rows == 0) return NFLHIP_OK;
-  if (!h_rows) return fail(ctx, NFLHIP_ERR_INVALID, "NULL data pointer");
-  Staged s(ctx);
-  const size_t bytes = rows * ctx->shape.n * ctx->word;
-  int rc = s.in(0, h_rows, bytes);
-  if (rc) return rc;
-  rc = nflhip_ntt_row_dev(ctx, ctx->stage[0], cm, mode, rows, ctx->hstream);
-  if (rc) return rc;
-  return s.out(h_rows, 0, bytes);
-}
-int nflhip_pointwise(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch) {
-  CHECK_CTX(ctx);
-  if (op < 0 || op > 4) return fail(ctx, NFLHIP_ERR_INVALID, "unknown element-wise op");
-  if (batch == 0) return NFLHIP_OK;
-  if (!o || !a || (op != NFLHIP_OP_COMPUTE_SHOUP && !b) || (op == NFLHIP_OP_MUL_SHOUP && !bp))
-    return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
-  Staged s(ctx);
-  const size_t bytes = poly_bytes(ctx, batch);
-  const void *ins[3] = {a, op != NFLHIP_OP_COMPUTE_SHOUP ? b : a, op == NFLHIP_OP_MUL_SHOUP ? bp : a};
-  int rc = run_pipelined(ctx, batch, ins, 3, o, [&](const void *const *d, void *out, size_t cnt, void *st) {
-    return nflhip_pointwise_dev(ctx, op, out, d[0], d[1], d[2], cnt, st);
-  });
-  if (rc != NFLHIP_ERR_UNSUPPORTED) return rc;
-  rc = s.in(0, a, bytes);
-  if (rc) return rc;
-  if (op != NFLHIP_OP_COMPUTE_SHOUP && (rc = s.in(1, b, bytes))) return rc;
-  if (op == NFLHIP_OP_MUL_SHOUP && (rc = s.in(2, bp, bytes))) return rc;
-  rc = nflhip_pointwise_dev(ctx, op, ctx->stage[0], ctx->stage[0], ctx->stage[1], ctx->stage[2], batch, ctx->hstream);
-  if (rc) return rc;
-  return s.out(o, 0, bytes);
-}
-int nflhip_eval(nflhip_ctx *ctx, void *h_out, const void *const *h_operands, size_t noperands, const unsigned char *program,
-                size_t proglen, size_t batch) {
-  CHECK_CTX(ctx);
-  if (!program || !h_operands) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
-  if (noperands == 0 || noperands > 4 || proglen == 0 || proglen > NFLHIP_EXPR_MAX_LEN)
-    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "host-pointer eval takes at most 4 distinct operands");
-  if (batch == 0) return NFLHIP_OK;
-  if (!h_out) return fail(ctx, NFLHIP_ERR_INVALID, "NULL output");
-  Staged s(ctx);
-  const size_t bytes = poly_bytes(ctx, batch);
-  for (size_t i = 0; i < noperands; ++i)
-    if (!h_operands[i]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
-  if (noperands <= 3) {   // (the pipeline's slots hold three inputs and the result)
-    int prc = run_pipelined(ctx, batch, h_operands, (int)noperands, h_out, [&](const void *const *d, void *out, size_t cnt, void *st) {
-      return eval_dev(ctx, out, d, noperands, program, proglen, cnt, st);
-    });
-    if (prc != NFLHIP_ERR_UNSUPPORTED) return prc;
-  }
-  const void *dops[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (size_t i = 0; i < noperands; ++i) {
-    if (!h_operands[i]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
-    int rc = s.in((int)i, h_operands[i], bytes);
-    if (rc) return rc;
-    dops[i] = ctx->stage[i];
-  }
-  // four operands (c = c + shoup(a * b, b'): the reference's FMA with a precomputed companion) fill the four staging buffers: the result
-  // is written over the first one -- the evaluation is element-wise, `out` may alias an input
-  const int oslot = noperands == 4 ? 0 : 3;
-  int rc = s.in(oslot, nullptr, bytes);
-  if (rc) return rc;
-  rc = eval_dev(ctx, ctx->stage[oslot], dops, noperands, program, proglen, batch, ctx->hstream);
-  if (rc) return rc;
-  return s.out(h_out, oslot, bytes);
-}
-
-int nflhip_polymul(nflhip_ctx *ctx, void *c, const void *a, const void *b, size_t batch) {
-  CHECK_CTX(ctx);
-  if (batch == 0) return NFLHIP_OK;
-  if (!c || !a || !b) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
-  Staged s(ctx);
-  const size_t bytes = poly_bytes(ctx, batch);
-  const void *ins[2] = {a, b};
-  int rc = run_pipelined(ctx, batch, ins, 2, c, [&](const void *const *d, void *out, size_t cnt, void *st) {
-    return nflhip_polymul_dev(ctx, out, d[0], d[1], cnt, st);
-  });
-  if (rc != NFLHIP_ERR_UNSUPPORTED) return rc;
-  rc = s.in(0, a, bytes);
-  if (rc) return rc;
-  if ((rc = s.in(1, b, bytes))) return rc;
-  rc = nflhip_polymul_dev(ctx, ctx->stage[0], ctx->stage[0], ctx->stage[1], batch, ctx->hstream);
-  if (rc) return rc;
-  return s.out(c, 0, bytes);
-}
-static int any_cmp_host(nflhip_ctx *ctx, const void *a, const void *b, size_t batch, int want_eq, int *result) {
-  CHECK_CTX(ctx);
-  if (!result) return fail(ctx, NFLHIP_ERR_INVALID, "NULL result");
-  if (batch == 0) { *result = 0; return NFLHIP_OK; }
-  if (!a || !b) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
-  Staged s(ctx);
-  const size_t bytes = poly_bytes(ctx, batch);
-  int rc = s.in(0, a, bytes);
-  if (rc) return rc;
-  if ((rc = s.in(1, b, bytes))) return rc;
-  return any_cmp_dev(ctx, ctx->stage[0], ctx->stage[1], batch, want_eq, result, ctx->hstream);
-}
-int nflhip_any_eq(nflhip_ctx *ctx, const void *a, const void *b, size_t batch, int *result) {
-  return any_cmp_host(ctx, a, b, batch, 1, result);
-}
-int nflhip_any_neq(nflhip_ctx *ctx, const void *a, const void *b, size_t batch, int *result) {
-  return any_cmp_host(ctx, a, b, batch, 0, result);
-}
-int nflhip_crt_lift(nflhip_ctx *ctx, uint64_t *limbs, const void *d, size_t batch) {
-  CHECK_CTX(ctx);
-  if (batch == 0) return NFLHIP_OK;
-  if (!limbs || !d) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
-  Staged s(ctx);
-  const size_t bytes = poly_bytes(ctx, batch);
-  const size_t lbytes = batch * ctx->shape.n * ctx->shape.crt_L * sizeof(uint64_t);
-  int rc = s.in(0, d, bytes);
-  if (rc) return rc;
-  if ((rc = s.in(1, nullptr, lbytes))) return rc;
-  rc = nflhip_crt_lift_dev(ctx, (uint64_t *)ctx->stage[1], ctx->stage[0], batch, ctx->hstream);
-  if (rc) return rc;
-  return s.out(limbs, 1, lbytes);
-}
-int nflhip_crt_project(nflhip_ctx *ctx, void *d, const uint64_t *limbs, size_t L_in, size_t batch) {
-  CHECK_CTX(ctx);
-  if (batch == 0) return NFLHIP_OK;
-  if (!limbs || !d) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
-  if (L_in == 0) return fail(ctx, NFLHIP_ERR_INVALID, "L_in must be positive");
-  Staged s(ctx);
-  const size_t bytes = poly_bytes(ctx, batch);
-  const size_t lbytes = batch * ctx->shape.n * L_in * sizeof(uint64_t);
-  int rc = s.in(1, limbs, lbytes);
-  if (rc) return rc;
-  if ((rc = s.in(0, nullptr, bytes))) return rc;
-  rc = nflhip_crt_project_dev(ctx, ctx->stage[0], (const uint64_t *)ctx->stage[1], L_in, batch, ctx->hstream);
-  if (rc) return rc;
-  return s.out(d, 0, bytes);
-}
-
-int nflhip_sample(nflhip_ctx *ctx, void *d, size_t batch, int dist, uint64_t p0, uint64_t p1, const unsigned char *key,
-                  uint64_t stream_id) {
-  CHECK_CTX(ctx);
-  if (batch == 0) return NFLHIP_OK;
-  if (!d) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
-  Staged s(ctx);
-  const size_t bytes = poly_bytes(ctx, batch);
-  int rc = s.in(0, nullptr, bytes);
-  if (rc) return rc;
-  rc = nflhip_sample_dev(ctx, ctx->stage[0], 0, batch, dist, p0, p1, key, stream_id, ctx->hstream);
-  if (rc) return rc;
-  return s.out(d, 0, bytes);
-}
-
-int nflhip_sample_gauss(nflhip_ctx *ctx, void *d, size_t batch, const nflhip_gauss *g, uint64_t amplifier,
-                        const unsigned char *key, uint64_t stream_id) {
-  CHECK_CTX(ctx);
-  if (batch == 0) return NFLHIP_OK;
-  if (!d) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
-  Staged s(ctx);
-  const size_t bytes = poly_bytes(ctx, batch);
-  int rc = s.in(0, nullptr, bytes);
-  if (rc) return rc;
-  rc = nflhip_sample_gauss_dev(ctx, ctx->stage[0], 0, batch, g, amplifier, key, stream_id, ctx->hstream);
-  if (rc) return rc;
-  return s.out(d, 0, bytes);
-}
-
-int nflhip_gauss_noise(nflhip_ctx *ctx, int64_t *h_out, size_t count, const nflhip_gauss *g, const unsigned char *key,
-                       uint64_t stream_id) {
-  CHECK_CTX(ctx);
-  if (count == 0) return NFLHIP_OK;
-  if (!h_out) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
-  Staged s(ctx);
-  const size_t bytes = count * sizeof(int64_t);
-  int rc = s.in(0, nullptr, bytes);
-  if (rc) return rc;
-  rc = nflhip_gauss_noise_dev(ctx, (int64_t *)ctx->stage[0], 0, count, g, key, stream_id, ctx->hstream);
-  if (rc) return rc;
-  return s.out(h_out, 0, bytes);
 }
 
 // ---------------------------------------------------------------------------

@@ -1,0 +1,523 @@
+// api_host.hip -- the host-pointer entry points of include/nflhip.h.  Each one checks its arguments and then runs the matching
+// device-pointer entry (api.hip) on staging buffers the context owns: small calls through the context's four staging slots,
+// large batches through a three-slot pipeline of pinned chunks.
+#include "../../include/nflhip.h"
+#include "../../include/nflhip_debug.h"
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "ctx.h"
+
+// Large batches through the host-pointer entry points (what an unchanged caller holding arrays of inline-storage
+// nfl::poly gets: poly.hpp:87-88, tests/tools.h:6-17).  hipMemcpy from pageable memory tops out at ~12 GB/s on this
+// platform (the runtime's single staging thread), 5x below PCIe.  Here the batch is cut into chunks that flow through
+// three slots of PINNED staging buffers: several host threads copy chunk k + 1 into its slot while chunk k crosses PCIe
+// (H2D stream), chunk k - 1 is computed (compute stream) and chunk k - 2 returns (D2H stream) and is copied out.
+// Results are what one call over the whole batch gives (every operation here is per-polynomial).
+namespace {
+class CopyPool {  // a few host threads that memcpy slices; process-wide, started on first use
+ public:
+  static CopyPool &get() {
+    static CopyPool *p = new CopyPool();  // (leaked on purpose: worker threads must not be joined from a static destructor)
+    return *p;
+  }
+  void copy(void *dst, const void *src, size_t bytes) {
+    const size_t slice = 512 << 10;
+    const size_t parts = (bytes + slice - 1) / slice;
+    if (parts <= 1 || workers_.empty()) {
+      std::memcpy(dst, src, bytes);
+      return;
+    }
+    // ONE job at a time: the pool is process-wide and keeps a single job's state, while callers on different contexts
+    // (one host thread per GPU, two ring types) hold only their own context's lock
+    std::lock_guard<std::mutex> call(call_mu_);
+    std::unique_lock<std::mutex> lk(mu_);
+    dst_ = (char *)dst;
+    src_ = (const char *)src;
+    bytes_ = bytes;
+    slice_ = slice;
+    next_ = 0;
+    parts_ = parts;
+    done_ = 0;
+    ++generation_;
+    gen_hint_.store(generation_, std::memory_order_release);
+    cv_.notify_all();
+    lk.unlock();
+    work();  // the calling thread copies too
+    lk.lock();
+    cv_done_.wait(lk, [&] { return done_ == parts_; });
+  }
+
+ private:
+  CopyPool() {
+    unsigned n = std::thread::hardware_concurrency();
+    n = n >= 64 ? 15 : (n > 16 ? 7 : (n > 2 ? n / 2 - 1 : 0));  // + the caller: 16 copying threads on a server host
+    for (unsigned i = 0; i < n; ++i) workers_.emplace_back([this] { loop(); }), workers_.back().detach();
+  }
+  void work() {
+    for (;;) {
+      size_t k;
+      {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (next_ >= parts_) return;
+        k = next_++;
+      }
+      const size_t off = k * slice_, len = bytes_ - off < slice_ ? bytes_ - off : slice_;
+      std::memcpy(dst_ + off, src_ + off, len);
+      std::lock_guard<std::mutex> lk(mu_);
+      if (++done_ == parts_) cv_done_.notify_all();
+    }
+  }
+  void loop() {
+    unsigned long long seen = 0;
+    for (;;) {
+      // a chunk is ~0.3 ms of copying for one thread: a sleeping worker wakes too late to help, so workers spin for a
+      // while after every job (the next chunk follows within microseconds while a call is in flight) and only then sleep
+      bool got = false;
+      for (int spin = 0; spin < 20000 && !got; ++spin) {
+        if (gen_hint_.load(std::memory_order_acquire) != seen) got = true;
+        else __builtin_ia32_pause();
+      }
+      {
+        std::unique_lock<std::mutex> lk(mu_);
+        if (!got) cv_.wait(lk, [&] { return generation_ != seen; });
+        seen = generation_;
+      }
+      work();
+    }
+  }
+  std::atomic<unsigned long long> gen_hint_{0};
+  std::mutex mu_, call_mu_;
+  std::condition_variable cv_, cv_done_;
+  std::vector<std::thread> workers_;
+  char *dst_ = nullptr;
+  const char *src_ = nullptr;
+  size_t bytes_ = 0, slice_ = 0, next_ = 0, parts_ = 0, done_ = 0;
+  unsigned long long generation_ = 0;
+};
+}  // namespace
+
+struct HostPipe {
+  static constexpr int kSlots = 3, kBufs = 4;            // per slot: up to 3 inputs + 1 output
+  static constexpr size_t kChunkBytes = size_t(8) << 20;  // per operand and slot
+  void *pinned[kSlots][kBufs] = {};
+  void *dev[kSlots][kBufs] = {};
+  hipStream_t s_h2d = nullptr, s_d2h = nullptr;
+  hipEvent_t ev_h2d[kSlots] = {}, ev_k[kSlots] = {}, ev_d2h[kSlots] = {};
+  double t_in = 0, t_out = 0, t_wait = 0, t_total = 0;   // seconds spent copying in / out, waiting for the device, in calls
+  ~HostPipe() {
+    for (int s = 0; s < kSlots; ++s) {
+      for (int b = 0; b < kBufs; ++b) {
+        if (pinned[s][b]) (void)hipHostFree(pinned[s][b]);
+        if (dev[s][b]) (void)hipFree(dev[s][b]);
+      }
+      if (ev_h2d[s]) (void)hipEventDestroy(ev_h2d[s]);
+      if (ev_k[s]) (void)hipEventDestroy(ev_k[s]);
+      if (ev_d2h[s]) (void)hipEventDestroy(ev_d2h[s]);
+    }
+    if (s_h2d) (void)hipStreamDestroy(s_h2d);
+    if (s_d2h) (void)hipStreamDestroy(s_d2h);
+  }
+};
+
+void pipe_destroy(nflhip_ctx *ctx) {
+  delete ctx->pipe;
+  ctx->pipe = nullptr;
+}
+
+static int pipe_get(nflhip_ctx *ctx, HostPipe **out) {
+  if (!ctx->pipe) {
+    std::unique_ptr<HostPipe> p(new (std::nothrow) HostPipe());
+    if (!p) return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+    HIPCHK(ctx, hipStreamCreateWithFlags(&p->s_h2d, hipStreamNonBlocking));
+    HIPCHK(ctx, hipStreamCreateWithFlags(&p->s_d2h, hipStreamNonBlocking));
+    for (int s = 0; s < HostPipe::kSlots; ++s) {
+      for (int b = 0; b < HostPipe::kBufs; ++b) {
+        HIPCHK(ctx, hipHostMalloc(&p->pinned[s][b], HostPipe::kChunkBytes, hipHostMallocDefault));
+        HIPCHK(ctx, hipMalloc(&p->dev[s][b], HostPipe::kChunkBytes));
+      }
+      HIPCHK(ctx, hipEventCreateWithFlags(&p->ev_h2d[s], hipEventDisableTiming));
+      HIPCHK(ctx, hipEventCreateWithFlags(&p->ev_k[s], hipEventDisableTiming));
+      HIPCHK(ctx, hipEventCreateWithFlags(&p->ev_d2h[s], hipEventDisableTiming));
+    }
+    ctx->pipe = p.release();
+  }
+  *out = ctx->pipe;
+  return NFLHIP_OK;
+}
+
+// in[j] (nin <= 3 host arrays of `batch` polynomials) -> out (host array); launch(d_in[], d_out, count, stream) enqueues
+// the per-polynomial operation on a chunk.  Caller holds ctx->mu.  Returns NFLHIP_ERR_UNSUPPORTED when the batch is too
+// small to pipeline (the simple staged path then serves it).
+template <typename F>
+static int run_pipelined(nflhip_ctx *ctx, size_t batch, const void *const *in, int nin, void *out, F launch) {
+  const size_t pb = poly_bytes(ctx, 1);
+  const size_t per = HostPipe::kChunkBytes / pb;  // polynomials per chunk
+  if (per == 0 || batch < 2 * per) return NFLHIP_ERR_UNSUPPORTED;
+  HostPipe *p = nullptr;
+  int rc = pipe_get(ctx, &p);
+  if (rc) return rc;
+  CopyPool &pool = CopyPool::get();
+  const size_t nchunks = (batch + per - 1) / per;
+  auto count_of = [&](size_t k) { return k + 1 < nchunks ? per : batch - k * per; };
+  typedef std::chrono::steady_clock clk;
+  auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+  const clk::time_point t_begin = clk::now();
+  // chunk k is back in its pinned slot: hand it to the caller.  Done by a SECOND host thread, so that results leave while
+  // the calling thread (and the pool) copies the next chunks in: the two directions overlap on the host as they do on PCIe
+  std::atomic<size_t> issued{0}, drained{0};
+  std::atomic<int> drain_rc{NFLHIP_OK};
+  std::atomic<bool> stop{false};
+  std::string drain_err;
+  auto drain_one = [&](size_t k) -> int {
+    const int s = int(k % HostPipe::kSlots);
+    const clk::time_point t0 = clk::now();
+    hipError_t he = hipEventSynchronize(p->ev_d2h[s]);
+    if (he != hipSuccess) {
+      drain_err = std::string("hipEventSynchronize: ") + hipGetErrorString(he);
+      return NFLHIP_ERR_HIP;
+    }
+    const clk::time_point t1 = clk::now();
+    std::memcpy((char *)out + k * per * pb, p->pinned[s][3], count_of(k) * pb);
+    p->t_wait += secs(t0, t1);
+    p->t_out += secs(t1, clk::now());
+    return NFLHIP_OK;
+  };
+  std::thread drainer;
+  try {
+    drainer = std::thread([&] {
+      (void)hipSetDevice(ctx->device);
+      for (size_t k = 0; k < nchunks; ++k) {
+        while (issued.load(std::memory_order_acquire) <= k) {
+          if (stop.load(std::memory_order_acquire)) return;
+          __builtin_ia32_pause();
+        }
+        const int r = drain_one(k);
+        if (r) { drain_rc.store(r); return; }
+        drained.store(k + 1, std::memory_order_release);
+      }
+    });
+  } catch (...) {  // (no exception crosses the C boundary)
+    return fail(ctx, NFLHIP_ERR_NOMEM, "cannot start the host thread that copies results out");
+  }
+  // Whatever way this function is left: the drainer is joined, and -- on an error path, where copies and kernels may still
+  // be in flight on the three streams against the pinned and device slots -- the streams are drained before the slots
+  // can be reused by the next call on this context
+  bool completed = false;
+  struct joiner {
+    std::thread &t; std::atomic<bool> &stop; bool &completed; HostPipe *p; nflhip_ctx *ctx;
+    ~joiner() {
+      stop.store(true);
+      if (t.joinable()) t.join();
+      if (!completed) {
+        (void)hipStreamSynchronize(p->s_h2d);
+        (void)hipStreamSynchronize(ctx->hstream);
+        (void)hipStreamSynchronize(p->s_d2h);
+        (void)hipGetLastError();
+      }
+    }
+  } join_guard{drainer, stop, completed, p, ctx};
+  for (size_t k = 0; k < nchunks; ++k) {
+    const int s = int(k % HostPipe::kSlots);
+    while (k >= size_t(HostPipe::kSlots) && drained.load(std::memory_order_acquire) + HostPipe::kSlots <= k) {  // the slot's previous tenant
+      if (drain_rc.load()) return fail(ctx, drain_rc.load(), drain_err);
+      __builtin_ia32_pause();
+    }
+    const size_t cnt = count_of(k), bytes = cnt * pb;
+    const void *d_in[3] = {nullptr, nullptr, nullptr};
+    for (int j = 0; j < nin; ++j) {
+      // (aliased operands -- polymul(a, a) -- are staged once)
+      int same = -1;
+      for (int i = 0; i < j; ++i)
+        if (in[i] == in[j]) same = i;
+      if (same >= 0) { d_in[j] = d_in[same]; continue; }
+      const clk::time_point t0 = clk::now();
+      pool.copy(p->pinned[s][j], (const char *)in[j] + k * per * pb, bytes);
+      p->t_in += secs(t0, clk::now());
+      HIPCHK(ctx, hipMemcpyAsync(p->dev[s][j], p->pinned[s][j], bytes, hipMemcpyHostToDevice, p->s_h2d));
+      d_in[j] = p->dev[s][j];
+    }
+    HIPCHK(ctx, hipEventRecord(p->ev_h2d[s], p->s_h2d));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->hstream, p->ev_h2d[s], 0));
+    rc = launch(d_in, p->dev[s][3], cnt, (void *)ctx->hstream);
+    if (rc) return rc;
+    HIPCHK(ctx, hipEventRecord(p->ev_k[s], ctx->hstream));
+    HIPCHK(ctx, hipStreamWaitEvent(p->s_d2h, p->ev_k[s], 0));
+    HIPCHK(ctx, hipMemcpyAsync(p->pinned[s][3], p->dev[s][3], bytes, hipMemcpyDeviceToHost, p->s_d2h));
+    HIPCHK(ctx, hipEventRecord(p->ev_d2h[s], p->s_d2h));
+    // (the next H2D into this slot's device inputs cannot overtake this chunk's kernel: the host reuses a slot only after
+    // its result has been drained.  No wait on the in-order H2D stream here -- it would hold chunk k + 1's copy, which
+    // goes to ANOTHER slot, behind kernel k, and copies would never overlap compute)
+    issued.store(k + 1, std::memory_order_release);
+  }
+  while (drained.load(std::memory_order_acquire) < nchunks) {
+    if (drain_rc.load()) return fail(ctx, drain_rc.load(), drain_err);
+    __builtin_ia32_pause();
+  }
+  p->t_total += secs(t_begin, clk::now());
+  completed = true;
+  return NFLHIP_OK;
+}
+
+// The simple staged path of one call, under the context's lock.  Every host-pointer call ends with ctx->hstream drained, so
+// in() may fill a pinned slot with a plain memcpy.  A call that leaves after its first in() without its result copied out
+// (an error on the way) drains the stream here: launches queued before the failing step may still use the slots, which the
+// next call refills from the host or frees when it grows them.
+namespace {
+struct Staged {
+  nflhip_ctx *ctx;
+  std::unique_lock<std::mutex> lk;
+  bool pending = false;  // work of this call may still be in flight on ctx->hstream
+  explicit Staged(nflhip_ctx *c) : ctx(c), lk(c->mu) {}
+  ~Staged() {
+    if (pending) {
+      (void)hipStreamSynchronize(ctx->hstream);
+      (void)hipGetLastError();
+    }
+  }
+  int in(int slot, const void *h, size_t bytes) {   // (h NULL: the slot is only made large enough)
+    pending = true;
+    int rc = ensure_stage(ctx, slot, bytes);
+    if (rc) return rc;
+    if (h && ctx->stage_host[slot]) std::memcpy(ctx->stage[slot], h, bytes);
+    else if (h) HIPCHK(ctx, hipMemcpyAsync(ctx->stage[slot], h, bytes, hipMemcpyHostToDevice, ctx->hstream));
+    return NFLHIP_OK;
+  }
+  int out(void *h, int slot, size_t bytes) {
+    if (!ctx->stage_host[slot]) HIPCHK(ctx, hipMemcpyAsync(h, ctx->stage[slot], bytes, hipMemcpyDeviceToHost, ctx->hstream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
+    pending = false;
+    if (ctx->stage_host[slot]) std::memcpy(h, ctx->stage[slot], bytes);
+    return NFLHIP_OK;
+  }
+};
+
+// An operand of a staged call: `bytes` of host memory at h, staged into slot `slot`.  h NULL: an operand the call does not
+// read -- nothing is staged, the device call gets the slot's buffer as it is (the pipeline: operand 0's chunk).
+struct HostIn { int slot; const void *h; size_t bytes; };
+// Its result: `bytes` copied from slot `slot` to h.  slot < 0: the device call hands its result back itself, having drained
+// the stream.
+struct HostOut { int slot; void *h; size_t bytes; };
+}  // namespace
+
+// Every host-pointer entry that computes on the device runs here once its arguments are checked.  With `pipelined` a batch
+// large enough takes the pinned pipeline; otherwise the inputs are staged in order, the result slot is made large enough,
+// and op(in[], out, batch, stream) runs once on the slots' buffers before the result is copied out.  op is the pipeline's
+// per-chunk launch as well (in[] the chunk's inputs, out its result buffer).
+template <typename Op>
+static int staged_call(nflhip_ctx *ctx, size_t batch, bool pipelined, const HostIn *ins, int nin, HostOut res, Op op) {
+  Staged s(ctx);
+  const void *d[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (pipelined) {
+    for (int j = 0; j < nin; ++j) d[j] = ins[j].h ? ins[j].h : ins[0].h;
+    const int rc = run_pipelined(ctx, batch, d, nin, res.h, op);
+    if (rc != NFLHIP_ERR_UNSUPPORTED) return rc;
+  }
+  for (int j = 0; j < nin; ++j) {
+    const int rc = ins[j].h ? s.in(ins[j].slot, ins[j].h, ins[j].bytes) : NFLHIP_OK;
+    if (rc) return rc;
+  }
+  const int rc = res.slot >= 0 ? s.in(res.slot, nullptr, res.bytes) : NFLHIP_OK;
+  if (rc) return rc;
+  for (int j = 0; j < nin; ++j) d[j] = ctx->stage[ins[j].slot];
+  const int orc = op(d, res.slot >= 0 ? ctx->stage[res.slot] : nullptr, batch, (void *)ctx->hstream);
+  if (orc) return orc;
+  if (res.slot >= 0) return s.out(res.h, res.slot, res.bytes);
+  s.pending = false;
+  return NFLHIP_OK;
+}
+
+extern "C" {
+
+void nflhip_debug_host_pipe_seconds(const nflhip_ctx *ctx, double out[4]) {
+  const HostPipe *p = ctx ? ctx->pipe : nullptr;
+  out[0] = p ? p->t_in : 0;
+  out[1] = p ? p->t_out : 0;
+  out[2] = p ? p->t_wait : 0;
+  out[3] = p ? p->t_total : 0;
+}
+
+// the transforms run in place: a pipeline chunk is first copied into its result buffer
+static int ntt_host(nflhip_ctx *ctx, void *h, size_t batch, int (*dev)(nflhip_ctx *, void *, size_t, void *)) {
+  CHECK_CTX(ctx);
+  if (batch == 0) return NFLHIP_OK;
+  if (!h) return fail(ctx, NFLHIP_ERR_INVALID, "NULL data pointer");
+  const size_t bytes = poly_bytes(ctx, batch);
+  const HostIn ins[] = {{0, h, bytes}};
+  return staged_call(ctx, batch, true, ins, 1, {0, h, bytes}, [&](const void *const *d, void *o, size_t cnt, void *st) {
+    if (o != d[0]) HIPCHK(ctx, hipMemcpyAsync(o, d[0], poly_bytes(ctx, cnt), hipMemcpyDeviceToDevice, (hipStream_t)st));
+    return dev(ctx, o, cnt, st);
+  });
+}
+int nflhip_ntt_fwd(nflhip_ctx *ctx, void *h, size_t batch) { return ntt_host(ctx, h, batch, nflhip_ntt_fwd_dev); }
+int nflhip_ntt_inv(nflhip_ctx *ctx, void *h, size_t batch) { return ntt_host(ctx, h, batch, nflhip_ntt_inv_dev); }
+
+int nflhip_automorphism(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, uint64_t k, int form) {
+  CHECK_CTX(ctx);
+  if (form != NFLHIP_FORM_COEFF && form != NFLHIP_FORM_NTT) return fail(ctx, NFLHIP_ERR_INVALID, "unknown polynomial form");
+  if ((k & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism exponent k must be odd");
+  if (batch == 0) return NFLHIP_OK;
+  if (!h_out || !h_in) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t bytes = poly_bytes(ctx, batch);
+  if (h_out != h_in && bytes_overlap(h_out, h_in, bytes)) return fail(ctx, NFLHIP_ERR_INVALID, "the output overlaps the input");
+  const HostIn ins[] = {{0, h_in, bytes}};
+  return staged_call(ctx, batch, true, ins, 1, {1, h_out, bytes}, [&](const void *const *d, void *o, size_t cnt, void *st) {
+    return nflhip_automorphism_dev(ctx, o, d[0], cnt, k, form, st);
+  });
+}
+
+int nflhip_ntt_row(nflhip_ctx *ctx, void *h_rows, size_t cm, int mode, size_t rows) {
+  CHECK_CTX(ctx);
+  if (rows == 0) return NFLHIP_OK;
+  if (!h_rows) return fail(ctx, NFLHIP_ERR_INVALID, "NULL data pointer");
+  const size_t bytes = rows * ctx->shape.n * ctx->word;
+  const HostIn ins[] = {{0, h_rows, bytes}};
+  return staged_call(ctx, rows, false, ins, 1, {0, h_rows, bytes}, [&](const void *const *, void *o, size_t cnt, void *st) {
+    return nflhip_ntt_row_dev(ctx, o, cm, mode, cnt, st);
+  });
+}
+
+int nflhip_pointwise(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch) {
+  CHECK_CTX(ctx);
+  if (op < 0 || op > 4) return fail(ctx, NFLHIP_ERR_INVALID, "unknown element-wise op");
+  if (batch == 0) return NFLHIP_OK;
+  if (!o || !a || (op != NFLHIP_OP_COMPUTE_SHOUP && !b) || (op == NFLHIP_OP_MUL_SHOUP && !bp))
+    return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t bytes = poly_bytes(ctx, batch);
+  const HostIn ins[] = {{0, a, bytes}, {1, op != NFLHIP_OP_COMPUTE_SHOUP ? b : nullptr, bytes}, {2, op == NFLHIP_OP_MUL_SHOUP ? bp : nullptr, bytes}};
+  return staged_call(ctx, batch, true, ins, 3, {0, o, bytes}, [&](const void *const *d, void *out, size_t cnt, void *st) {
+    return nflhip_pointwise_dev(ctx, op, out, d[0], d[1], d[2], cnt, st);
+  });
+}
+
+int nflhip_eval(nflhip_ctx *ctx, void *h_out, const void *const *h_operands, size_t noperands, const unsigned char *program,
+                size_t proglen, size_t batch) {
+  CHECK_CTX(ctx);
+  if (!program || !h_operands) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
+  if (noperands == 0 || noperands > 4 || proglen == 0 || proglen > NFLHIP_EXPR_MAX_LEN)
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "host-pointer eval takes at most 4 distinct operands");
+  if (batch == 0) return NFLHIP_OK;
+  if (!h_out) return fail(ctx, NFLHIP_ERR_INVALID, "NULL output");
+  const size_t bytes = poly_bytes(ctx, batch);
+  HostIn ins[4];
+  for (size_t i = 0; i < noperands; ++i) {
+    if (!h_operands[i]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+    ins[i] = {(int)i, h_operands[i], bytes};
+  }
+  // four operands (c = c + shoup(a * b, b'): the reference's FMA with a precomputed companion) fill the four staging buffers: the result
+  // is written over the first one -- the evaluation is element-wise, `out` may alias an input.  (The pipeline's slots hold three
+  // inputs and the result.)
+  return staged_call(ctx, batch, noperands <= 3, ins, (int)noperands, {noperands == 4 ? 0 : 3, h_out, bytes},
+                     [&](const void *const *d, void *out, size_t cnt, void *st) {
+                       return nflhip_eval_dev(ctx, out, d, noperands, program, proglen, cnt, st);
+                     });
+}
+
+int nflhip_polymul(nflhip_ctx *ctx, void *c, const void *a, const void *b, size_t batch) {
+  CHECK_CTX(ctx);
+  if (batch == 0) return NFLHIP_OK;
+  if (!c || !a || !b) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t bytes = poly_bytes(ctx, batch);
+  const HostIn ins[] = {{0, a, bytes}, {1, b, bytes}};
+  return staged_call(ctx, batch, true, ins, 2, {0, c, bytes}, [&](const void *const *d, void *out, size_t cnt, void *st) {
+    return nflhip_polymul_dev(ctx, out, d[0], d[1], cnt, st);
+  });
+}
+
+static int any_cmp_host(nflhip_ctx *ctx, const void *a, const void *b, size_t batch, int want_eq, int *result) {
+  CHECK_CTX(ctx);
+  if (!result) return fail(ctx, NFLHIP_ERR_INVALID, "NULL result");
+  if (batch == 0) { *result = 0; return NFLHIP_OK; }
+  if (!a || !b) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t bytes = poly_bytes(ctx, batch);
+  const HostIn ins[] = {{0, a, bytes}, {1, b, bytes}};
+  return staged_call(ctx, batch, false, ins, 2, {-1, nullptr, 0}, [&](const void *const *d, void *, size_t cnt, void *st) {
+    return (want_eq ? nflhip_any_eq_dev : nflhip_any_neq_dev)(ctx, d[0], d[1], cnt, result, st);
+  });
+}
+int nflhip_any_eq(nflhip_ctx *ctx, const void *a, const void *b, size_t batch, int *result) {
+  return any_cmp_host(ctx, a, b, batch, 1, result);
+}
+int nflhip_any_neq(nflhip_ctx *ctx, const void *a, const void *b, size_t batch, int *result) {
+  return any_cmp_host(ctx, a, b, batch, 0, result);
+}
+
+int nflhip_check_range(const nflhip_ctx *ctx, const void *h_data, size_t batch, int *bad) {
+  // host words against the host copy of the moduli: an assertion about the CALLER's data, nothing is computed
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (!bad || (batch && !h_data)) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
+  const size_t n = ctx->shape.n, nm = ctx->shape.nm;
+  int hit = 0;
+  for (size_t r = 0; r < batch * nm && !hit; ++r) {
+    const uint64_t p = ctx->h_P[r % nm];
+    if (ctx->word == 8) { const uint64_t *w = (const uint64_t *)h_data + r * n; for (size_t i = 0; i < n; ++i) hit |= w[i] >= p; }
+    else if (ctx->word == 4) { const uint32_t *w = (const uint32_t *)h_data + r * n; for (size_t i = 0; i < n; ++i) hit |= w[i] >= p; }
+    else { const uint16_t *w = (const uint16_t *)h_data + r * n; for (size_t i = 0; i < n; ++i) hit |= w[i] >= p; }
+  }
+  *bad = hit ? 1 : 0;
+  return NFLHIP_OK;
+}
+
+int nflhip_crt_lift(nflhip_ctx *ctx, uint64_t *limbs, const void *d, size_t batch) {
+  CHECK_CTX(ctx);
+  if (batch == 0) return NFLHIP_OK;
+  if (!limbs || !d) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
+  const size_t lbytes = batch * ctx->shape.n * ctx->shape.crt_L * sizeof(uint64_t);
+  const HostIn ins[] = {{0, d, poly_bytes(ctx, batch)}};
+  return staged_call(ctx, batch, false, ins, 1, {1, limbs, lbytes}, [&](const void *const *s, void *o, size_t cnt, void *st) {
+    return nflhip_crt_lift_dev(ctx, (uint64_t *)o, s[0], cnt, st);
+  });
+}
+int nflhip_crt_project(nflhip_ctx *ctx, void *d, const uint64_t *limbs, size_t L_in, size_t batch) {
+  CHECK_CTX(ctx);
+  if (batch == 0) return NFLHIP_OK;
+  if (!limbs || !d) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
+  if (L_in == 0) return fail(ctx, NFLHIP_ERR_INVALID, "L_in must be positive");
+  const HostIn ins[] = {{1, limbs, batch * ctx->shape.n * L_in * sizeof(uint64_t)}};
+  return staged_call(ctx, batch, false, ins, 1, {0, d, poly_bytes(ctx, batch)}, [&](const void *const *s, void *o, size_t cnt, void *st) {
+    return nflhip_crt_project_dev(ctx, o, (const uint64_t *)s[0], L_in, cnt, st);
+  });
+}
+
+int nflhip_sample(nflhip_ctx *ctx, void *d, size_t batch, int dist, uint64_t p0, uint64_t p1, const unsigned char *key,
+                  uint64_t stream_id) {
+  CHECK_CTX(ctx);
+  if (batch == 0) return NFLHIP_OK;
+  if (!d) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
+  return staged_call(ctx, batch, false, nullptr, 0, {0, d, poly_bytes(ctx, batch)}, [&](const void *const *, void *o, size_t cnt, void *st) {
+    return nflhip_sample_dev(ctx, o, 0, cnt, dist, p0, p1, key, stream_id, st);
+  });
+}
+
+int nflhip_sample_gauss(nflhip_ctx *ctx, void *d, size_t batch, const nflhip_gauss *g, uint64_t amplifier,
+                        const unsigned char *key, uint64_t stream_id) {
+  CHECK_CTX(ctx);
+  if (batch == 0) return NFLHIP_OK;
+  if (!d) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
+  return staged_call(ctx, batch, false, nullptr, 0, {0, d, poly_bytes(ctx, batch)}, [&](const void *const *, void *o, size_t cnt, void *st) {
+    return nflhip_sample_gauss_dev(ctx, o, 0, cnt, g, amplifier, key, stream_id, st);
+  });
+}
+
+int nflhip_gauss_noise(nflhip_ctx *ctx, int64_t *h_out, size_t count, const nflhip_gauss *g, const unsigned char *key,
+                       uint64_t stream_id) {
+  CHECK_CTX(ctx);
+  if (count == 0) return NFLHIP_OK;
+  if (!h_out) return fail(ctx, NFLHIP_ERR_INVALID, "NULL argument");
+  return staged_call(ctx, count, false, nullptr, 0, {0, h_out, count * sizeof(int64_t)}, [&](const void *const *, void *o, size_t cnt, void *st) {
+    return nflhip_gauss_noise_dev(ctx, (int64_t *)o, 0, cnt, g, key, stream_id, st);
+  });
+}
+
+}  // extern "C"

@@ -1,0 +1,118 @@
+// ctx.h -- the context of include/nflhip.h and the error / staging helpers shared by the C-ABI translation units:
+// api.hip (context, tables, device-pointer entry points) and api_host.hip (host-pointer entry points).  Not installed.
+#pragma once
+#include "../../include/nflhip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "kernels.h"
+
+namespace nflhip {
+int set_error(int code, const std::string &msg);  // api.hip: the calling thread's nflhip_last_error text
+}
+
+struct nflhip_ctx {
+  int device = 0;
+  nflhip::Shape shape{};
+  nflhip::DevTables tabs{};
+  size_t word = 8;  // bytes per limb
+  // host-pointer path: staging buffers + private stream, serialised by a mutex
+  std::mutex mu;
+  hipStream_t hstream = nullptr;
+  void *stage[4] = {nullptr, nullptr, nullptr, nullptr};
+  size_t stage_bytes[4] = {0, 0, 0, 0};
+  // a staging buffer of up to kStageHostMax bytes is PINNED HOST memory the kernels read and write directly (one polynomial per call, the
+  // nfl::poly surface: a 128 KiB operand crosses PCIe inside the kernel in less time than a copy engine needs to start); larger ones are device
+  // memory filled by copies
+  bool stage_host[4] = {false, false, false, false};
+  bool flag_host = false;          // tabs.flag is pinned host memory
+  // large host-pointer calls: a three-slot pipeline of pinned staging chunks (HostPipe, api_host.hip), created on first use
+  struct HostPipe *pipe = nullptr;
+  // scratch for the composed (non-fused) polymul path, per stream use is serialised by the caller
+  void *scratch = nullptr;
+  size_t scratch_bytes = 0;
+  std::mutex scratch_mu;
+  // large-row polymul pipeline: two helper streams so that the HBM-bound streaming passes of one
+  // chunk overlap the VALU-bound fused kernel of another; ev_prev orders successive calls on the scratch
+  hipStream_t aux[2] = {nullptr, nullptr};
+  hipEvent_t ev_start = nullptr, ev_done[2] = {nullptr, nullptr};
+  bool ev_prev_valid = false;
+  hipEvent_t ev_scratch = nullptr;  // end of the last single-stream pipeline that used the scratch
+  bool ev_scratch_valid = false;
+  // any_eq / any_neq: every call owns one result slot (device int) for its memset + kernel + readback, so host
+  // threads comparing on distinct streams never share a flag
+  static constexpr int kCmpSlots = 32;
+  std::mutex cmp_mu[kCmpSlots];
+  int cmp_token[kCmpSlots] = {};   // the token of the slot's latest comparison (under its mutex)
+  std::atomic<unsigned> cmp_next{0};
+  // host copies for introspection
+  std::vector<uint64_t> h_Q;                     // moduli_product limbs
+  std::vector<std::vector<uint64_t>> h_lifting;  // lifting_integers[cm]
+  std::vector<uint64_t> h_P;
+  std::vector<uint64_t> h_roots, h_invk, h_phi;  // params<T>::primitive_roots / invkMaxPolyDegree, phi = 2n-th root per modulus
+  int kmax_log2 = 0;
+  // core::ntt(x, wtab, winvtab, p) (core.hpp:455-532) on the device: one single-modulus child context per
+  // (modulus, table set) whose twiddle table is the CYCLIC one, created on first use -- see nflhip_ntt_row_dev
+  int cyclic = 0;  // 0: negacyclic tables (the normal context); 1 / 2: cyclic over omega / omega^-1 (child contexts)
+  std::mutex row_mu;
+  std::vector<nflhip_ctx *> row_ctx;  // [2 * cm + inverse_tables]
+};
+
+void pipe_destroy(nflhip_ctx *ctx);  // api_host.hip: frees the context's host-pointer pipeline
+
+inline int fail(const nflhip_ctx *ctx, int code, const std::string &msg) {
+  (void)ctx;
+  return nflhip::set_error(code, msg);
+}
+inline int hipfail(const nflhip_ctx *ctx, hipError_t e, const char *where) {
+  return fail(ctx, e == hipErrorNoDevice || e == hipErrorInvalidDevice ? NFLHIP_ERR_NO_DEVICE : NFLHIP_ERR_HIP,
+              std::string(where) + ": " + hipGetErrorString(e));
+}
+#define HIPCHK(ctx, call)                                   \
+  do {                                                      \
+    hipError_t _e = (call);                                 \
+    if (_e != hipSuccess) return hipfail(ctx, _e, #call);   \
+  } while (0)
+
+inline int set_device(const nflhip_ctx *ctx) {
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return NFLHIP_OK;
+}
+#define CHECK_CTX(ctx)                                                \
+  do {                                                                \
+    if (!(ctx)) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL"); \
+    int _rc = set_device(ctx);                                        \
+    if (_rc) return _rc;                                              \
+  } while (0)
+
+inline size_t poly_bytes(const nflhip_ctx *ctx, size_t batch) { return batch * ctx->shape.nm * ctx->shape.n * ctx->word; }
+inline bool bytes_overlap(const void *a, const void *b, size_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
+}
+
+constexpr size_t kStageHostMax = (size_t)1 << 20;
+inline void free_stage(nflhip_ctx *ctx, int slot) {
+  if (ctx->stage[slot]) (void)(ctx->stage_host[slot] ? hipHostFree(ctx->stage[slot]) : hipFree(ctx->stage[slot]));
+  ctx->stage[slot] = nullptr;
+  ctx->stage_bytes[slot] = 0;
+  ctx->stage_host[slot] = false;
+}
+inline int ensure_stage(nflhip_ctx *ctx, int slot, size_t bytes) {
+  if (ctx->stage_bytes[slot] >= bytes) return NFLHIP_OK;
+  free_stage(ctx, slot);
+  if (bytes <= kStageHostMax && hipHostMalloc(&ctx->stage[slot], bytes, hipHostMallocDefault) == hipSuccess) {
+    ctx->stage_host[slot] = true;
+  } else {   // (also when the pinned allocation is refused -- a locked-memory limit: the copies take over)
+    (void)hipGetLastError();
+    ctx->stage[slot] = nullptr;
+    HIPCHK(ctx, hipMalloc(&ctx->stage[slot], bytes));
+  }
+  ctx->stage_bytes[slot] = bytes;
+  return NFLHIP_OK;
+}

@@ -160,12 +160,17 @@ static Fix fix_exp_neg(const Fix &t) {
 
 }  // namespace
 
-int build_gauss_table(double sigma, unsigned security, unsigned samples, double center, GaussTable *out,
-                      std::string *err) {
+int check_gauss_params(double sigma, unsigned security, unsigned samples, double center, std::string *err) {
   if (!(sigma > 0) || !std::isfinite(sigma) || !std::isfinite(center) || security == 0 || samples == 0) {
     *err = "gaussian: sigma must be positive and finite, security and samples positive";
     return 1;
   }
+  return 0;
+}
+
+int build_gauss_table(double sigma, unsigned security, unsigned samples, double center, GaussTable *out,
+                      std::string *err) {
+  if (check_gauss_params(sigma, security, samples, center, err)) return 1;
   // FastGaussianNoise::init (FastGaussianNoise.hpp:239-262)
   const double k = (double)security + 1 + std::ceil(std::log((double)samples) / std::log(2.0));
   double tail = std::sqrt(1 + 2 * k * std::log(2.0));

@@ -16,6 +16,9 @@ struct GaussTable {
   std::vector<uint64_t> cdt;   // [entries][words]  floor(2^(64 words) * P(X <= x_min + k)), last entry all ones
 };
 
+// 0 when sigma is positive and finite, center finite, security and samples positive; else fills *err
+int check_gauss_params(double sigma, unsigned security, unsigned samples, double center, std::string *err);
+
 // returns 0 on success, else fills *err
 int build_gauss_table(double sigma, unsigned security, unsigned samples, double center, GaussTable *out, std::string *err);
 

@@ -232,3 +232,15 @@ def test_the_narrow_gaussian_draw_has_the_tables_distribution(sigma, security):
     hi = S.chacha20_lanes(KEY, 77, 0, N, 4, counter_base=S.domain_base("gauss32")).astype(np.uint64)
     lo = S.chacha20_lanes(KEY, 77, 0, N, 4, counter_base=S.domain_base("gauss32_ref")).astype(np.uint64)
     assert np.array_equal(r[:, 0], (hi << np.uint64(32)) | lo) and not np.array_equal(hi, lo)
+
+
+def test_gaussian_table_refuses_invalid_parameters_once_a_table_is_cached():
+    """the per-process table cache is keyed on (sigma, security, samples, center): a NaN compares equivalent to every key, so
+    the parameters are checked before the lookup -- never a cached table for another sigma"""
+    from nfllib_amd.engine import gauss_table
+    from nfllib_amd._lib import NflHipError
+    assert gauss_table(3.2)["entries"] > 0
+    for args in ((float("nan"),), (float("inf"),), (3.2, 128, 1024, float("nan")), (-1.0,)):
+        with pytest.raises(NflHipError) as e:
+            gauss_table(*args)
+        assert e.value.code == 1, args
