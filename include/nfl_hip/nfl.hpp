@@ -104,9 +104,12 @@
 #endif
 
 // The header is split into parts (round 6); this file is the umbrella: it owns the include guard, the standard includes and the
-// order.  types -> samplers -> queue -> expr -> poly -> poly_p -> batch.
+// order.  types -> samplers -> payload -> queue_plan -> queue -> expr -> poly -> poly_p -> batch (the deferred queue is three parts: the
+// handles' payloads, the planning of a run from its records, and recording / hand-over / launching on top of both).
 #include "types.hpp"
 #include "samplers.hpp"
+#include "payload.hpp"
+#include "queue_plan.hpp"
 #include "queue.hpp"
 #include "expr.hpp"
 #include "poly.hpp"

@@ -193,7 +193,7 @@ inline unsigned strict_exempt(const unsigned char *code, size_t len) {
   return as_companion & ~as_value;
 }
 
-// The lock of the recording path (detail::lazy<P>::mu, the buffer pool of detail::context): recursive, ONE atomic operation per
+// The lock of the recording path (detail::lazy<P>::mu in queue.hpp, the buffer pool of detail::context): recursive, ONE atomic operation per
 // outermost acquisition and a plain release store -- a std::recursive_mutex costs a locked instruction each way plus two
 // calls into libc, and the LWE demo's loop takes the queue's lock sixteen times per encryption: a third of its host time
 // inside a process that has other threads at all (the HIP runtime's), where glibc's single-thread shortcuts are off.
@@ -325,7 +325,7 @@ class light_lock {
   }
 };
 
-// Every ring type whose per-polynomial operations can be deferred (detail::lazy<P> below) registers the function that
+// Every ring type whose per-polynomial operations can be deferred (detail::lazy<P>, queue.hpp) registers the function that
 // runs its queue.  Whoever is about to invalidate something recorded operations refer to -- a FastGaussianNoise that
 // dies (its device tables), nfl::set_sampler_key (the key recorded draws will be made with) -- runs all queues first.
 // Leaked on purpose: objects with static storage may call it while the program's other statics are being destroyed.

@@ -15,7 +15,10 @@
 //   5. transforms that join the record of the operation that produced their operand (detail::lazy::join_transform) next
 //      to the ones that must stay records of their own: a reader between the two, two transforms in a row, a transform
 //      after a queue run, a constructor / transform pair of the wrong kinds, a value written twice, a fused
-//      multiply-add transformed back at once.
+//      multiply-add transformed back at once;
+//   6. the SECOND result of a fused pair of multiply-adds as the only thing its reader depends on, beside an earlier,
+//      independent operation of the reader's signature (whose group opens before the pair's): the second result is a
+//      write like the first.
 // Usage: deferred_loops [reps].  Exit code 0 = identical.  Runs against the real library (GPU) and against the toy
 // arithmetic of tests/cpp/mock (CPU: tests/test_host_logic.py).
 #include <nfl.hpp>
@@ -87,7 +90,7 @@ template <class T, size_t Degree, size_t NbModuli> static bool run(size_t reps) 
       save(acc);
       for (auto &k : keep) save(k);
     }
-    {  // 4. shapes around the transform fusion (detail::lazy::fuse): sequences it may rewrite and sequences it must leave alone
+    {  // 4. shapes around the transform fusion (detail::plan::fuse): sequences it may rewrite and sequences it must leave alone
       poly_p s{G(&fg)}, k1{nfl::uniform()}, k2{nfl::uniform()};
       s.ntt_pow_phi();
       const size_t m = reps / 4 + 3;
@@ -149,6 +152,28 @@ template <class T, size_t Degree, size_t NbModuli> static bool run(size_t reps) 
       for (size_t i = 0; i < m; ++i) {
         save(r0[i]);
         save(r1[i]);
+      }
+    }
+    {  // 6. the second result of a fused pair, read alone
+      poly_p k1{nfl::uniform()}, k2{nfl::uniform()};
+      const size_t m = reps / 4 + 3;
+      std::vector<poly_p> r0(m), r1(m), w(m), t(m);
+      for (size_t i = 0; i < m; ++i) r1[i] = poly_p{nfl::ZO_dist()};              // buffers (and values) exist before the loop below
+      (void)const_cast<const poly_p &>(r1[0])(0, 0);                              // ... (a host read runs the queue)
+      for (size_t i = 0; i < m; ++i) {
+        w[i] = k1 + k1;                                                           // depends on nothing recorded
+        poly_p u{G(&fg)}, e1{G(&fg, 2)}, e2{G(&fg, 2)};
+        u.ntt_pow_phi();
+        e1.ntt_pow_phi();
+        e2.ntt_pow_phi();
+        r0[i] = u * k1 + e1;
+        r1[i] = u * k2 + e2;
+        t[i] = r1[i] + r1[i];                                                     // same expression as w[i]; reads the second result only
+      }
+      for (size_t i = 0; i < m; i += 2) {
+        save(t[i]);
+        save(w[i]);
+        save(r0[i]);
       }
     }
     poly_p::synchronize();

@@ -137,27 +137,27 @@ def test_the_harness_notices_a_broken_queue(mock, tmp_path):
     commute): proof that the mock keeps what the queue's correctness depends on"""
     inc = tmp_path / "include"
     shutil.copytree(os.path.join(ROOT, "include"), inc)
-    hdr = inc / "nfl_hip" / "queue.hpp"      # (the deferred queue's part of the split header)
+    hdr = inc / "nfl_hip" / "queue_plan.hpp"      # (the planning part of the deferred queue: plan<P>::level, what a write waits for)
     text = hdr.read_text()
-    good = "L = std::max(L, std::max(wlev[o.out_pin], rlev[o.out_pin]) + 1);"
+    good = "L = std::max(L, std::max(wlev[k], rlev[k]) + 1);"
     assert good in text
-    hdr.write_text(text.replace(good, "L = std::max(L, wlev[o.out_pin] + 1);"))
+    hdr.write_text(text.replace(good, "L = std::max(L, wlev[k] + 1);"))
     exe = str(tmp_path / "fuzz_mutant")
     build_program("deferred_fuzz.cpp", exe, include=str(inc))
     r = run(exe, 40, 1)
     assert r.returncode != 0 and "all checks passed" not in r.stdout
 
 
-def _mutants_fail(tmp_path, edits, tag, also=None):
-    """builds deferred_loops.cpp against copies of include/ with ONE line of queue.hpp changed each (side by side) and expects
-    every one of them to fail the loop comparison"""
+def _mutants_fail(tmp_path, part, edits, tag, also=None):
+    """builds deferred_loops.cpp against copies of include/ with ONE line of `part` (queue.hpp: recording, queue_plan.hpp:
+    planning) changed each (side by side) and expects every one of them to fail the loop comparison"""
     from concurrent.futures import ThreadPoolExecutor
 
     def build(k):
         old, new = edits[k]
         inc = tmp_path / ("include%d" % k)
         shutil.copytree(os.path.join(ROOT, "include"), inc)
-        hdr = inc / "nfl_hip" / "queue.hpp"      # (the deferred queue's part of the split header)
+        hdr = inc / "nfl_hip" / part
         text = hdr.read_text()
         assert old in text
         text = text.replace(old, new)
@@ -178,14 +178,24 @@ def _mutants_fail(tmp_path, edits, tag, also=None):
 def test_the_harness_notices_a_broken_fusion(mock, tmp_path):
     """a header whose transform fusion forgets that a sampled-and-transformed temporary may still have a handle (or another
     reader) must fail the loop comparison: proof that the look-alike shapes of deferred_loops.cpp bite"""
-    _mutants_fail(tmp_path, [("      return fw[k] != d || r.dead[k] != 0;", "      return true;"), ("uses[size_t(dn)] != want_uses || ", "")], "loops",
+    _mutants_fail(tmp_path, "queue_plan.hpp", [("      return fw[k] != d || dead[k] != 0;", "      return true;"), ("uses[size_t(dn)] != want_uses || ", "")], "loops",
                   also={1: ("if (ux != 1 && ux != 2) continue;", "if (ux < 1) continue;")})
 
 
 def test_the_harness_notices_a_transform_joined_too_eagerly(mock, tmp_path):
     """a header whose transforms join the producing record although the value was read in between, or although that record
     already carries a transform, must fail the loop comparison (section 5 of deferred_loops.cpp)"""
-    _mutants_fail(tmp_path, [("p->rec_r > p->rec_w || ", ""), ("if (t.post || t.out != p || ", "if (t.out != p || ")], "join")
+    _mutants_fail(tmp_path, "queue.hpp", [("p->rec_r > p->rec_w || ", ""), ("if (t.post || t.out != p || ", "if (t.out != p || ")], "join")
+
+
+def test_the_harness_notices_a_broken_planning_rule(mock, tmp_path):
+    """the facts that queue_plan.hpp states once each: a visitor (plan<P>::for_each_pin) that forgets the second result of a fused
+    pair as a write (section 6 of deferred_loops.cpp: its only reader then runs before the pair), a signature key without the
+    samplers' second parameter (Gaussian draws of different amplifiers then share a launch), and a run finder that accepts an
+    operand stride that changes in mid-run (section 2: the key changes twice) must each fail the loop comparison"""
+    _mutants_fail(tmp_path, "queue_plan.hpp", [("    if (o.kind == K_FWD_FMA && o.f.out2) on_write(o.f.out2, o.f.out2_pin);\n", ""),
+                                               ("      k.w[3] = o.s.p1;\n", ""),
+                                               ("        else if (size_t(d) != s.in[j] * chunk) ok = false;\n", "")], "plan")
 
 
 def test_random_programs_under_address_and_undefined_behaviour_sanitizers(mock, tmp_path):
@@ -197,7 +207,7 @@ def test_random_programs_under_address_and_undefined_behaviour_sanitizers(mock, 
 
 
 def test_the_queue_thread_and_one_recording_thread_under_thread_sanitizer(mock, tmp_path):
-    """the hand-over protocol of the queue's own thread (lazy::take / post / execute / collect / retire) under ThreadSanitizer:
+    """the hand-over protocol of the queue's own thread (lazy::take / execute / collect / retire over detail::handover's post / wait) under ThreadSanitizer:
     one recording thread, runs handed over every few records (NFL_HIP_QUEUE_MIN=5, limit 40), random programs and the loop
     shapes: no data race -- a run works on the per-run arrays take() filled and never touches a payload -- and deferred ==
     immediate.  (NFL_HIP_NO_BIASED_LOCK: the buffer pool's lock is taken by both threads; its membarrier-based bias is not
