@@ -132,6 +132,20 @@ template <class P> class device_batch {
                                                            ntt_form ? NFLHIP_FORM_NTT : NFLHIP_FORM_COEFF, src.queue()),
                   "automorphisms");
   }
+  // RNS rescale (include/nflhip.h): *this = round(src / q), q the last modulus of src's ring, which has one modulus more than
+  // this batch's.  The two ring types own different streams: this batch's earlier work is awaited, the launch goes on src's
+  // stream, and the call returns once it has finished there, so later work on either batch sees the result.
+  template <class Q> void assign_rescale(const device_batch<Q> &src, bool ntt_form = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && Q::nmoduli == P::nmoduli + 1,
+                  "assign_rescale: the source ring has the same limbs and degree and exactly one modulus more");
+    if (src.size() != n_) throw std::runtime_error("nfl(hip): batch sizes differ");
+    if (src.device() != device()) throw std::runtime_error("nfl(hip): rescale operands on different devices");
+    sync();
+    src.strict("rescale");
+    detail::check(src.ctx(), nflhip_rescale_dev(src.ctx(), d_, src.data(), n_, ntt_form ? NFLHIP_FORM_NTT : NFLHIP_FORM_COEFF, src.queue()),
+                  "rescale");
+    src.sync();
+  }
   // CRT lift / project of the whole resident batch (gmp.hpp:183-219): out[(b*degree + i)*L .. +L) = little-endian limbs
   // of X_{b,i} in [0, Q), L = P::crt_limbs(); limbs2poly takes L_in limbs per coefficient
   void poly2limbs(std::vector<uint64_t> &out) const {
@@ -438,6 +452,12 @@ template <class P> class sharded_batch {
   void assign_automorphism(const sharded_batch &src, uint64_t k, bool ntt_form = false) {
     same_split(src);
     for (size_t r = 0; r < shards(); ++r) if (count(r)) shards_[r].assign_automorphism(src.shards_[r], k, ntt_form);
+  }
+  template <class Q> void assign_rescale(const sharded_batch<Q> &src, bool ntt_form = false) {  // shard by shard
+    if (src.size() != n_ || src.shards() != shards()) throw std::runtime_error("nfl(hip): sharded batches are split differently");
+    for (size_t r = 0; r < shards(); ++r)
+      if (src.count(r) != count(r) || src.shard(r).device() != shards_[r].device()) throw std::runtime_error("nfl(hip): sharded batches are split differently");
+    for (size_t r = 0; r < shards(); ++r) if (count(r)) shards_[r].assign_rescale(src.shard(r), ntt_form);
   }
   static void assign_automorphisms(sharded_batch *const *outs, const uint64_t *ks, size_t count, const sharded_batch &src,
                                    bool ntt_form = false) {

@@ -247,6 +247,27 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out._p = dst;
   }
 
+  // RNS rescale (nfl::rescale / nfl::rescale_ntt below) into the ring with one modulus less.  That ring type has a deferred
+  // queue, a stream and a buffer pool of its own: both queues run first, the output side's stream is awaited (earlier users
+  // of the pooled buffer), the launch goes on THIS (the input) side's stream, and the call returns once it has finished
+  // there -- operations recorded later on either side see the result.  Never fused into a queue's rewrites.
+  template <class, size_t, size_t> friend class poly_p;
+  static void rescale_into(poly_p<T, Degree, NbModuli - 1> &out, poly_p const &in, int form) {
+    static_assert(NbModuli >= 2, "nfl::rescale drops the last modulus: the input needs at least two");
+    typedef poly_p<T, Degree, NbModuli - 1> out_t;
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    ptr_type src = in._p;  // (holds the input while the launch is enqueued)
+    typename out_t::ptr_type dst = out_t::fresh();
+    const void *s = src->dev_ro();
+    void *d = dst->dev_wo();
+    const char *what = form == NFLHIP_FORM_NTT ? "rescale_ntt" : "rescale";
+    detail::check(out_t::ctx_t::get(), nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue()), what);
+    detail::check(ctx_t::get(), nflhip_rescale_dev(ctx_t::get(), d, s, 1, form, ctx_t::queue()), what);
+    detail::check(ctx_t::get(), nflhip_stream_sync(ctx_t::get(), ctx_t::queue()), what);
+    out._p = dst;
+  }
+
   /* ntt stuff - public API (poly_p.hpp:141-142): in place in HBM */
   void ntt_pow_phi() { transform(lazy_t::K_NTT_FWD); }
   void invntt_pow_invphi() { transform(lazy_t::K_NTT_INV); }
@@ -341,6 +362,25 @@ template <class T, size_t D, size_t M> void automorphism(poly_p<T, D, M> &out, p
 }
 template <class T, size_t D, size_t M> void automorphism_ntt(poly_p<T, D, M> &out, poly_p<T, D, M> const &in, uint64_t k) {
   poly_p<T, D, M>::automorphism_into(out, in, k, NFLHIP_FORM_NTT);
+}
+
+/* RNS rescale (include/nflhip.h): out = round(in / q), q the last modulus of in's ring; out lives in the ring over the first
+ * M - 1 moduli.  rescale_ntt takes and leaves values in the order ntt_pow_phi() produces.  M == 1 does not compile. */
+template <class T, size_t D, size_t M> void rescale(poly<T, D, M - 1> &out, poly<T, D, M> const &in) {
+  static_assert(M >= 2, "nfl::rescale drops the last modulus: the input needs at least two");
+  typedef poly<T, D, M> P;
+  detail::check(P::ctx(), nflhip_rescale(P::ctx(), out.data(), in.cdata(), 1, NFLHIP_FORM_COEFF), "rescale");
+}
+template <class T, size_t D, size_t M> void rescale_ntt(poly<T, D, M - 1> &out, poly<T, D, M> const &in) {
+  static_assert(M >= 2, "nfl::rescale_ntt drops the last modulus: the input needs at least two");
+  typedef poly<T, D, M> P;
+  detail::check(P::ctx(), nflhip_rescale(P::ctx(), out.data(), in.cdata(), 1, NFLHIP_FORM_NTT), "rescale_ntt");
+}
+template <class T, size_t D, size_t M> void rescale(poly_p<T, D, M - 1> &out, poly_p<T, D, M> const &in) {
+  poly_p<T, D, M>::rescale_into(out, in, NFLHIP_FORM_COEFF);
+}
+template <class T, size_t D, size_t M> void rescale_ntt(poly_p<T, D, M - 1> &out, poly_p<T, D, M> const &in) {
+  poly_p<T, D, M>::rescale_into(out, in, NFLHIP_FORM_NTT);
 }
 
 /* high level wrappers (poly.hpp:314-332) */

@@ -161,6 +161,32 @@ int nflhip_automorphism(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t b
 int nflhip_automorphism_multi_dev(nflhip_ctx *ctx, void *const *d_outs, const uint64_t *ks, size_t count, const void *d_in,
                                   size_t batch, int form, void *stream);
 
+/* ---- RNS rescale: exact division with rounding by the last modulus -----------------------
+ * The primitive behind CKKS rescaling, BGV / BFV modulus switching and the mod-down step of key switching.  Context: nmoduli >= 2
+ * moduli p_0 .. p_L (L = nmoduli - 1), q = p_L, Q = their product, Q' = Q / q, h = (q - 1) / 2.  For every coefficient position
+ * X in [0, Q) is the integer whose residues are the input words; the output holds the residues mod p_0 .. p_(L-1) of
+ *     Y = floor((X + h) / q) mod Q'
+ * -- X / q rounded to nearest (and the centred representative of X rounded correctly) -- as canonical words in [0, p_i).  In RNS
+ * arithmetic r = (x_L + h) mod q and y_i = (x_i + h - r) q^-1 mod p_i; no multi-precision integer is formed.
+ *   input   [batch][nmoduli][degree]
+ *   output  [batch][nmoduli - 1][degree], dense: the layout of the context over the first nmoduli - 1 moduli (callers chain
+ *           through that context to drop further moduli)
+ *   NFLHIP_FORM_COEFF  the formula word by word, one streaming pass.
+ *   NFLHIP_FORM_NTT    input and output in the order nflhip_ntt_fwd_dev produces: the dropped row is inverse-transformed under q,
+ *                      d_i = (h - r) mod p_i forward-transformed under p_i, y_i = (x_i + NTT_i(d_i)) q^-1 mod p_i, so that
+ *                      ntt_inv'(rescale_ntt(ntt_fwd(x))) == rescale_coeff(x) word for word (ntt_inv' of the smaller context).
+ *                      Rows below 32 KiB run in one launch with no scratch (it can be captured into a hipGraph); longer rows,
+ *                      and contexts created under NFLHIP_VARIANT=hipcc, compose the transform launchers around context-owned
+ *                      scratch (allocated on first use and when the batch grows).  NFLHIP_FORM_NTT | NFLHIP_RESCALE_COMPOSED
+ *                      selects the composed plan whatever the shape, NFLHIP_FORM_NTT | NFLHIP_RESCALE_FUSED the one-launch
+ *                      kernel (rows up to 32 KiB, NFLHIP_ERR_UNSUPPORTED beyond): each is the other's cross-check, same words.
+ * NFLHIP_ERR_INVALID: fewer than two moduli, a NULL pointer, an unknown form, an output that overlaps the input (the strides
+ * differ, so neither variant works in place), or a cyclic row context.  Every argument is checked before the device is touched. */
+#define NFLHIP_RESCALE_COMPOSED 0x100
+#define NFLHIP_RESCALE_FUSED 0x200
+int nflhip_rescale_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, int form, void *stream);
+int nflhip_rescale(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, int form);   /* staged host variant */
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

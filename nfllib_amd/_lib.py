@@ -21,6 +21,7 @@ ABI_VERSION = 6
 FMT_WORDS, FMT_I8, FMT_I16, FMT_I32 = range(4)
 FORM_COEFF, FORM_NTT = 0, 1
 AUTOMORPHISM_MAX_OUTPUTS = 16
+RESCALE_COMPOSED, RESCALE_FUSED = 0x100, 0x200
 
 # every symbol include/nflhip.h declares: (name, restype, argtypes)
 _vp, _sz, _i, _u64 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint64
@@ -45,6 +46,8 @@ SYMBOLS = [
     ("nflhip_automorphism_dev", _i, [_vp, _vp, _vp, _sz, _u64, _i, _vp]),
     ("nflhip_automorphism", _i, [_vp, _vp, _vp, _sz, _u64, _i]),
     ("nflhip_automorphism_multi_dev", _i, [_vp, _vp, C.POINTER(_u64), _sz, _vp, _sz, _i, _vp]),
+    ("nflhip_rescale_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
+    ("nflhip_rescale", _i, [_vp, _vp, _vp, _sz, _i]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     ("nflhip_eval_dev", _i, [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp]),

@@ -363,6 +363,26 @@ static int build_tables(nflhip_ctx *c, const void *Pv, const void *rootsv, const
   HIPCHK(nullptr, hipMalloc(&c->tabs.mc, mc.size() * sizeof(ModConst<T>)));
   HIPCHK(nullptr, hipMemcpy(c->tabs.mc, mc.data(), mc.size() * sizeof(ModConst<T>), hipMemcpyHostToDevice));
   c->tabs.mc_inc[0] = c->tabs.mc_inc[1] = nullptr;
+  // RNS rescale by the last modulus q (kernels_rescale.hip): q^-1 mod p_i, its Shoup companion and h = (q - 1) / 2 per kept row
+  c->tabs.resc = nullptr;
+  if (nm >= 2 && !c->cyclic) {
+    const uint64_t q = P[nm - 1];
+    std::vector<RescConst<T>> resc(nm - 1);
+    bool coprime = true;
+    for (size_t cm = 0; cm + 1 < nm; ++cm) {
+      const uint64_t p = P[cm];
+      if (q % p == 0) coprime = false;
+      const uint64_t qinv = powmod_h(q % p, p - 2, p);
+      resc[cm].qinv = (T)qinv;
+      resc[cm].qinv_sh = (T)shoup_h(qinv, p, wb);
+      resc[cm].h = (T)((q - 1) / 2);
+      resc[cm].p = (T)p;
+    }
+    if (coprime) {  // (a chain that repeats its last modulus has no rescale: the entry reports it)
+      HIPCHK(nullptr, hipMalloc(&c->tabs.resc, resc.size() * sizeof(RescConst<T>)));
+      HIPCHK(nullptr, hipMemcpy(c->tabs.resc, resc.data(), resc.size() * sizeof(RescConst<T>), hipMemcpyHostToDevice));
+    }
+  }
   if (sizeof(T) == 4 && n >= 1024 && n <= 4096 && !c->cyclic) {
     // 32-bit limbs, rows of 1024 / 2048 / 4096 words: the product on incomplete transforms (tools/gen_row1024_u32_asm.py base_mul,
     // level 2 only) reads (n / 4)^-1 in the n^-1 fields and floor(2^62 / p) - 2^32 in the mu field
@@ -746,7 +766,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -760,8 +780,10 @@ static int warm_up_device(nflhip_ctx *c) {
   return NFLHIP_OK;
 }
 
+// `parent`: a child context takes the parent's configuration instead of reading the environment again
 static int ctx_create_mode(nflhip_ctx **out, int device, int limb_bits, size_t degree, size_t nmoduli, const void *P,
-                           const void *primitive_roots, const void *invkmax, int kmax_log2, int cyclic) {
+                           const void *primitive_roots, const void *invkmax, int kmax_log2, int cyclic,
+                           const nflhip_ctx *parent = nullptr) {
   if (!out) return fail(nullptr, NFLHIP_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (limb_bits != 16 && limb_bits != 32 && limb_bits != 64)
@@ -789,7 +811,10 @@ static int ctx_create_mode(nflhip_ctx **out, int device, int limb_bits, size_t d
   c->shape.small_delta = 1;
   c->shape.nm_small = 0;
   // the environment is read HERE, once per context (include/nflhip.h "environment")
-  {
+  if (parent) {
+    c->shape.compiled_only = parent->shape.compiled_only;
+    c->shape.plan = parent->shape.plan;
+  } else {
     const char *v = getenv("NFLHIP_VARIANT");
     c->shape.compiled_only = v && (!strcmp(v, "hipcc") || !strcmp(v, "compiled")) ? 1 : 0;
     const char *x = getenv("NFLHIP_XCD");
@@ -833,7 +858,13 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   if (!ctx) return NFLHIP_OK;
   for (nflhip_ctx *child : ctx->row_ctx) nflhip_ctx_destroy(child);
   ctx->row_ctx.clear();
+  nflhip_ctx_destroy(ctx->resc_last);
+  nflhip_ctx_destroy(ctx->resc_kept);
+  ctx->resc_last = ctx->resc_kept = nullptr;
   (void)hipSetDevice(ctx->device);
+  if (ctx->ev_resc) (void)hipEventDestroy(ctx->ev_resc);
+  if (ctx->resc_scratch) (void)hipFree(ctx->resc_scratch);
+  if (ctx->tabs.resc) (void)hipFree(ctx->tabs.resc);
   if (ctx->hstream) (void)hipStreamDestroy(ctx->hstream);
   for (int k = 0; k < 2; ++k) {
     if (ctx->aux[k]) { (void)hipStreamSynchronize(ctx->aux[k]); (void)hipStreamDestroy(ctx->aux[k]); }
@@ -1033,6 +1064,103 @@ int nflhip_automorphism_multi_dev(nflhip_ctx *ctx, void *const *d_outs, const ui
                                   size_t batch, int form, void *stream) {
   CHECK_CTX(ctx);
   return automorphism_multi(ctx, d_outs, ks, count, d_in, batch, form, (hipStream_t)stream);
+}
+
+// RNS rescale by the last modulus (kernels_rescale.hip).  The composed NTT-form plan: the dropped rows go to context-owned scratch
+// and through the inverse transform of a one-modulus child context (the last modulus); d_i = (h - r) mod p_i is expanded into the
+// output, which the child context over the first nm - 1 moduli forward-transforms in place; one pass combines it with the kept
+// input rows.  Every transform launcher of the project therefore serves it, the compiled ones under NFLHIP_VARIANT=hipcc.
+static int rescale_children(nflhip_ctx *ctx) {  // under resc_mu
+  if (ctx->resc_last && ctx->resc_kept) return NFLHIP_OK;
+  const size_t nm = ctx->shape.nm;
+  return with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    std::vector<T> P(nm), roots(nm), invk(nm);
+    for (size_t cm = 0; cm < nm; ++cm) {
+      P[cm] = (T)ctx->h_P[cm];
+      roots[cm] = (T)ctx->h_roots[cm];
+      invk[cm] = (T)ctx->h_invk[cm];
+    }
+    int rc = NFLHIP_OK;
+    if (!ctx->resc_last)
+      rc = ctx_create_mode(&ctx->resc_last, ctx->device, ctx->shape.limb_bits, ctx->shape.n, 1, &P[nm - 1], &roots[nm - 1], &invk[nm - 1],
+                           ctx->kmax_log2, 0, ctx);
+    if (!rc && !ctx->resc_kept)
+      rc = ctx_create_mode(&ctx->resc_kept, ctx->device, ctx->shape.limb_bits, ctx->shape.n, nm - 1, P.data(), roots.data(), invk.data(),
+                           ctx->kmax_log2, 0, ctx);
+    return rc;
+  });
+}
+static int rescale_composed(nflhip_ctx *ctx, void *out, const void *in, size_t batch, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->resc_mu);
+  int rc = rescale_children(ctx);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t row = ctx->shape.n * ctx->word, nm = ctx->shape.nm, need = batch * row;
+  const bool cap = is_capturing(st);
+  if (ctx->resc_scratch_bytes < need) {
+    if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "rescale: the composed plan's scratch has to grow, which a stream capture cannot do");
+    if (ctx->resc_scratch) HIPCHK(ctx, hipFree(ctx->resc_scratch));  // (synchronises: nothing still reads it)
+    ctx->resc_scratch = nullptr;
+    ctx->resc_scratch_bytes = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->resc_scratch, need));
+    ctx->resc_scratch_bytes = need;
+  }
+  if (!ctx->ev_resc) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_resc, hipEventDisableTiming));
+  if (!cap && ctx->ev_resc_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_resc, 0));  // a previous call on another stream
+  HIPCHK(ctx, hipMemcpy2DAsync(ctx->resc_scratch, row, (const char *)in + (nm - 1) * row, nm * row, row, batch, hipMemcpyDeviceToDevice, st));
+  rc = nflhip_ntt_inv_dev(ctx->resc_last, ctx->resc_scratch, batch, st);
+  if (rc) return rc;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_rescale_expand<T>(ctx->shape, ctx->tabs, (T *)out, (const T *)ctx->resc_scratch, batch, st);
+  });
+  if (e != hipSuccess) return hipfail(ctx, e, "rescale: expand");
+  if (!cap) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev_resc, st));
+    ctx->ev_resc_valid = true;
+  }
+  rc = nflhip_ntt_fwd_dev(ctx->resc_kept, out, batch, st);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_rescale_combine<T>(ctx->shape, ctx->tabs, (T *)out, (const T *)in, batch, st);
+  });
+  if (e != hipSuccess) return hipfail(ctx, e, "rescale: combine");
+  return NFLHIP_OK;
+}
+// Where the one-launch kernel serves the NTT form by default: rows below 32 KiB.  Measured against the composed plan in one run
+// (profiles/r08_rescale.txt): 1.45x faster at u64/1024/2, 1.03x at u32/1024/2, but 0.95x at u64/4096/4 (rows of 32 KiB), where the
+// generated register-tiled transforms of the composed plan outrun the radix-4 LDS transforms by more than the traffic they add.
+static bool rescale_fused_on(const nflhip_ctx *ctx) {
+  return !ctx->shape.compiled_only && ctx->shape.n * ctx->word < 32768;
+}
+
+int nflhip_rescale_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, int form, void *stream) {
+  int rc = rescale_check(ctx, d_out, d_in, batch, form, false);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e;
+  if (form == NFLHIP_FORM_COEFF) {
+    e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_rescale_coeff<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *)d_in, batch, st);
+    });
+    return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "rescale");
+  }
+  const bool forced = (form & NFLHIP_RESCALE_FUSED) != 0;
+  if (forced || (form == NFLHIP_FORM_NTT && rescale_fused_on(ctx))) {
+    e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_rescale_ntt_fused<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *)d_in, batch, st);
+    });
+    if (e == hipSuccess) return NFLHIP_OK;
+    if (e != hipErrorNotSupported) return hipfail(ctx, e, "rescale (fused)");
+    if (forced) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "rescale: two rows of this shape do not fit the one-launch kernel's LDS");
+  }
+  return rescale_composed(ctx, d_out, d_in, batch, st);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

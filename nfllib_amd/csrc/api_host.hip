@@ -377,6 +377,19 @@ int nflhip_automorphism(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t b
   });
 }
 
+// RNS rescale: the result is one row per polynomial shorter than the input, so the call is staged whole (the pipeline's chunks
+// assume operands of one size)
+int nflhip_rescale(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, int form) {
+  int rc = rescale_check(ctx, h_out, h_in, batch, form, true);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t bytes = poly_bytes(ctx, batch), obytes = bytes - batch * ctx->shape.n * ctx->word;
+  const HostIn ins[] = {{0, h_in, bytes}};
+  return staged_call(ctx, batch, false, ins, 1, {1, h_out, obytes}, [&](const void *const *d, void *o, size_t cnt, void *st) {
+    return nflhip_rescale_dev(ctx, o, d[0], cnt, form, st);
+  });
+}
+
 int nflhip_ntt_row(nflhip_ctx *ctx, void *h_rows, size_t cm, int mode, size_t rows) {
   CHECK_CTX(ctx);
   if (rows == 0) return NFLHIP_OK;

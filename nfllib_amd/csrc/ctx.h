@@ -61,6 +61,14 @@ struct nflhip_ctx {
   int cyclic = 0;  // 0: negacyclic tables (the normal context); 1 / 2: cyclic over omega / omega^-1 (child contexts)
   std::mutex row_mu;
   std::vector<nflhip_ctx *> row_ctx;  // [2 * cm + inverse_tables]
+  // composed NTT-form rescale (api.hip rescale_composed): child contexts over the last modulus alone and over the first nm - 1,
+  // created on first use, and the scratch that holds the inverse-transformed dropped rows; calls are ordered on it by ev_resc
+  std::mutex resc_mu;
+  nflhip_ctx *resc_last = nullptr, *resc_kept = nullptr;
+  void *resc_scratch = nullptr;
+  size_t resc_scratch_bytes = 0;
+  hipEvent_t ev_resc = nullptr;
+  bool ev_resc_valid = false;
 };
 
 void pipe_destroy(nflhip_ctx *ctx);  // api_host.hip: frees the context's host-pointer pipeline
@@ -96,6 +104,24 @@ inline bool bytes_overlap(const void *a, const void *b, size_t bytes) {
   return x < y + bytes && y < x + bytes;
 }
 
+
+// nflhip_rescale / nflhip_rescale_dev: every argument check, before any device use (`host`: the staged host-pointer variant)
+inline int rescale_check(const nflhip_ctx *ctx, const void *out, const void *in, size_t batch, int form, bool host) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "rescale: a cyclic row context has no modulus chain");
+  if (ctx->shape.nm < 2) return fail(ctx, NFLHIP_ERR_INVALID, "rescale needs at least two moduli");
+  const int plan = form & (NFLHIP_RESCALE_COMPOSED | NFLHIP_RESCALE_FUSED), base = form & ~plan;  // a plan flag: NTT form only, one at most
+  if ((base != NFLHIP_FORM_COEFF && base != NFLHIP_FORM_NTT) || (plan && base != NFLHIP_FORM_NTT) ||
+      plan == (NFLHIP_RESCALE_COMPOSED | NFLHIP_RESCALE_FUSED))
+    return fail(ctx, NFLHIP_ERR_INVALID, "unknown polynomial form");
+  if (!ctx->tabs.resc) return fail(ctx, NFLHIP_ERR_INVALID, "rescale: the last modulus repeats an earlier one");
+  if (batch == 0) return NFLHIP_OK;
+  if (!out || !in) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t row = ctx->shape.n * ctx->word, ib = batch * ctx->shape.nm * row, ob = ib - batch * row;
+  const uintptr_t x = (uintptr_t)out, y = (uintptr_t)in;
+  if (x < y + ib && y < x + ob) return fail(ctx, NFLHIP_ERR_INVALID, host ? "the output overlaps the input" : "the output overlaps the input (the strides differ: never in place)");
+  return NFLHIP_OK;
+}
 constexpr size_t kStageHostMax = (size_t)1 << 20;
 inline void free_stage(nflhip_ctx *ctx, int slot) {
   if (ctx->stage[slot]) (void)(ctx->stage_host[slot] ? hipHostFree(ctx->stage[slot]) : hipFree(ctx->stage[slot]));

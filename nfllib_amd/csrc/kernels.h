@@ -26,6 +26,14 @@ template <typename T> struct ModConst {
   T mu2;        // floor(2^(2W-3)/p): Barrett constant for lazily reduced operands (< 2^(W-2) + 3*delta)
 };
 
+// Per-kept-row constants of the RNS rescale by the LAST modulus q = p_(nm-1) (kernels_rescale.hip): row i < nm - 1
+template <typename T> struct alignas(4 * sizeof(T)) RescConst {
+  T qinv;     // q^-1 mod p_i
+  T qinv_sh;  // its Shoup companion
+  T h;        // (q - 1) / 2, below every p_i (the moduli of a limb width have one bit length)
+  T p;        // p_i again, so that a kept row costs one 4-word record
+};
+
 // Twiddle pair as stored on the device: psi^bitrev(k) and its Shoup companion.
 template <typename T> struct alignas(2 * sizeof(T)) Tw {
   T w, wp;
@@ -71,6 +79,7 @@ struct DevTables {
   void *crt_bproj;  // the same for the projection: digit t of 256^k mod p_cm, k = 32 s + 16 (lane >> 5) + byte, cm = lane & 31, or nullptr
   uint64_t *crt_c2048; // [32][2] 2^2048 mod p_cm and its Shoup companion: how the residue of an input's upper 32 words joins the lower words'
   uint64_t *crt_coff; // [32][2] 2^18 p_cm + 128 sum_k (256^k mod p_cm in those digits), 128 bits: what the projection adds before reducing
+  void *resc;       // [nm - 1] RescConst<T>: the rescale by the last modulus, or nullptr with a single modulus
 };
 
 // ---- launchers (kernels_generic.hip) ----
@@ -102,6 +111,20 @@ hipError_t launch_fill_uniform(const Shape &s, const DevTables &t, T *d, size_t 
 template <typename T>
 hipError_t launch_automorphism(const Shape &s, const DevTables &t, T *const *outs, const uint64_t *ks, int count, const T *in,
                                int ntt_form, size_t batch, hipStream_t st);
+// RNS rescale by the last modulus (kernels_rescale.hip; include/nflhip.h "RNS rescale"): in = [batch][nm][n], out = the dense
+// [batch][nm - 1][n]; nm >= 2 and out must not overlap in (api.hip checks).  _coeff: the coefficient form, one streaming pass.
+// _ntt_fused: the NTT form in ONE launch, a workgroup per polynomial with two rows in LDS; hipErrorNotSupported when two rows
+// exceed 64 KiB.  The composed NTT-form plan (api.hip rescale_composed) runs the transform launchers between _expand (out row i =
+// (h - r) mod p_i from the inverse-transformed dropped rows t = [batch][n], r = (t + h) mod q) and _combine (out row i =
+// (in row i + out row i) q^-1 mod p_i).
+template <typename T>
+hipError_t launch_rescale_coeff(const Shape &s, const DevTables &t, T *out, const T *in, size_t batch, hipStream_t st);
+template <typename T>
+hipError_t launch_rescale_ntt_fused(const Shape &s, const DevTables &t, T *out, const T *in, size_t batch, hipStream_t st);
+template <typename T>
+hipError_t launch_rescale_expand(const Shape &s, const DevTables &t, T *out, const T *dropped, size_t batch, hipStream_t st);
+template <typename T>
+hipError_t launch_rescale_combine(const Shape &s, const DevTables &t, T *out, const T *in, size_t batch, hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);
@@ -248,6 +271,7 @@ hipError_t warm_crt_mfma(hipStream_t st);
 hipError_t warm_sample(hipStream_t st);
 hipError_t warm_wave(hipStream_t st);
 hipError_t warm_automorph(hipStream_t st);
+hipError_t warm_rescale(hipStream_t st);
 int polymul_level();   // 0 / 1 / 2: transforms of the coefficient-form products complete / incomplete (kernels_fast.hip, nflhip_debug_polymul_level)
 hipError_t launch_polymul_pipe64k_u64(const Shape &s, const DevTables &t, uint64_t *c_v, const uint64_t *a_v,
                                       const uint64_t *b_v, int cnt_v, const uint64_t *fa_src, uint64_t *fa_dst,

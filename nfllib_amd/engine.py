@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, FORM_COEFF, FORM_NTT,  # noqa: F401
+from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -160,6 +160,26 @@ class Engine:
         out = np.empty_like(a)
         form = FORM_NTT if ntt else FORM_COEFF
         self._chk(self.lib.nflhip_automorphism(self.ctx, _vp(out), _vp(a), self._hb(a), self._k(k), form))
+        return out
+
+    # ---- RNS rescale: divide and round by the last modulus (include/nflhip.h "RNS rescale") ----
+    def rescale(self, d, ntt=False, out=None, stream=None, composed=False, fused=False):
+        """floor((X + h) / q) of every coefficient, q the last modulus: [batch, nm, n] -> a new [batch, nm - 1, n] tensor
+        (or `out`, which must not overlap d) in the layout of Engine(limb_bits, degree, nm - 1); ntt=True for NTT-form
+        data; composed=True / fused=True force the composed NTT-form plan / the one-launch kernel"""
+        batch = self._batch(d)
+        if out is None:
+            out = _torch().empty((batch, self.nmoduli - 1, self.degree), dtype=self.torch_dtype, device=d.device)
+        form = (FORM_NTT | (RESCALE_COMPOSED if composed else 0) | (RESCALE_FUSED if fused else 0)) if ntt else FORM_COEFF
+        self._chk(self.lib.nflhip_rescale_dev(self.ctx, _vp(out), _vp(d), batch, form, self._stream(stream)))
+        return out
+
+    def h_rescale(self, a, ntt=False):
+        """host-pointer variant: a numpy [batch, nm, n] batch -> [batch, nm - 1, n], staged through the context"""
+        a = np.ascontiguousarray(a, dtype=self.np_dtype)
+        batch = self._hb(a)
+        out = np.empty((batch, self.nmoduli - 1, self.degree), dtype=self.np_dtype)
+        self._chk(self.lib.nflhip_rescale(self.ctx, _vp(out), _vp(a), batch, FORM_NTT if ntt else FORM_COEFF))
         return out
 
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
