@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -19,11 +20,10 @@
 
 #include "ctx.h"
 #include "gauss_table.h"
+#include "host_tables.h"
 #include "kernels.h"
 
 using namespace nflhip;
-
-typedef unsigned __int128 u128;
 
 // errno-style: one message per calling thread, so concurrent callers of one context never race on it
 static thread_local std::string g_last_error = "";
@@ -36,437 +36,59 @@ int set_error(int code, const std::string &msg) {  // (ctx.h fail, comm.hip)
 }  // namespace nflhip
 
 // ---------------------------------------------------------------------------
-// host-side modular helpers used only to BUILD tables (once per context)
+// the context's device tables: host_tables.cpp computes them, this uploads and frees them
 // ---------------------------------------------------------------------------
-static inline uint64_t mulmod_h(uint64_t a, uint64_t b, uint64_t p) { return (uint64_t)((u128)a * b % p); }
-static uint64_t powmod_h(uint64_t a, uint64_t e, uint64_t p) {
-  uint64_t r = 1 % p;
-  a %= p;
-  while (e) {
-    if (e & 1) r = mulmod_h(r, a, p);
-    a = mulmod_h(a, a, p);
-    e >>= 1;
-  }
-  return r;
-}
-static inline uint64_t shoup_h(uint64_t w, uint64_t p, int wb) { return (uint64_t)((((u128)w) << wb) / p); }
-static unsigned bitrev_h(unsigned k, int bits) {
-  unsigned r = 0;
-  for (int i = 0; i < bits; ++i) {
-    r = (r << 1) | (k & 1u);
-    k >>= 1;
-  }
-  return r;
+struct TableSlot {
+  void **dev;
+  const HostTables::Bytes *host;
+};
+// THE list of device tables: upload_tables and free_tables both walk it (h == nullptr: only the device side is read)
+static std::array<TableSlot, 16> table_slots(DevTables &t, const HostTables *h) {
+  static const HostTables none;
+  if (!h) h = &none;
+  return {{{&t.psi, &h->psi}, {&t.psi_lm, &h->psi_lm}, {&t.mc, &h->mc}, {&t.mc_inc[0], &h->mc_inc[0]}, {&t.mc_inc[1], &h->mc_inc[1]},
+           {&t.resc, &h->resc}, {(void **)&t.qhat, &h->qhat}, {(void **)&t.qsh, &h->qsh}, {(void **)&t.qparts, &h->qparts},
+           {(void **)&t.bparts, &h->bparts}, {(void **)&t.qhat_w, &h->qhat_w}, {(void **)&t.qsh_w, &h->qsh_w},
+           {&t.crt_bfrag, &h->crt_bfrag}, {&t.crt_bproj, &h->crt_bproj}, {(void **)&t.crt_coff, &h->crt_coff},
+           {(void **)&t.crt_c2048, &h->crt_c2048}}};
 }
 
-// little-endian multi-limb helpers for the CRT constants (gmp.hpp:113-155)
-typedef std::vector<uint64_t> Big;
-static void big_trim(Big &a) { while (!a.empty() && a.back() == 0) a.pop_back(); }
-static Big big_mul_u64(const Big &a, uint64_t w) {
-  Big r(a.size() + 1, 0);
-  u128 c = 0;
-  for (size_t i = 0; i < a.size(); ++i) {
-    c += (u128)a[i] * w;
-    r[i] = (uint64_t)c;
-    c >>= 64;
+// an empty host table leaves its pointer null; a failure leaves every pointer null or owned (nflhip_ctx_destroy frees them)
+static int upload_tables(nflhip_ctx *c, const HostTables &h) {
+  for (const TableSlot &s : table_slots(c->tabs, &h)) {
+    *s.dev = nullptr;
+    if (s.host->empty()) continue;
+    HIPCHK(nullptr, hipMalloc(s.dev, s.host->size()));
+    HIPCHK(nullptr, hipMemcpy(*s.dev, s.host->data(), s.host->size(), hipMemcpyHostToDevice));
   }
-  r[a.size()] = (uint64_t)c;
-  big_trim(r);
-  return r;
-}
-static uint64_t big_divrem_u64(const Big &a, uint64_t d, Big *q) {
-  Big out(a.size(), 0);
-  u128 r = 0;
-  for (size_t k = a.size(); k-- > 0;) {
-    r = (r << 64) | a[k];
-    out[k] = (uint64_t)(r / d);
-    r %= d;
-  }
-  big_trim(out);
-  if (q) *q = out;
-  return (uint64_t)r;
-}
-static size_t big_bits(const Big &a) {
-  if (a.empty()) return 0;
-  size_t b = 0;
-  uint64_t t = a.back();
-  while (t) { ++b; t >>= 1; }
-  return (a.size() - 1) * 64 + b;
-}
-static Big big_shl(const Big &a, int k, size_t limbs) {
-  Big r(limbs, 0);
-  for (size_t i = 0; i < a.size() && i < limbs; ++i) {
-    r[i] |= a[i] << k;
-    if (k && i + 1 < limbs) r[i + 1] |= a[i] >> (64 - k);
-  }
-  return r;
+  c->tabs.proj_K = h.proj_K;
+  c->tabs.inv_qtop = h.inv_qtop;
+  c->tabs.crt_Lw = h.crt_Lw;
+  c->tabs.crt_nsh = h.crt_nsh;
+  c->shape.crt_L = h.crt_L;
+  c->shape.crt_Lacc = h.crt_Lacc;
+  c->shape.crt_Q0 = h.crt_Q0;
+  c->shape.small_delta = h.small_delta;
+  c->shape.nm_small = h.nm_small;
+  c->h_Q = h.Q;
+  c->h_lifting = h.lifting;
+  c->h_P = h.P;
+  c->h_roots = h.roots;
+  c->h_invk = h.invk;
+  c->h_phi = h.phi;
+  return NFLHIP_OK;
 }
 
-// fewest moduli for which the lift runs as an int8 GEMM on the matrix cores (kernels_crt_mfma.hip).  Its cost hardly depends on
-// the modulus count (the tile is always 32 modulus slots x 256 columns: 0.48 ms at 12 moduli, 0.75 ms at 30 for 4 Mi
-// coefficients), the VALU kernels of kernels_crt.hip grow with its square (0.24 ms at 12, 0.56 at 20, 0.76 at 24, 1.19 at 30):
-// they cross between 20 and 21.  The projection's VALU kernels take a second launch beyond 16 residues: 0.40 ms at 16, 0.61 at 18
-// against the GEMM's 0.40 / 0.43 -- it takes over at 17 (same-box sweeps in profiles/r04_crt_mfma.txt)
-#ifndef NFLHIP_CRT_MFMA_MIN_NM
-#define NFLHIP_CRT_MFMA_MIN_NM 21
-#endif
-#ifndef NFLHIP_CRT_MFMA_PROJ_MIN_NM
-#define NFLHIP_CRT_MFMA_PROJ_MIN_NM 17
-#endif
+static void free_tables(nflhip_ctx *c) {
+  for (const TableSlot &s : table_slots(c->tabs, nullptr)) {
+    if (*s.dev) (void)hipFree(*s.dev);
+    *s.dev = nullptr;
+  }
+}
 
-template <typename T>
-static int build_tables(nflhip_ctx *c, const void *Pv, const void *rootsv, const void *invkv, int kmax_log2) {
-  const T *P = (const T *)Pv, *roots = (const T *)rootsv, *invk = (const T *)invkv;
-  const Shape &s = c->shape;
-  const int wb = s.limb_bits, logn = s.logn;
-  const size_t n = s.n, nm = s.nm;
-  // moduli sanity: the engine relies on p being 2 bits below the word (params.hpp:27-28,61-62,104-105)
-  for (size_t cm = 0; cm < nm; ++cm) {
-    const uint64_t p = P[cm];
-    if (p < 3 || (p >> (wb - 2)) != 0 || (p >> (wb - 3)) == 0)
-      return fail(nullptr, NFLHIP_ERR_INVALID, "modulus is not (word-2) bits long");
-    c->h_P.push_back(p);
-    c->h_roots.push_back(roots[cm]);
-    c->h_invk.push_back(invk[cm]);
-    if (((((uint64_t)1) << (wb - 2)) - p) >> 32) c->shape.small_delta = 0;
-    if (c->shape.small_delta) c->shape.nm_small = (int)cm + 1;
-  }
-  c->kmax_log2 = kmax_log2;
-  // CRT constants
-  Big Q(1, 1);
-  for (size_t cm = 0; cm < nm; ++cm) Q = big_mul_u64(Q, P[cm]);
-  const size_t bitsQ = big_bits(Q);
-  c->shape.crt_L = (bitsQ + 63) / 64;
-  c->shape.crt_Lacc = c->shape.crt_L + 1;
-  const size_t Lacc = c->shape.crt_Lacc;
-  c->h_Q = Q;
-  c->h_Q.resize(c->shape.crt_L, 0);
-  c->shape.crt_Q0 = Q.empty() ? 0 : Q[0];
-  const size_t kStride = 36;  // fixed, zero-padded row stride of the device CRT tables
-  const bool crt_ok = Lacc <= kStride;  // beyond that crt_lift reports NFLHIP_ERR_UNSUPPORTED, the transforms still work
-  std::vector<uint64_t> qhat(nm * kStride, 0), qsh(6 * kStride, 0);
-  std::vector<uint64_t> yinv(nm, 0);
-  c->h_lifting.resize(nm);
-  for (size_t cm = 0; cm < nm; ++cm) {
-    Big quot;
-    big_divrem_u64(Q, P[cm], &quot);                       // Q / p_cm            (mpz_divexact)
-    const uint64_t qmod = big_divrem_u64(quot, P[cm], nullptr);
-    yinv[cm] = powmod_h(qmod, P[cm] - 2, P[cm]);           // (Q/p_cm)^-1 mod p_cm (mpz_invert)
-    for (size_t k = 0; crt_ok && k < quot.size(); ++k) qhat[cm * kStride + k] = quot[k];
-    c->h_lifting[cm] = big_mul_u64(quot, yinv[cm]);        // lifting_integers[cm] (gmp.hpp:149-150)
-  }
-  for (int k = 0; crt_ok && k < 6; ++k) {
-    Big sh = big_shl(Q, k, Lacc);
-    for (size_t i = 0; i < Lacc; ++i) qsh[k * kStride + i] = sh[i];
-  }
-  // beyond the register-resident lift kernels (nm > 32 or more limbs than their tables hold): limb-serial tables
-  std::vector<uint64_t> qhat_w, qsh_w;
-  int Lw = 0, nsh = 0;
-  if (!crt_ok || nm > 32) {
-    Lw = (int)c->shape.crt_L + 2;
-    while ((((size_t)1) << nsh) <= nm) ++nsh;  // 2^nsh > nm >= S / Q
-    qhat_w.assign(nm * (size_t)Lw, 0);
-    qsh_w.assign((size_t)nsh * Lw, 0);
-    for (size_t cm = 0; cm < nm; ++cm) {
-      Big quot;
-      big_divrem_u64(Q, P[cm], &quot);
-      for (size_t k = 0; k < quot.size(); ++k) qhat_w[cm * Lw + k] = quot[k];
-    }
-    for (int k = 0; k < nsh; ++k) {
-      Big sh = big_shl(Q, k, (size_t)Lw);
-      for (int i = 0; i < Lw; ++i) qsh_w[(size_t)k * Lw + i] = sh[i];
-    }
-  }
-  // carry-free multiply-accumulate tables for 64-bit limbs (kernels_crt.hip)
-  std::vector<uint32_t> qparts, bparts;
-  int proj_K = 0;
-  if (wb == 64 && crt_ok && nm <= 32) {
-    const size_t L = c->shape.crt_L, S32 = 2 * kStride;
-    qparts.assign(nm * 3 * S32, 0);
-    for (size_t cm = 0; cm < nm; ++cm) {
-      Big quot;
-      big_divrem_u64(Q, P[cm], &quot);
-      for (int j = 0; j < 3; ++j) {
-        const Big sh = big_shl(quot, 21 * j, L);  // (Q/p) << 42 < Q: fits L words
-        for (size_t i = 0; i < L; ++i) {
-          qparts[(cm * 3 + j) * S32 + 2 * i] = (uint32_t)sh[i];
-          qparts[(cm * 3 + j) * S32 + 2 * i + 1] = (uint32_t)(sh[i] >> 32);
-        }
-      }
-    }
-    proj_K = (int)(2 * L + 2);
-    const size_t nmS = (nm + 3) & ~(size_t)3;  // row stride: zero padded, the kernel runs without guards
-    bparts.assign((size_t)proj_K * 2 * 3 * nmS, 0);
-    for (size_t cm = 0; cm < nm; ++cm) {
-      const uint64_t p = P[cm], two32 = (((uint64_t)1) << 32) % p;
-      uint64_t cur = 1 % p;  // 2^(32 t) mod p, t = 2k + half
-      for (size_t t = 0; t < (size_t)proj_K * 2; ++t) {
-        uint32_t *e = &bparts[t * 3 * nmS + cm];
-        e[0] = (uint32_t)(cur & 0x1fffff);
-        e[nmS] = (uint32_t)((cur >> 21) & 0x1fffff);
-        e[2 * nmS] = (uint32_t)(cur >> 42);
-        cur = mulmod_h(cur, two32, p);
-      }
-    }
-  }
-
-  // the lift as an int8 GEMM (kernels_crt_mfma.hip): balanced base-256 digits of Q/p_cm, laid out as the B operand of
-  // v_mfma_i32_32x32x32_i8 -- K-step s, N-tile t, lane (column j = lane & 31, half h = lane >> 5), byte e:
-  // modulus slot cm = 4 s + 2 h + (e >> 3), digit of y a = e & 7, column k = 8 j + t  ->  digit k - a of Q/p_cm.
-  // Slot 31 is the quotient row: the digits of Q itself against the single digit "-floor(S / Q)" (a = 0).
-  std::vector<int8_t> bfrag;
-  if (wb == 64 && crt_ok && nm >= NFLHIP_CRT_MFMA_MIN_NM && nm <= 32 && c->shape.crt_L >= 4 && c->shape.crt_L <= 31) {
-    const size_t ND = 264;
-    std::vector<int8_t> dig(32 * ND, 0);
-    for (size_t cm = 0; cm < 32; ++cm) {
-      Big quot;
-      if (cm < nm) big_divrem_u64(Q, P[cm], &quot);
-      else if (cm == 31) quot = Q;   // (with 32 moduli the slot is the 32nd modulus's and the kernel subtracts the quotient itself)
-      else continue;
-      int carry = 0;
-      for (size_t k = 0; k < ND; ++k) {
-        const size_t w = k / 8;
-        int v = (w < quot.size() ? (int)((quot[w] >> (8 * (k % 8))) & 0xff) : 0) + carry;
-        carry = 0;
-        if (v >= 128) { v -= 256; carry = 1; }
-        dig[cm * ND + k] = (int8_t)v;
-      }
-    }
-    bfrag.assign((size_t)8 * 8 * 64 * 16, 0);
-    for (int st = 0; st < 8; ++st)
-      for (int t = 0; t < 8; ++t)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int e = 0; e < 16; ++e) {
-            const int cm = 4 * st + 2 * (lane >> 5) + (e >> 3), a = e & 7, k = 8 * (lane & 31) + t;
-            if (k >= a && ((size_t)cm < nm || a == 0)) bfrag[(((size_t)st * 8 + t) * 64 + lane) * 16 + e] = dig[cm * ND + (k - a)];
-          }
-  }
-
-  // the projection as an int8 GEMM (kernels_crt_mfma.hip): balanced base-256 digits of 256^k mod p_cm, k < 256, as the B
-  // operand -- K-step s, N-tile t = digit, lane (cm = lane & 31, half h = lane >> 5), byte e: k = 32 s + 16 h + e -- and the
-  // per-residue constant 2^18 p + 128 sum_k (256^k mod p) (the input bytes enter as a - 128; the sum is made non-negative)
-  std::vector<int8_t> bproj;
-  std::vector<uint64_t> coff, c2048;
-  if (wb == 64 && c->shape.small_delta && nm >= NFLHIP_CRT_MFMA_PROJ_MIN_NM && nm <= 32) {
-    std::vector<int8_t> dig((size_t)32 * 256 * 8, 0);   // [cm][k][digit]
-    coff.assign(32 * 2, 0);
-    c2048.assign(32 * 2, 0);
-    for (size_t cm = 0; cm < nm; ++cm) {
-      const uint64_t p = P[cm];
-      uint64_t cur = 1 % p;
-      __int128 colsum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int k = 0; k < 256; ++k) {
-        int carry = 0;
-        for (int b = 0; b < 8; ++b) {
-          int v = (int)((cur >> (8 * b)) & 0xff) + carry;
-          carry = 0;
-          if (v >= 128 && b < 7) { v -= 256; carry = 1; }   // (the top digit of a 62-bit value is below 65: no carry out)
-          dig[(cm * 256 + k) * 8 + b] = (int8_t)v;
-          colsum[b] += 128 * v;
-        }
-        cur = mulmod_h(cur, 256 % p, p);
-      }
-      __int128 off = (__int128)p << 18;
-      for (int b = 0; b < 8; ++b) off += colsum[b] * ((__int128)1 << (8 * b));
-      coff[2 * cm] = (uint64_t)off;
-      coff[2 * cm + 1] = (uint64_t)((unsigned __int128)off >> 64);
-      c2048[2 * cm] = powmod_h(2 % p, 2048, p);
-      c2048[2 * cm + 1] = shoup_h(c2048[2 * cm], p, 64);
-    }
-    bproj.assign((size_t)8 * 8 * 64 * 16, 0);
-    for (int st = 0; st < 8; ++st)
-      for (int t = 0; t < 8; ++t)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int e = 0; e < 16; ++e) {
-            const size_t cm = lane & 31;
-            const int k = 32 * st + 16 * (lane >> 5) + e;
-            if (cm < nm) bproj[(((size_t)st * 8 + t) * 64 + lane) * 16 + e] = dig[(cm * 256 + k) * 8 + t];
-          }
-  }
-
-  // twiddles + per-modulus constants
-  std::vector<Tw<T>> psi(nm * n);
-  std::vector<ModConst<T>> mc(nm);
-  for (size_t cm = 0; cm < nm; ++cm) {
-    const uint64_t p = P[cm];
-    // phi: primitive 2n-th root from the primitive 2*kMax-th root (core.hpp:640-645)
-    uint64_t phi = roots[cm];
-    for (int i = 0; i < kmax_log2 - logn; ++i) phi = mulmod_h(phi, phi, p);
-    if (powmod_h(phi, n, p) != p - 1) return fail(nullptr, NFLHIP_ERR_INVALID, "primitive root has the wrong order");
-    c->h_phi.push_back(phi);
-    const uint64_t base = c->cyclic == 2 ? powmod_h(phi, 2 * n - 1, p) : phi;  // phi^-1 for the inverse tables
-    std::vector<uint64_t> pw(n);
-    uint64_t cur = 1;
-    for (size_t i = 0; i < n; ++i) {
-      pw[i] = cur;
-      cur = mulmod_h(cur, base, p);
-    }
-    Tw<T> *tw = psi.data() + cm * n;
-    for (size_t k = 0; k < n; ++k) {
-      // negacyclic: psi_br[k] = phi^bitrev(k).  With k = m + j (m = the power of two <= k: stage with m blocks, block j)
-      // that exponent is (n/2m)(2 brev_m(j) + 1); the cyclic transform core::ntt computes needs omega^((n/2m) brev_m(j))
-      // = phi^(bitrev(k) - n/2m) in the same slot, so every forward kernel runs it unchanged on this table.
-      size_t e = bitrev_h((unsigned)k, logn);
-      if (c->cyclic && k > 0) {
-        size_t m = 1;
-        while (2 * m <= k) m *= 2;
-        e -= n / (2 * m);
-      }
-      const uint64_t w = pw[e];
-      tw[k].w = (T)w;
-      tw[k].wp = (T)shoup_h(w, p, wb);
-    }
-    ModConst<T> &m = mc[cm];
-    m.p = (T)p;
-    m.p2 = (T)(2 * p);
-    m.mu = (T)((((u128)1) << (2 * wb - 4)) / p);
-    // n^-1 = kMax^-1 * (kMax/n) (core.hpp:664-665)
-    const uint64_t ninv = mulmod_h(invk[cm], (((uint64_t)1) << kmax_log2) / n, p);
-    if (mulmod_h(ninv, n % p, p) != 1 % p) return fail(nullptr, NFLHIP_ERR_INVALID, "invkMaxPolyDegree is not the inverse");
-    m.ninv = (T)ninv;
-    m.ninv_sh = (T)shoup_h(ninv, p, wb);
-    const uint64_t w1 = n >= 2 ? (uint64_t)tw[1].w : 1;
-    const uint64_t w1n = mulmod_h(w1, ninv, p);
-    m.w1ninv = (T)w1n;
-    m.w1ninv_sh = (T)shoup_h(w1n, p, wb);
-    const uint64_t beta = (uint64_t)((((u128)1) << 64) % p);
-    m.beta = (T)beta;
-    m.beta_sh = (T)shoup_h(beta, p, wb);
-    m.yinv = (T)yinv[cm];
-    m.yinv_sh = (T)shoup_h(yinv[cm], p, wb);
-    int bits = 0;
-    while (bits < wb && (((u128)1) << bits) <= (u128)p) ++bits;
-    m.mask = (T)(bits >= 64 ? ~(uint64_t)0 : ((((uint64_t)1) << bits) - 1));
-    m.delta = (T)((((uint64_t)1) << (wb - 2)) - p);
-    m.mu2 = (T)((((u128)1) << (2 * wb - 3)) / p);
-  }
-
-  HIPCHK(nullptr, hipMalloc(&c->tabs.psi, psi.size() * sizeof(Tw<T>)));
-  HIPCHK(nullptr, hipMemcpy(c->tabs.psi, psi.data(), psi.size() * sizeof(Tw<T>), hipMemcpyHostToDevice));
-  c->tabs.psi_lm = nullptr;
-  if (sizeof(T) == 8 && n >= 4096) {
-    // the generated 64-bit kernels read the last four stages (indices n/16 .. n-1) LANE-MAJOR: stage logn-4+s transposed
-    // from [(u << s) + g] to [g (n/16) + u], so that the 64 lanes of a wave fetch consecutive records
-    // (tools/gen_polymul_asm.py tw_base_lm); indices below n/16 are shared with the natural table
-    std::vector<Tw<T>> lm(psi);
-    const size_t m = n >> 4;
-    for (size_t cm = 0; cm < nm; ++cm)
-      for (int s = 0; s < 4; ++s) {
-        const Tw<T> *src = psi.data() + cm * n + (m << s);
-        Tw<T> *dst = lm.data() + cm * n + (m << s);
-        for (size_t u = 0; u < m; ++u)
-          for (size_t g = 0; g < ((size_t)1 << s); ++g) dst[g * m + u] = src[(u << s) + g];
-      }
-    HIPCHK(nullptr, hipMalloc(&c->tabs.psi_lm, lm.size() * sizeof(Tw<T>)));
-    HIPCHK(nullptr, hipMemcpy(c->tabs.psi_lm, lm.data(), lm.size() * sizeof(Tw<T>), hipMemcpyHostToDevice));
-  }
-  HIPCHK(nullptr, hipMalloc(&c->tabs.mc, mc.size() * sizeof(ModConst<T>)));
-  HIPCHK(nullptr, hipMemcpy(c->tabs.mc, mc.data(), mc.size() * sizeof(ModConst<T>), hipMemcpyHostToDevice));
-  c->tabs.mc_inc[0] = c->tabs.mc_inc[1] = nullptr;
-  // RNS rescale by the last modulus q (kernels_rescale.hip): q^-1 mod p_i, its Shoup companion and h = (q - 1) / 2 per kept row
-  c->tabs.resc = nullptr;
-  if (nm >= 2 && !c->cyclic) {
-    const uint64_t q = P[nm - 1];
-    std::vector<RescConst<T>> resc(nm - 1);
-    bool coprime = true;
-    for (size_t cm = 0; cm + 1 < nm; ++cm) {
-      const uint64_t p = P[cm];
-      if (q % p == 0) coprime = false;
-      const uint64_t qinv = powmod_h(q % p, p - 2, p);
-      resc[cm].qinv = (T)qinv;
-      resc[cm].qinv_sh = (T)shoup_h(qinv, p, wb);
-      resc[cm].h = (T)((q - 1) / 2);
-      resc[cm].p = (T)p;
-    }
-    if (coprime) {  // (a chain that repeats its last modulus has no rescale: the entry reports it)
-      HIPCHK(nullptr, hipMalloc(&c->tabs.resc, resc.size() * sizeof(RescConst<T>)));
-      HIPCHK(nullptr, hipMemcpy(c->tabs.resc, resc.data(), resc.size() * sizeof(RescConst<T>), hipMemcpyHostToDevice));
-    }
-  }
-  if (sizeof(T) == 4 && n >= 1024 && n <= 4096 && !c->cyclic) {
-    // 32-bit limbs, rows of 1024 / 2048 / 4096 words: the product on incomplete transforms (tools/gen_row1024_u32_asm.py base_mul,
-    // level 2 only) reads (n / 4)^-1 in the n^-1 fields and floor(2^62 / p) - 2^32 in the mu field
-    std::vector<ModConst<T>> mi(mc);
-    for (size_t cm = 0; cm < nm; ++cm) {
-      const uint64_t p = P[cm];
-      const uint64_t ng = mulmod_h((uint64_t)mc[cm].ninv, 4, p), wg = mulmod_h((uint64_t)mc[cm].w1ninv, 4, p);
-      mi[cm].ninv = (T)ng;
-      mi[cm].ninv_sh = (T)shoup_h(ng, p, wb);
-      mi[cm].w1ninv = (T)wg;
-      mi[cm].w1ninv_sh = (T)shoup_h(wg, p, wb);
-      mi[cm].mu = (T)(uint64_t)(((((u128)1) << 62) / p) - (((u128)1) << 32));
-    }
-    HIPCHK(nullptr, hipMalloc(&c->tabs.mc_inc[1], mi.size() * sizeof(ModConst<T>)));
-    HIPCHK(nullptr, hipMemcpy(c->tabs.mc_inc[1], mi.data(), mi.size() * sizeof(ModConst<T>), hipMemcpyHostToDevice));
-  }
-  if (sizeof(T) == 8 && n >= 1024 && !c->cyclic && (c->shape.small_delta || (n == 4096 && c->shape.nm_small > 0))) {
-    // the metric product on incomplete transforms (nflhip_polymul4096i{1,2}_asm): the inverse undoes 12 - level stages, so the
-    // scale folded into its last stage is (n / 2^level)^-1; the base multiplication reduces sums below 2^127 with
-    // floor(2^127 / p) = 2^65 + m, m < 2^35 (delta < 2^32), handed over in the mu2 field
-    for (int level = 1; level <= 2; ++level) {
-      std::vector<ModConst<T>> mi(mc);
-      for (size_t cm = 0; cm < nm; ++cm) {
-        const uint64_t p = P[cm];
-        const uint64_t ng = mulmod_h((uint64_t)mc[cm].ninv, (uint64_t)1 << level, p);
-        const uint64_t wg = mulmod_h((uint64_t)mc[cm].w1ninv, (uint64_t)1 << level, p);
-        mi[cm].ninv = (T)ng;
-        mi[cm].ninv_sh = (T)shoup_h(ng, p, wb);
-        mi[cm].w1ninv = (T)wg;
-        mi[cm].w1ninv_sh = (T)shoup_h(wg, p, wb);
-        mi[cm].mu2 = (T)(uint64_t)(((((u128)1) << 127) / p) - (((u128)1) << 65));
-      }
-      HIPCHK(nullptr, hipMalloc(&c->tabs.mc_inc[level - 1], mi.size() * sizeof(ModConst<T>)));
-      HIPCHK(nullptr, hipMemcpy(c->tabs.mc_inc[level - 1], mi.data(), mi.size() * sizeof(ModConst<T>), hipMemcpyHostToDevice));
-    }
-  }
-  HIPCHK(nullptr, hipMalloc((void **)&c->tabs.qhat, qhat.size() * sizeof(uint64_t)));
-  HIPCHK(nullptr, hipMemcpy(c->tabs.qhat, qhat.data(), qhat.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-  HIPCHK(nullptr, hipMalloc((void **)&c->tabs.qsh, qsh.size() * sizeof(uint64_t)));
-  HIPCHK(nullptr, hipMemcpy(c->tabs.qsh, qsh.data(), qsh.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-  c->tabs.qparts = nullptr;
-  c->tabs.bparts = nullptr;
-  c->tabs.proj_K = 0;
-  if (!qparts.empty()) {
-    HIPCHK(nullptr, hipMalloc((void **)&c->tabs.qparts, qparts.size() * sizeof(uint32_t)));
-    HIPCHK(nullptr, hipMemcpy(c->tabs.qparts, qparts.data(), qparts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMalloc((void **)&c->tabs.bparts, bparts.size() * sizeof(uint32_t)));
-    HIPCHK(nullptr, hipMemcpy(c->tabs.bparts, bparts.data(), bparts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    c->tabs.proj_K = proj_K;
-    // Q / 2^(32 max(2L - 3, 0)) from its top words (the kernel divides the top five 32-bit digits of the sum by it)
-    const size_t L = c->shape.crt_L;
-    long double qt = 0.0L;
-    for (size_t k = L; k-- > 0;) qt = qt * 18446744073709551616.0L + (long double)Q[k];
-    for (long w = 0; w < 2 * (long)L - 3; ++w) qt /= 4294967296.0L;
-    c->tabs.inv_qtop = (double)(1.0L / qt);
-  }
-  c->tabs.crt_bfrag = nullptr;
-  c->tabs.crt_bproj = nullptr;
-  c->tabs.crt_coff = nullptr;
-  c->tabs.crt_c2048 = nullptr;
-  if (!bproj.empty()) {
-    HIPCHK(nullptr, hipMalloc(&c->tabs.crt_bproj, bproj.size()));
-    HIPCHK(nullptr, hipMemcpy(c->tabs.crt_bproj, bproj.data(), bproj.size(), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMalloc((void **)&c->tabs.crt_coff, coff.size() * sizeof(uint64_t)));
-    HIPCHK(nullptr, hipMemcpy(c->tabs.crt_coff, coff.data(), coff.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMalloc((void **)&c->tabs.crt_c2048, c2048.size() * sizeof(uint64_t)));
-    HIPCHK(nullptr, hipMemcpy(c->tabs.crt_c2048, c2048.data(), c2048.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-  }
-  if (!bfrag.empty()) {
-    HIPCHK(nullptr, hipMalloc(&c->tabs.crt_bfrag, bfrag.size()));
-    HIPCHK(nullptr, hipMemcpy(c->tabs.crt_bfrag, bfrag.data(), bfrag.size(), hipMemcpyHostToDevice));
-  }
-  c->tabs.qhat_w = nullptr;
-  c->tabs.qsh_w = nullptr;
-  c->tabs.crt_Lw = Lw;
-  c->tabs.crt_nsh = nsh;
-  if (!qhat_w.empty()) {
-    HIPCHK(nullptr, hipMalloc((void **)&c->tabs.qhat_w, qhat_w.size() * sizeof(uint64_t)));
-    HIPCHK(nullptr, hipMemcpy(c->tabs.qhat_w, qhat_w.data(), qhat_w.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIPCHK(nullptr, hipMalloc((void **)&c->tabs.qsh_w, qsh_w.size() * sizeof(uint64_t)));
-    HIPCHK(nullptr, hipMemcpy(c->tabs.qsh_w, qsh_w.data(), qsh_w.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-  }
-  // the comparison flags: pinned host memory the kernels store into and the caller reads once the stream has drained (device memory +
-  // a copy when the pinned allocation is refused); a hit stores the call's TOKEN, so nothing has to be cleared in front of a launch
+// the comparison flags: pinned host memory the kernels store into and the caller reads once the stream has drained (device memory +
+// a copy when the pinned allocation is refused); a hit stores the call's TOKEN, so nothing has to be cleared in front of a launch
+static int alloc_cmp_flags(nflhip_ctx *c) {
   if (hipHostMalloc((void **)&c->tabs.flag, nflhip_ctx::kCmpSlots * sizeof(int), hipHostMallocDefault) == hipSuccess) {
     c->flag_host = true;
     std::memset(c->tabs.flag, 0, nflhip_ctx::kCmpSlots * sizeof(int));
@@ -808,8 +430,7 @@ static int ctx_create_mode(nflhip_ctx **out, int device, int limb_bits, size_t d
   c->shape.limb_bits = limb_bits;
   c->shape.n = degree;
   c->shape.nm = nmoduli;
-  c->shape.small_delta = 1;
-  c->shape.nm_small = 0;
+  c->kmax_log2 = kmax_log2;
   // the environment is read HERE, once per context (include/nflhip.h "environment")
   if (parent) {
     c->shape.compiled_only = parent->shape.compiled_only;
@@ -824,12 +445,16 @@ static int ctx_create_mode(nflhip_ctx **out, int device, int limb_bits, size_t d
   while ((((size_t)1) << c->shape.logn) < degree) c->shape.logn++;
   int rc;
   try {  // (host containers: no exception may cross the C boundary)
-    rc = with_limb(c, [&](auto z) { return build_tables<decltype(z)>(c, P, primitive_roots, invkmax, kmax_log2); });
+    HostTables h;
+    std::string err;
+    rc = build_host_tables(limb_bits, degree, nmoduli, cyclic, kmax_log2, P, primitive_roots, invkmax, &h, &err);
+    rc = rc != NFLHIP_OK ? fail(nullptr, rc, err) : upload_tables(c, h);
   } catch (const std::bad_alloc &) {
     rc = fail(nullptr, NFLHIP_ERR_NOMEM, "out of host memory while building the tables");
   } catch (const std::exception &ex) {
     rc = fail(nullptr, NFLHIP_ERR_INVALID, std::string("table construction failed: ") + ex.what());
   }
+  if (rc == NFLHIP_OK) rc = alloc_cmp_flags(c);
   if (rc == NFLHIP_OK) {
     hipError_t se = hipStreamCreateWithFlags(&c->hstream, hipStreamNonBlocking);
     for (int k = 0; k < 2 && se == hipSuccess; ++k) {
@@ -864,7 +489,6 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->ev_resc) (void)hipEventDestroy(ctx->ev_resc);
   if (ctx->resc_scratch) (void)hipFree(ctx->resc_scratch);
-  if (ctx->tabs.resc) (void)hipFree(ctx->tabs.resc);
   if (ctx->hstream) (void)hipStreamDestroy(ctx->hstream);
   for (int k = 0; k < 2; ++k) {
     if (ctx->aux[k]) { (void)hipStreamSynchronize(ctx->aux[k]); (void)hipStreamDestroy(ctx->aux[k]); }
@@ -875,22 +499,8 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   pipe_destroy(ctx);
   for (int i = 0; i < 4; ++i) free_stage(ctx, i);
   if (ctx->scratch) (void)hipFree(ctx->scratch);
-  if (ctx->tabs.psi) (void)hipFree(ctx->tabs.psi);
-  if (ctx->tabs.psi_lm) (void)hipFree(ctx->tabs.psi_lm);
-  if (ctx->tabs.mc) (void)hipFree(ctx->tabs.mc);
-  for (int i = 0; i < 2; ++i)
-    if (ctx->tabs.mc_inc[i]) (void)hipFree(ctx->tabs.mc_inc[i]);
-  if (ctx->tabs.qhat) (void)hipFree(ctx->tabs.qhat);
-  if (ctx->tabs.qsh) (void)hipFree(ctx->tabs.qsh);
-  if (ctx->tabs.qparts) (void)hipFree(ctx->tabs.qparts);
-  if (ctx->tabs.crt_bfrag) (void)hipFree(ctx->tabs.crt_bfrag);
-  if (ctx->tabs.crt_bproj) (void)hipFree(ctx->tabs.crt_bproj);
-  if (ctx->tabs.crt_coff) (void)hipFree(ctx->tabs.crt_coff);
-  if (ctx->tabs.crt_c2048) (void)hipFree(ctx->tabs.crt_c2048);
-  if (ctx->tabs.bparts) (void)hipFree(ctx->tabs.bparts);
+  free_tables(ctx);
   if (ctx->tabs.flag) (void)(ctx->flag_host ? hipHostFree(ctx->tabs.flag) : hipFree(ctx->tabs.flag));
-  if (ctx->tabs.qhat_w) (void)hipFree(ctx->tabs.qhat_w);
-  if (ctx->tabs.qsh_w) (void)hipFree(ctx->tabs.qsh_w);
   delete ctx;
   return NFLHIP_OK;
 }
@@ -928,39 +538,9 @@ int nflhip_get_table(const nflhip_ctx *ctx, int which, size_t cm, void *host_out
     case NFLHIP_TAB_SHOUPINVPOLY_INVPHIS:
     case NFLHIP_TAB_OMEGAS:
     case NFLHIP_TAB_INVOMEGAS: {
-      // the reference's own table layouts (poly.hpp:228-237), rebuilt on the host from phi: what a caller holding
-      // core::base sees.  Host arithmetic, once per request; the device never reads these.
       const size_t n = ctx->shape.n, words = (which == NFLHIP_TAB_OMEGAS || which == NFLHIP_TAB_INVOMEGAS) ? 2 * n : n;
       if (host_bytes < words * w) return fail(ctx, NFLHIP_ERR_INVALID, "output buffer too small");
-      const uint64_t p = ctx->h_P[cm], phi = ctx->h_phi[cm];
-      const int wb = ctx->shape.limb_bits;
-      std::vector<uint64_t> v(words, 0);
-      const uint64_t invphi = powmod_h(phi, 2 * n - 1, p);
-      if (which == NFLHIP_TAB_PHIS || which == NFLHIP_TAB_SHOUPPHIS) {  // core.hpp:649-656
-        uint64_t t = 1;
-        for (size_t i = 0; i < n; ++i) {
-          v[i] = which == NFLHIP_TAB_PHIS ? t : shoup_h(t, p, wb);
-          t = mulmod_h(t, phi, p);
-        }
-      } else if (which == NFLHIP_TAB_INVPOLY_INVPHIS || which == NFLHIP_TAB_SHOUPINVPOLY_INVPHIS) {  // core.hpp:664-676
-        uint64_t t = mulmod_h(ctx->h_invk[cm], (((uint64_t)1) << ctx->kmax_log2) / n, p);
-        for (size_t i = 0; i < n; ++i) {
-          v[i] = which == NFLHIP_TAB_INVPOLY_INVPHIS ? t : shoup_h(t, p, wb);
-          t = mulmod_h(t, invphi, p);
-        }
-      } else {  // core::prep_wtab, core.hpp:564-581: stage-concatenated powers, Shoup companions at offset n
-        uint64_t wcur = which == NFLHIP_TAB_OMEGAS ? mulmod_h(phi, phi, p) : mulmod_h(invphi, invphi, p);
-        size_t pos = 0;
-        for (size_t K = n; K >= 2; K /= 2) {
-          uint64_t wi = 1;
-          for (size_t i = 0; i < K / 2; ++i, ++pos) {
-            v[pos] = wi;
-            v[n + pos] = shoup_h(wi, p, wb);
-            wi = mulmod_h(wi, wcur, p);
-          }
-          wcur = mulmod_h(wcur, wcur, p);
-        }
-      }
+      const std::vector<uint64_t> v = reference_table(ctx->h_P[cm], ctx->h_phi[cm], ctx->h_invk[cm], ctx->kmax_log2, n, ctx->shape.limb_bits, which);
       for (size_t i = 0; i < words; ++i) {
         if (w == 8) ((uint64_t *)host_out)[i] = v[i];
         else if (w == 4) ((uint32_t *)host_out)[i] = (uint32_t)v[i];

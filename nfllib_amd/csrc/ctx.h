@@ -1,5 +1,5 @@
 // ctx.h -- the context of include/nflhip.h and the error / staging helpers shared by the C-ABI translation units:
-// api.hip (context, tables, device-pointer entry points) and api_host.hip (host-pointer entry points).  Not installed.
+// api.hip (context, upload of the tables host_tables.cpp computes, device-pointer entry points) and api_host.hip (host-pointer entry points).  Not installed.
 #pragma once
 #include "../../include/nflhip.h"
 

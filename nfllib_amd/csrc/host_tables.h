@@ -1,0 +1,39 @@
+// host_tables.h -- every per-context table, computed on the host (see host_tables.cpp).  No HIP: api.hip uploads the result.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace nflhip {
+
+struct HostTables {
+  typedef std::vector<unsigned char> Bytes;
+  // the device tables, byte for byte as DevTables (kernels.h) describes them; an empty vector: the context has no such table
+  Bytes psi, psi_lm, mc, mc_inc[2], resc;
+  Bytes qhat, qsh, qparts, bparts, qhat_w, qsh_w;
+  Bytes crt_bfrag, crt_bproj, crt_coff, crt_c2048;
+  // the scalars of DevTables
+  int proj_K = 0;
+  double inv_qtop = 0;
+  int crt_Lw = 0, crt_nsh = 0;
+  // the shape facts the moduli decide (Shape, kernels.h)
+  size_t crt_L = 0, crt_Lacc = 0;
+  uint64_t crt_Q0 = 0;
+  int small_delta = 1, nm_small = 0;
+  // host copies the context keeps for introspection and for its child contexts
+  std::vector<uint64_t> Q;                     // moduli_product limbs
+  std::vector<std::vector<uint64_t>> lifting;  // lifting_integers[cm]
+  std::vector<uint64_t> P, roots, invk, phi;   // params<T>::P / primitive_roots / invkMaxPolyDegree, phi = 2n-th root per modulus
+};
+
+// Fills *out for n = 2^k coefficients and nm moduli of limb_bits (16 / 32 / 64) bits: P, roots, invk are arrays of nm limbs of that
+// width.  cyclic: 0 negacyclic tables, 1 / 2 cyclic over omega / omega^-1.  Returns NFLHIP_OK, or an NFLHIP_ERR_* code with *err set.
+int build_host_tables(int limb_bits, size_t n, size_t nm, int cyclic, int kmax_log2, const void *P, const void *roots,
+                      const void *invk, HostTables *out, std::string *err);
+
+// nflhip_get_table, NFLHIP_TAB_PHIS .. NFLHIP_TAB_INVOMEGAS: one modulus's table in the reference's own layout (n words, 2 n for
+// the two omega tables), each word below 2^limb_bits
+std::vector<uint64_t> reference_table(uint64_t p, uint64_t phi, uint64_t invk, int kmax_log2, size_t n, int limb_bits, int which);
+
+}  // namespace nflhip

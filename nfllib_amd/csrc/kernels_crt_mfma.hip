@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256, 2) void k_crt_lift_mfma(u64 *out, const u64 *d
 #endif
 }
 
-// `bfrag` / `qdig`: DevTables::crt_bfrag (api.hip build_tables; its modulus slot 31 holds the digits of Q itself), row 0 of
+// `bfrag` / `qdig`: DevTables::crt_bfrag (host_tables.cpp lift_fragments; its modulus slot 31 holds the digits of Q itself), row 0 of
 // DevTables::qsh (Q as 32-bit digits, zero padded to 72).  hipErrorNotSupported when the shape has no table (few moduli: the
 // VALU kernels are on the memory system there) or the batch is not a multiple
 // of the tile.
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256, 2) void k_crt_project_mfma(u64 *d, const u64 *
   }
 }
 
-// `bproj` / `coff` / `c2048`: DevTables::crt_bproj / crt_coff / crt_c2048 (api.hip build_tables).  hipErrorNotSupported when the
+// `bproj` / `coff` / `c2048`: DevTables::crt_bproj / crt_coff / crt_c2048 (host_tables.cpp projection_fragments).  hipErrorNotSupported when the
 // shape has no table (few moduli), the input is wider than 64 words or the batch is not a multiple of the tile.
 hipError_t launch_crt_project_mfma_u64(const Shape &s, const DevTables &t, uint64_t *d, const uint64_t *limbs, size_t L_in,
                                        size_t batch, hipStream_t st) {

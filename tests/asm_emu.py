@@ -1064,7 +1064,7 @@ def run_kernel(asm_text, mem, kernarg, grid, lds_bytes, waves_per_wg=4, concurre
 
 def device_tables(limb_bits, n, nm, prm, lane_major=False, incomplete=0):
     """the twiddle table (Tw<T>: {psi^bitrev(k), Shoup companion}) and the ModConst<T> records exactly as
-    nfllib_amd/csrc/api.hip build_tables lays them out on the device (negacyclic case), from params<T>.
+    nfllib_amd/csrc/host_tables.cpp twiddles_and_modconst lays them out on the device (negacyclic case), from params<T>.
     lane_major: DevTables::psi_lm, what the ring-mode 64-bit kernels (rows of 8192 words and up) are handed -- the last four stages (indices n/16 .. n-1)
     with stage logn-4+s transposed from [(u << s) + g] to [g * (n/16) + u]"""
     wb, logn = limb_bits, n.bit_length() - 1
@@ -1089,7 +1089,7 @@ def device_tables(limb_bits, n, nm, prm, lane_major=False, incomplete=0):
         rec = [p, 2 * p, (1 << (2 * wb - 4)) // p, ninv, (ninv << wb) // p, w1n, (w1n << wb) // p, beta, (beta << wb) // p,
                0, 0, (1 << bits) - 1, (1 << (wb - 2)) - p, (1 << (2 * wb - 3)) // p]   # (yinv: CRT only, unused by the row kernels)
         if incomplete:
-            # DevTables::mc_inc (api.hip build_tables): the records of the incomplete-transform product (tools/asmgen/incomplete.py) --
+            # DevTables::mc_inc (host_tables.cpp incomplete_records): the records of the incomplete-transform product (tools/asmgen/incomplete.py) --
             # (n / G)^-1 in the n^-1 fields, floor(2^127 / p) - 2^65 in the mu2 field
             g = 1 << incomplete
             ninv_g = ninv * g % p

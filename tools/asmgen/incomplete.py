@@ -15,7 +15,7 @@ Base multiplication, per group (c_k = sum_{i+j=k} a_i b_j + zeta sum_{i+j=k+G} a
         th = T >> 63,  mu = floor(2^127 / p) = 2^65 + m  (m < 2^35),  q^ = 2 th + floor(th m / 2^64)   (mod 2^64: T / p may
         reach 2^64 for lazily reduced operands, and only q^ mod 2^64 enters r),  r = T - q^ p  in [0, 4p)  (q - q^ <= 3),
     then the two-bit fold, like the point-wise product of the complete kernel.
-The host hands this kernel a ModConst record whose n^-1 fields are (n / G)^-1 and whose mu2 field is m (api.hip build_tables).
+The host hands this kernel a ModConst record whose n^-1 fields are (n / G)^-1 and whose mu2 field is m (host_tables.cpp incomplete_records).
 Instruction count per thread against the complete kernel: -(2 x 16 x 18 + 16 x 20) per dropped stage, + the base multiplication
 instead of 16 point-wise products (tools/asm_cost.py prints both)."""
 from . import state as cfg

@@ -77,7 +77,7 @@ RING_RECOMPUTE_TWA = False
 # table) read a lane-major copy of those stages: stage S = logn-4+s holds M 2^s records (M = n/16 = 256 << r), natural position
 # (u << s) + g for thread-index u = 256 blk + t and group g, lane-major position g M + u.  A wave's 64 lanes then fetch 64
 # CONSECUTIVE records per load (8 cache lines, all bytes used) instead of 64 records 16 << s bytes apart (up to 64 lines,
-# 16 bytes used of each: 5.7 x the L2 -> L1 traffic over a pass).  The host lays the copy out (api.hip build_tables,
+# 16 bytes used of each: 5.7 x the L2 -> L1 traffic over a pass).  The host lays the copy out (host_tables.cpp lane_major,
 # DevTables::psi_lm); every other pass reads indices below n/16, which both layouts share.
 #   ascending  (F3): index = K + ((256 c) << r) + t,          c  = 2^s - 1 + g            (K = 256 (2^r + blk))
 #   descending (I1): index = K + ((256 c') << r) - 1 - t,     c' = 2^(s+1) - 2 - g        (K = (512 << r) - 256 blk)
