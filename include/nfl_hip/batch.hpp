@@ -146,6 +146,23 @@ template <class P> class device_batch {
                   "rescale");
     src.sync();
   }
+  // Sums of products across polynomials (include/nflhip.h): this batch holds `groups` polynomials, a and b groups * terms each,
+  // term-minor: (*this)[g] = sum_j a[g * terms + j] * b[g * terms + j].  assign_matvec: v holds the `terms` polynomials every
+  // group shares, (*this)[g] = sum_j m[g * terms + j] * v[j].  The operands must be other batches.
+  void assign_dot(const device_batch &a, const device_batch &b, size_t terms) {
+    if (terms == 0 || a.n_ != n_ * terms || b.n_ != n_ * terms) throw std::runtime_error("nfl(hip): dot operands hold groups * terms polynomials");
+    same_device(a), same_device(b);
+    a.strict("dot"); b.strict("dot");
+    const nflhip_dot_operand x = {a.d_, terms, 1}, y = {b.d_, terms, 1};
+    detail::check(ctx(), nflhip_dot_dev(ctx(), d_, &x, &y, nullptr, n_, terms, 0, queue()), "dot");
+  }
+  void assign_matvec(const device_batch &m, const device_batch &v) {
+    if (v.n_ == 0 || m.n_ != n_ * v.n_) throw std::runtime_error("nfl(hip): the matrix holds groups * terms polynomials, the vector terms");
+    same_device(m), same_device(v);
+    m.strict("matvec"); v.strict("matvec");
+    const nflhip_dot_operand x = {m.d_, v.n_, 1}, y = {v.d_, 0, 1};
+    detail::check(ctx(), nflhip_dot_dev(ctx(), d_, &x, &y, nullptr, n_, v.n_, 0, queue()), "matvec");
+  }
   // CRT lift / project of the whole resident batch (gmp.hpp:183-219): out[(b*degree + i)*L .. +L) = little-endian limbs
   // of X_{b,i} in [0, Q), L = P::crt_limbs(); limbs2poly takes L_in limbs per coefficient
   void poly2limbs(std::vector<uint64_t> &out) const {
@@ -266,6 +283,9 @@ template <class P> class device_batch {
  private:
   void same_size(const device_batch &o) const {
     if (o.n_ != n_) throw std::runtime_error("nfl(hip): batch size mismatch");
+    if (o.c_ != c_) throw std::runtime_error("nfl(hip): the batches of one operation must live on one device");
+  }
+  void same_device(const device_batch &o) const {
     if (o.c_ != c_) throw std::runtime_error("nfl(hip): the batches of one operation must live on one device");
   }
   void sample(int dist, uint64_t p0, uint64_t p1, const char *what, size_t first_poly, uint64_t stream_id) {

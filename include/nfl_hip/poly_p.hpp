@@ -268,6 +268,31 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out._p = dst;
   }
 
+  // Sum of products (nfl::dot / nfl::dot_add below): the deferred queue of this ring type runs first (on the caller), then the
+  // pointer form of the entry on the queue's stream, 16 terms per launch, chained through the addend.  The result gets a
+  // payload of its own, so `out` may be one of the inputs and copy-on-write sharers of out's old value keep it.
+  static void dot_into(poly_p &out, poly_p const *a, poly_p const *b, size_t terms, bool add) {
+    if (terms == 0) throw std::runtime_error("nfl(hip): dot of zero terms");
+    lazy_t::inst().flush();
+    ptr_type old = out._p;  // (holds the addend while the launches are enqueued)
+    ptr_type dst = fresh();
+    void *d = dst->dev_wo();
+    const void *addend = add ? old->dev_ro() : nullptr;
+    for (size_t k = 0; k < terms; k += NFLHIP_DOT_MAX_POINTERS) {
+      const size_t cnt = terms - k < NFLHIP_DOT_MAX_POINTERS ? terms - k : NFLHIP_DOT_MAX_POINTERS;
+      ptr_type hold[2 * NFLHIP_DOT_MAX_POINTERS];
+      const void *pa[NFLHIP_DOT_MAX_POINTERS], *pb[NFLHIP_DOT_MAX_POINTERS];
+      for (size_t j = 0; j < cnt; ++j) {
+        hold[2 * j] = a[k + j]._p;
+        hold[2 * j + 1] = b[k + j]._p;
+        pa[j] = hold[2 * j]->dev_ro();
+        pb[j] = hold[2 * j + 1]->dev_ro();
+      }
+      detail::check(ctx_t::get(), nflhip_dot_ptrs_dev(ctx_t::get(), d, pa, pb, cnt, k == 0 ? addend : d, ctx_t::queue()), "dot");
+    }
+    out._p = dst;
+  }
+
   /* ntt stuff - public API (poly_p.hpp:141-142): in place in HBM */
   void ntt_pow_phi() { transform(lazy_t::K_NTT_FWD); }
   void invntt_pow_invphi() { transform(lazy_t::K_NTT_INV); }
@@ -381,6 +406,37 @@ template <class T, size_t D, size_t M> void rescale(poly_p<T, D, M - 1> &out, po
 }
 template <class T, size_t D, size_t M> void rescale_ntt(poly_p<T, D, M - 1> &out, poly_p<T, D, M> const &in) {
   poly_p<T, D, M>::rescale_into(out, in, NFLHIP_FORM_NTT);
+}
+
+/* Sums of products across polynomials (include/nflhip.h): out = sum_{j < terms} a[j] * b[j], element-wise in every row -- the
+ * inner product of NTT-form operands.  dot_add: out += the sum.  a and b are arrays of `terms` polynomials; out may be one of
+ * them.  On poly the arrays go through the staged host entry; on poly_p the sum runs on the resident values. */
+template <class T, size_t D, size_t M> void dot(poly<T, D, M> &out, poly<T, D, M> const *a, poly<T, D, M> const *b, size_t terms) {
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  P *tmp = P::make_temp();  // (out may be an element of a or b)
+  const int rc = nflhip_dot(P::ctx(), tmp->data(), a->cdata(), b->cdata(), 1, terms, 0);
+  if (rc == 0) std::memcpy(static_cast<void *>(out.data()), tmp->cdata(), sizeof(P));
+  P::drop_temp(tmp);
+  detail::check(P::ctx(), rc, "dot");
+}
+template <class T, size_t D, size_t M> void dot_add(poly<T, D, M> &out, poly<T, D, M> const *a, poly<T, D, M> const *b, size_t terms) {
+  typedef poly<T, D, M> P;
+  P *tmp = P::make_temp();
+  try {
+    dot(*tmp, a, b, terms);
+    out = out + *tmp;
+  } catch (...) {
+    P::drop_temp(tmp);
+    throw;
+  }
+  P::drop_temp(tmp);
+}
+template <class T, size_t D, size_t M> void dot(poly_p<T, D, M> &out, poly_p<T, D, M> const *a, poly_p<T, D, M> const *b, size_t terms) {
+  poly_p<T, D, M>::dot_into(out, a, b, terms, false);
+}
+template <class T, size_t D, size_t M> void dot_add(poly_p<T, D, M> &out, poly_p<T, D, M> const *a, poly_p<T, D, M> const *b, size_t terms) {
+  poly_p<T, D, M>::dot_into(out, a, b, terms, true);
 }
 
 /* high level wrappers (poly.hpp:314-332) */

@@ -187,6 +187,43 @@ int nflhip_automorphism_multi_dev(nflhip_ctx *ctx, void *const *d_outs, const ui
 int nflhip_rescale_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, int form, void *stream);
 int nflhip_rescale(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, int form);   /* staged host variant */
 
+/* ---- sums of products across polynomials: dot and matrix-vector forms ----------------------
+ * The inner step of an XPIR reply (out[r] = sum_j db[r][j] (.) query[j]), of key switching (sum_j digit_j (.) key_j), of
+ * relinearisation and of any linear layer over ciphertexts.  For every group g < groups, row m and position i
+ *     out[g][m][i] = (addend[g][m][i] + sum_{j < terms} a(g,j)[m][i] * b(g,j)[m][i]) mod p_m
+ * as the canonical word in [0, p_m); the inputs are canonical words (the contract of the element-wise MUL).  The operation does not
+ * look at the form: callers pass NTT-form data.  One pass: the products are accumulated unreduced in a double-width word and
+ * reduced once per 16 terms, the accumulator never touches memory, and every input word is read once (a shared operand once per
+ * four groups, below).
+ *   operand  polynomial (g, j) starts (g * group_stride + j * term_stride) polynomials after ptr; group_stride 0 = shared by all
+ *            groups.  A plain dot: {A, terms, 1} against {B, terms, 1}; a matrix times a shared vector: b = {V, 0, 1}; a key laid
+ *            out [term][component]: b = {K + c, 0, 2}; one shared polynomial: both strides 0.
+ *   out      dense [groups][nmoduli][degree]
+ *   addend   NULL, or dense like out; it may be out itself (the same first byte): out += sum
+ *   flags    0, or NFLHIP_DOT_UNTILED.  When one operand is shared (group_stride 0) and groups > 1 a thread serves four consecutive
+ *            groups per load of the shared words; NFLHIP_DOT_UNTILED forces one group per pass -- each plan is the other's
+ *            cross-check, same words.
+ * The pointer form computes ONE output polynomial from terms <= NFLHIP_DOT_MAX_POINTERS polynomials anywhere in device memory:
+ * d_a / d_b are HOST arrays of device pointers, which travel to the kernel by value (longer sums chain through the addend).
+ * The _dev entries allocate nothing, use no scratch and do not synchronise: they can be captured into a hipGraph.
+ * The host variant takes a dense as [groups][terms] and b as [groups][terms], or as [terms] when b_shared is non-zero.
+ * NFLHIP_ERR_INVALID: a NULL context or pointer, terms == 0 or terms > 2^31 (terms > 16 in the pointer form), unknown flag bits, an output that
+ * overlaps any byte of an operand's extent -- the (groups - 1) * group_stride + (terms - 1) * term_stride + 1 polynomials from its
+ * ptr --, an addend that overlaps the output other than exactly, or a cyclic row context.  groups == 0 returns NFLHIP_OK and
+ * touches nothing.  Every argument is checked before the device is touched. */
+typedef struct nflhip_dot_operand {
+  const void *ptr;      /* device pointer to element (0,0) */
+  size_t group_stride;  /* polynomials from (g,j) to (g+1,j); 0 = shared by all groups */
+  size_t term_stride;   /* polynomials from (g,j) to (g,j+1) */
+} nflhip_dot_operand;
+#define NFLHIP_DOT_UNTILED 0x100
+#define NFLHIP_DOT_MAX_POINTERS 16
+int nflhip_dot_dev(nflhip_ctx *ctx, void *d_out, const nflhip_dot_operand *a, const nflhip_dot_operand *b, const void *d_addend,
+                   size_t groups, size_t terms, int flags, void *stream);
+int nflhip_dot_ptrs_dev(nflhip_ctx *ctx, void *d_out, const void *const *d_a, const void *const *d_b, size_t terms,
+                        const void *d_addend, void *stream);
+int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, size_t groups, size_t terms, int b_shared);   /* staged host variant */
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

@@ -22,6 +22,14 @@ FMT_WORDS, FMT_I8, FMT_I16, FMT_I32 = range(4)
 FORM_COEFF, FORM_NTT = 0, 1
 AUTOMORPHISM_MAX_OUTPUTS = 16
 RESCALE_COMPOSED, RESCALE_FUSED = 0x100, 0x200
+DOT_UNTILED = 0x100
+DOT_MAX_POINTERS = 16
+
+
+class DotOperand(C.Structure):
+    """nflhip_dot_operand: device pointer to polynomial (0, 0), strides in polynomials between groups (0 = shared) and terms"""
+    _fields_ = [("ptr", C.c_void_p), ("group_stride", C.c_size_t), ("term_stride", C.c_size_t)]
+
 
 # every symbol include/nflhip.h declares: (name, restype, argtypes)
 _vp, _sz, _i, _u64 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint64
@@ -48,6 +56,9 @@ SYMBOLS = [
     ("nflhip_automorphism_multi_dev", _i, [_vp, _vp, C.POINTER(_u64), _sz, _vp, _sz, _i, _vp]),
     ("nflhip_rescale_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_rescale", _i, [_vp, _vp, _vp, _sz, _i]),
+    ("nflhip_dot_dev", _i, [_vp, _vp, C.POINTER(DotOperand), C.POINTER(DotOperand), _vp, _sz, _sz, _i, _vp]),
+    ("nflhip_dot_ptrs_dev", _i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _sz, _vp, _vp]),
+    ("nflhip_dot", _i, [_vp, _vp, _vp, _vp, _sz, _sz, _i]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     ("nflhip_eval_dev", _i, [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp]),

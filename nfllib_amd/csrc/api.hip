@@ -388,7 +388,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -741,6 +741,46 @@ int nflhip_rescale_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t ba
     if (forced) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "rescale: two rows of this shape do not fit the one-launch kernel's LDS");
   }
   return rescale_composed(ctx, d_out, d_in, batch, st);
+}
+
+// Sums of products across polynomials (kernels_dot.hip).  A shared operand takes the tiled plan by default: it is read once per four
+// groups.  Measured against the untiled plan at 4 / 16 / 64 terms (profiles/r09_dot.txt): 7 % faster at 16, level
+// at 4 and 64, nowhere slower by more than two runs differ, so the rule has no threshold.
+static bool dot_tiled_on(const nflhip_dot_operand *a, const nflhip_dot_operand *b, size_t groups, int flags) {
+  return !(flags & NFLHIP_DOT_UNTILED) && groups > 1 && (a->group_stride == 0 || b->group_stride == 0);
+}
+int nflhip_dot_dev(nflhip_ctx *ctx, void *d_out, const nflhip_dot_operand *a, const nflhip_dot_operand *b, const void *d_addend,
+                   size_t groups, size_t terms, int flags, void *stream) {
+  int rc = dot_check(ctx, d_out, a, b, d_addend, groups, terms, flags);  // in full, before any device use
+  if (rc || groups == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const int tiled = dot_tiled_on(a, b, groups, flags);
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_dot<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *)a->ptr, a->group_stride, a->term_stride, (const T *)b->ptr,
+                         b->group_stride, b->term_stride, (const T *)d_addend, groups, terms, tiled, (hipStream_t)stream);
+  });
+  return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "dot");
+}
+int nflhip_dot_ptrs_dev(nflhip_ctx *ctx, void *d_out, const void *const *d_a, const void *const *d_b, size_t terms, const void *d_addend,
+                        void *stream) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "dot: not on a cyclic row context");
+  if (terms == 0 || terms > NFLHIP_DOT_MAX_POINTERS) return fail(ctx, NFLHIP_ERR_INVALID, "dot: the pointer form takes 1 to 16 terms");
+  if (!d_out || !d_a || !d_b) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t pb = poly_bytes(ctx, 1);
+  for (size_t j = 0; j < terms; ++j) {
+    if (!d_a[j] || !d_b[j]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+    if (bytes_overlap(d_out, d_a[j], pb) || bytes_overlap(d_out, d_b[j], pb)) return fail(ctx, NFLHIP_ERR_INVALID, "dot: the output overlaps an operand");
+  }
+  int rc = dot_check_out(ctx, d_out, pb, d_addend);
+  if (rc || (rc = set_device(ctx))) return rc;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_dot_ptrs<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *const *)d_a, (const T *const *)d_b, terms, (const T *)d_addend,
+                              (hipStream_t)stream);
+  });
+  return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "dot (pointer form)");
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

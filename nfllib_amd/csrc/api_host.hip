@@ -390,6 +390,28 @@ int nflhip_rescale(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch,
   });
 }
 
+// sums of products across polynomials: the operands are `terms` times the size of the result, so the call is staged whole
+int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, size_t groups, size_t terms, int b_shared) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "dot: not on a cyclic row context");
+  if (terms == 0 || terms > 0xffffffffu) return fail(ctx, NFLHIP_ERR_INVALID, "dot: the number of terms is out of range");
+  if (groups == 0) return NFLHIP_OK;
+  if (!h_out || !h_a || !h_b) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  size_t polys, abytes;
+  if (__builtin_mul_overflow(groups, terms, &polys) || __builtin_mul_overflow(polys, poly_bytes(ctx, 1), &abytes))
+    return fail(ctx, NFLHIP_ERR_INVALID, "dot: an operand's size overflows");
+  const size_t obytes = poly_bytes(ctx, groups), bbytes = b_shared ? poly_bytes(ctx, terms) : abytes;
+  if (ranges_overlap(h_out, obytes, h_a, abytes) || ranges_overlap(h_out, obytes, h_b, bbytes))
+    return fail(ctx, NFLHIP_ERR_INVALID, "dot: the output overlaps an operand");
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  const HostIn ins[] = {{0, h_a, abytes}, {1, h_b, bbytes}};
+  return staged_call(ctx, groups, false, ins, 2, {2, h_out, obytes}, [&](const void *const *d, void *o, size_t cnt, void *st) {
+    const nflhip_dot_operand a = {d[0], terms, 1}, b = {d[1], b_shared ? 0 : terms, 1};
+    return nflhip_dot_dev(ctx, o, &a, &b, nullptr, cnt, terms, 0, st);
+  });
+}
+
 int nflhip_ntt_row(nflhip_ctx *ctx, void *h_rows, size_t cm, int mode, size_t rows) {
   CHECK_CTX(ctx);
   if (rows == 0) return NFLHIP_OK;

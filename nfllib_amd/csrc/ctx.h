@@ -122,6 +122,39 @@ inline int rescale_check(const nflhip_ctx *ctx, const void *out, const void *in,
   if (x < y + ib && y < x + ob) return fail(ctx, NFLHIP_ERR_INVALID, host ? "the output overlaps the input" : "the output overlaps the input (the strides differ: never in place)");
   return NFLHIP_OK;
 }
+// nflhip_dot_dev / nflhip_dot_ptrs_dev: every argument check, before any device use.  An operand's extent is the
+// (groups - 1) group_stride + (terms - 1) term_stride + 1 polynomials from its ptr; the output may overlap no byte of it, and the
+// addend is the output itself or apart from it.
+inline bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bbytes && y < x + abytes;
+}
+inline int dot_check_out(const nflhip_ctx *ctx, const void *out, size_t obytes, const void *addend) {
+  if (addend && addend != out && ranges_overlap(out, obytes, addend, obytes))
+    return fail(ctx, NFLHIP_ERR_INVALID, "dot: the addend overlaps the output without being the output");
+  return NFLHIP_OK;
+}
+inline int dot_check(const nflhip_ctx *ctx, const void *out, const nflhip_dot_operand *a, const nflhip_dot_operand *b, const void *addend,
+                     size_t groups, size_t terms, int flags) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "dot: not on a cyclic row context");
+  if (flags & ~NFLHIP_DOT_UNTILED) return fail(ctx, NFLHIP_ERR_INVALID, "dot: unknown flag bits");
+  if (terms == 0 || terms > nflhip::kDotMaxTerms) return fail(ctx, NFLHIP_ERR_INVALID, "dot: the number of terms is out of range (1 to 2^31)");
+  if (!a || !b) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  if (groups == 0) return NFLHIP_OK;
+  if (!out || !a->ptr || !b->ptr) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t pb = poly_bytes(ctx, 1);
+  size_t obytes;
+  if (__builtin_mul_overflow(groups, pb, &obytes)) return fail(ctx, NFLHIP_ERR_INVALID, "dot: the output size overflows");
+  for (const nflhip_dot_operand *x : {a, b}) {
+    size_t g, t, polys, bytes;
+    if (__builtin_mul_overflow(groups - 1, x->group_stride, &g) || __builtin_mul_overflow(terms - 1, x->term_stride, &t) ||
+        __builtin_add_overflow(g, t, &polys) || __builtin_add_overflow(polys, (size_t)1, &polys) || __builtin_mul_overflow(polys, pb, &bytes))
+      return fail(ctx, NFLHIP_ERR_INVALID, "dot: an operand's extent overflows");
+    if (ranges_overlap(out, obytes, x->ptr, bytes)) return fail(ctx, NFLHIP_ERR_INVALID, "dot: the output overlaps an operand");
+  }
+  return dot_check_out(ctx, out, obytes, addend);
+}
 constexpr size_t kStageHostMax = (size_t)1 << 20;
 inline void free_stage(nflhip_ctx *ctx, int slot) {
   if (ctx->stage[slot]) (void)(ctx->stage_host[slot] ? hipHostFree(ctx->stage[slot]) : hipFree(ctx->stage[slot]));

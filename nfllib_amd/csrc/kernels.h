@@ -95,6 +95,19 @@ template <typename T>
 hipError_t launch_rescale_expand(const Shape &s, const DevTables &t, T *out, const T *dropped, size_t batch, hipStream_t st);
 template <typename T>
 hipError_t launch_rescale_combine(const Shape &s, const DevTables &t, T *out, const T *in, size_t batch, hipStream_t st);
+// sums of products across polynomials (kernels_dot.hip; include/nflhip.h "sums of products"): out[g] = addend[g] + sum_j a(g,j) b(g,j),
+// a(g,j) the polynomial at a + (g a_gs + j a_ts) polynomials (b alike), out and addend dense [groups][nm][n], addend nullptr or
+// possibly out itself; out must not overlap a or b (api.hip checks).  tiled: when one operand is shared by all groups (group
+// stride 0) and groups > 1, a thread serves 4 groups per load of the shared words.  _ptrs: one group, terms <= kDotMaxPointers
+// HOST arrays of device pointers, which travel in the kernel arguments.
+constexpr int kDotMaxPointers = 16;
+constexpr size_t kDotMaxTerms = (size_t)1 << 31;  // the kernel counts terms in 32 bits, a few ahead: j + 4 must not wrap
+template <typename T>
+hipError_t launch_dot(const Shape &s, const DevTables &t, T *out, const T *a, size_t a_gs, size_t a_ts, const T *b, size_t b_gs, size_t b_ts,
+                      const T *addend, size_t groups, size_t terms, int tiled, hipStream_t st);
+template <typename T>
+hipError_t launch_dot_ptrs(const Shape &s, const DevTables &t, T *out, const T *const *a, const T *const *b, size_t terms, const T *addend,
+                           hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);
@@ -242,6 +255,7 @@ hipError_t warm_sample(hipStream_t st);
 hipError_t warm_wave(hipStream_t st);
 hipError_t warm_automorph(hipStream_t st);
 hipError_t warm_rescale(hipStream_t st);
+hipError_t warm_dot(hipStream_t st);
 int polymul_level();   // 0 / 1 / 2: transforms of the coefficient-form products complete / incomplete (kernels_fast.hip, nflhip_debug_polymul_level)
 hipError_t launch_polymul_pipe64k_u64(const Shape &s, const DevTables &t, uint64_t *c_v, const uint64_t *a_v,
                                       const uint64_t *b_v, int cnt_v, const uint64_t *fa_src, uint64_t *fa_dst,

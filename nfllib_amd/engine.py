@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
+from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -180,6 +180,58 @@ class Engine:
         batch = self._hb(a)
         out = np.empty((batch, self.nmoduli - 1, self.degree), dtype=self.np_dtype)
         self._chk(self.lib.nflhip_rescale(self.ctx, _vp(out), _vp(a), batch, FORM_NTT if ntt else FORM_COEFF))
+        return out
+
+    # ---- sums of products across polynomials (include/nflhip.h "sums of products") ----
+    def dot_strided(self, a, a_strides, b, b_strides, groups, terms, addend=None, out=None, untiled=False, stream=None):
+        """out[g] = addend[g] + sum_j a(g, j) * b(g, j): polynomial (g, j) of an operand starts g * strides[0] + j * strides[1]
+        polynomials after its first word (strides[0] == 0: shared by all groups); a / b are tensors (views allowed) or device
+        addresses; addend may be `out` itself; untiled=True forces one group per pass where an operand is shared"""
+        if out is None:
+            out = self.empty(groups)
+        oa = _lib.DotOperand(a if isinstance(a, int) else a.data_ptr(), a_strides[0], a_strides[1])
+        ob = _lib.DotOperand(b if isinstance(b, int) else b.data_ptr(), b_strides[0], b_strides[1])
+        self._chk(self.lib.nflhip_dot_dev(self.ctx, _vp(out), C.byref(oa), C.byref(ob), _vp(addend), groups, terms,
+                                          DOT_UNTILED if untiled else 0, self._stream(stream)))
+        return out
+
+    def dot(self, a, b, terms, addend=None, out=None, untiled=False, stream=None):
+        """a and b dense with groups * terms polynomials: out[g] = addend[g] + sum_j a[g * terms + j] * b[g * terms + j]"""
+        batch = self._batch(a)
+        if terms <= 0 or batch % terms or self._batch(b) != batch:
+            raise ValueError("a and b hold groups * terms polynomials each")
+        return self.dot_strided(a, (terms, 1), b, (terms, 1), batch // terms, terms, addend, out, untiled, stream)
+
+    def matvec(self, m, v, addend=None, out=None, untiled=False, stream=None):
+        """matrix times shared vector: v holds `terms` polynomials, m groups * terms: out[g] = addend[g] + sum_j m[g, j] * v[j]"""
+        terms, batch = self._batch(v), self._batch(m)
+        if terms == 0 or batch % terms:
+            raise ValueError("m holds groups * terms polynomials, v terms")
+        return self.dot_strided(m, (terms, 1), v, (0, 1), batch // terms, terms, addend, out, untiled, stream)
+
+    def dot_list(self, as_, bs, addend=None, out=None, stream=None):
+        """one polynomial: addend + sum_j as_[j] * bs[j] over lists of one-polynomial tensors anywhere in device memory; the
+        pointers travel by value, 16 per launch, longer lists chain through the addend"""
+        if len(as_) != len(bs) or not as_:
+            raise ValueError("two lists of one length, at least one term")
+        if out is None:
+            out = self.empty(1)
+        for k in range(0, len(as_), DOT_MAX_POINTERS):
+            xa, xb = as_[k:k + DOT_MAX_POINTERS], bs[k:k + DOT_MAX_POINTERS]
+            pa = (C.c_void_p * len(xa))(*[x.data_ptr() for x in xa])
+            pb = (C.c_void_p * len(xb))(*[x.data_ptr() for x in xb])
+            self._chk(self.lib.nflhip_dot_ptrs_dev(self.ctx, _vp(out), pa, pb, len(xa), _vp(addend if k == 0 else out),
+                                                   self._stream(stream)))
+        return out
+
+    def h_dot(self, a, b, terms, b_shared=False):
+        """host-pointer variant: numpy a = [groups * terms, nm, n], b alike or [terms, nm, n] with b_shared; -> [groups, nm, n]"""
+        a, b = np.ascontiguousarray(a, dtype=self.np_dtype), np.ascontiguousarray(b, dtype=self.np_dtype)
+        if terms <= 0 or self._hb(a) % terms or self._hb(b) != (terms if b_shared else self._hb(a)):
+            raise ValueError("a holds groups * terms polynomials, b as many, or terms with b_shared")
+        groups = self._hb(a) // terms
+        out = np.empty((groups, self.nmoduli, self.degree), dtype=self.np_dtype)
+        self._chk(self.lib.nflhip_dot(self.ctx, _vp(out), _vp(a), _vp(b), groups, terms, int(bool(b_shared))))
         return out
 
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
