@@ -128,7 +128,7 @@ static int ensure_scratch(nflhip_ctx *ctx, size_t bytes) {
 static constexpr int kPipeChunks = NFLHIP_PIPE_CHUNKS;
 
 
-// Rows of 65536 / 32768 words in ONE launch of persistent workgroups (kernels_fast.hip launch_polymul_xcd_u64) instead
+// Rows of 65536 / 32768 words in ONE launch of persistent workgroups (asm_launch.hip launch_polymul_xcd_u64) instead
 // of the chunked pipeline / the register-resident row kernels: by default for SMALL batches, where the other plans'
 // fill and drain launches (n = 65536) or the one-workgroup-per-row grid (n = 32768) leave CUs idle.  Measured (MI355X):
 // n = 65536 / 30 moduli +5 % at batch 4, +11 % at 8, +-0 at 16, -2 % at 64; n = 32768 / 2 moduli against the row
@@ -190,7 +190,7 @@ static int polymul_composed(nflhip_ctx *ctx, T *c, const T *a, const T *b, int b
   }
   if (sizeof(T) == 8 && !b_is_ntt && xcd_on(ctx, batch)) {
     // rows of 65536 / 32768 words: ONE launch of persistent workgroups, every row's three roles on one XCD and the
-    // intermediates through that XCD's L2 (kernels_fast.hip launch_polymul_xcd_u64); needs only a ring of row slots
+    // intermediates through that XCD's L2 (asm_launch.hip launch_polymul_xcd_u64); needs only a ring of row slots
     const size_t need = xcd_plan_bytes(ctx->shape, batch);
     if (need) {
       int rcx = ensure_scratch(ctx, need);

@@ -256,7 +256,7 @@ hipError_t warm_wave(hipStream_t st);
 hipError_t warm_automorph(hipStream_t st);
 hipError_t warm_rescale(hipStream_t st);
 hipError_t warm_dot(hipStream_t st);
-int polymul_level();   // 0 / 1 / 2: transforms of the coefficient-form products complete / incomplete (kernels_fast.hip, nflhip_debug_polymul_level)
+int polymul_level();   // 0 / 1 / 2: transforms of the coefficient-form products complete / incomplete (asm_launch.hip, nflhip_debug_polymul_level)
 hipError_t launch_polymul_pipe64k_u64(const Shape &s, const DevTables &t, uint64_t *c_v, const uint64_t *a_v,
                                       const uint64_t *b_v, int cnt_v, const uint64_t *fa_src, uint64_t *fa_dst,
                                       const uint64_t *fb_src, uint64_t *fb_dst, int cnt_f, uint64_t *inv, int cnt_i,

@@ -136,23 +136,60 @@ def test_product_path_never_touches_the_test_doubles():
     assert not bad, bad
 
 
+_CSRC = os.path.join(ROOT, "nfllib_amd", "csrc")
+_DEF_ENTRY = re.compile(r'X\((kAsm[A-Za-z0-9]+), "(nflhip_[a-z0-9_]+_asm)", (\d*), (\d*), (\d*)\)(?:\s*//.*)?')
+
+
+def _generated_kernels():
+    """asm_kernels.def: [(kind, name, row, level, whole)], every line that is not blank or a comment parsed as exactly one entry"""
+    rows = []
+    for no, line in enumerate(open(os.path.join(_CSRC, "asm_kernels.def")), 1):
+        line = line.strip()
+        if not line or line.startswith("//"):
+            continue
+        m = _DEF_ENTRY.fullmatch(line)
+        assert m, "asm_kernels.def:%d is not one X(kind, \"name\", row, level, whole) entry: %r" % (no, line)
+        rows.append(m.groups())
+    return rows
+
+
+def test_the_table_of_generated_kernels_is_the_only_one():
+    """enum AsmKind and the kernels' symbol names are both expanded from asm_kernels.def, so a kind cannot be paired with
+    another kernel's name (and kernarg layout): every kind once, every name once, the standard-argument columns all set or all
+    empty, and no second list of either anywhere else in the library's sources"""
+    rows = _generated_kernels()
+    kinds, names = [r[0] for r in rows], [r[1] for r in rows]
+    assert len(rows) >= 30
+    assert len(set(kinds)) == len(kinds), sorted(k for k in set(kinds) if kinds.count(k) > 1)
+    assert len(set(names)) == len(names), sorted(n for n in set(names) if names.count(n) > 1)
+    for kind, _, row, level, whole in rows:
+        if row == "":
+            assert level == "" and whole == "", kind
+        else:
+            assert 12 <= int(row) <= 15 and level in ("0", "1", "2") and whole in ("0", "1"), kind
+    for f in sorted(os.listdir(_CSRC)):
+        if not f.endswith((".hip", ".cpp", ".h", ".def")) or f == "asm_kernels.def":
+            continue
+        txt = open(os.path.join(_CSRC, f)).read()
+        assert not re.findall(r'"nflhip_[a-z0-9_]+_asm"', txt), f
+        code = re.sub(r"//[^\n]*", "", txt)
+        # the one enum that lists kinds is the expansion of the table (asm_launch.h); nothing defines a kAsm... constant by hand
+        for body in re.findall(r"\benum\b[^;{]*\{([^}]*)\}", code):
+            if "kAsm" in body or "asm_kernels.def" in body:
+                assert f == "asm_launch.h", f
+                assert re.sub(r"^\s*#.*$", "", body, flags=re.M).split() == ["kAsmCount"], body
+        assert not re.findall(r"\bkAsm[A-Za-z0-9]+\s*=[^=]|#\s*define\s+kAsm", code), f
+        used = set(re.findall(r"\bkAsm[A-Z][A-Za-z0-9]*\b", code)) - {"kAsmCount", "kAsmInfo"}
+        assert used <= set(kinds), (f, sorted(used - set(kinds)))
+
+
 def test_every_generated_kernel_the_launchers_name_is_in_the_code_object():
-    """kernels_fast.hip looks the generated assembly kernels up BY NAME in the embedded code object and treats a miss as
+    """asm_launch.hip looks the generated assembly kernels up BY NAME in the embedded code object and treats a miss as
     "not supported" (the compiled kernels then serve the call): a typo would silently cost the tuned path.  Every name in
-    kAsmNames must be a kernel symbol of the code object the Makefile links, and every kernel in it must be named."""
-    import re
+    asm_kernels.def must be a kernel symbol of the code object the Makefile links, and every kernel in it must be named."""
     import subprocess
-    csrc = os.path.join(ROOT, "nfllib_amd", "csrc")
-    src = open(os.path.join(csrc, "kernels_fast.hip")).read()
-    block = src[src.index("kAsmNames[kAsmCount] = {"):]
-    block = block[:block.index("};")]
-    names = re.findall(r'"(nflhip_[a-z0-9_]+_asm)"', block)
-    assert len(names) >= 30 and len(set(names)) == len(names)
-    enum = src[src.index("enum AsmKind {"):]
-    enum = enum[:enum.index("kAsmCount")]
-    kinds = re.findall(r"\bkAsm[A-Za-z0-9]+\b", re.sub(r"//[^\n]*", "", enum))
-    assert len(kinds) == len(names), "enum AsmKind and kAsmNames must list the same kernels in the same order"
-    hsaco = os.path.join(csrc, "polymul4096_gfx950.hsaco")
+    names = [r[1] for r in _generated_kernels()]
+    hsaco = os.path.join(_CSRC, "polymul4096_gfx950.hsaco")
     if not os.path.exists(hsaco):
         pytest.skip("code object not built here")
     tool = "/opt/rocm/lib/llvm/bin/llvm-readelf"

@@ -1,4 +1,4 @@
-"""Rows of 32768 / 65536 words in ONE launch of persistent workgroups (csrc/kernels_fast.hip launch_polymul_xcd_u64,
+"""Rows of 32768 / 65536 words in ONE launch of persistent workgroups (csrc/asm_launch.hip launch_polymul_xcd_u64,
 tools/gen_polymul_asm.py fused_header): every row's three roles run on one XCD, handed out by per-domain credit /
 ticket counters.  Checked here: the words are those of the chunked pipeline (which test_gpu_parity.py holds against
 the oracle) and of the oracle itself on a sample row, for batches whose row counts are not multiples of anything, in

@@ -247,7 +247,7 @@ def test_generators_that_die_early_key_changes_and_failing_launches(mock, tmp_pa
 
 
 def test_pipeline_xcd_remap_is_a_bijection_and_its_one_multiply_division_is_exact():
-    """n = 65536 pipeline kernel (tools/gen_polymul_asm.py build_pipe, kernels_fast.hip launch_polymul_pipe64k_u64): the workgroup
+    """n = 65536 pipeline kernel (tools/gen_polymul_asm.py build_pipe, asm_launch.hip launch_polymul_pipe64k_u64): the workgroup
     with linear index L = wgx + gx * cm takes unit u = (L mod 8) * U/8 + L div 8 of the modulus-major order and recovers
     (cm, wgx) = (u div gx, u mod gx) with ONE 32-bit multiply-high by ceil(2^32 / gx).  The launcher switches the remap on
     only if U = gx * nm is a multiple of 8 and U * gx < 2^32: under exactly that condition the division must be exact and the
