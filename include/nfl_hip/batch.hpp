@@ -163,6 +163,20 @@ template <class P> class device_batch {
     const nflhip_dot_operand x = {m.d_, v.n_, 1}, y = {v.d_, 0, 1};
     detail::check(ctx(), nflhip_dot_dev(ctx(), d_, &x, &y, nullptr, n_, v.n_, 0, queue()), "matvec");
   }
+  // Gadget decomposition (include/nflhip.h): this batch holds src.size() * terms polynomials, terms = nmoduli * ceil(modulus
+  // bits / w): (*this)[b * terms + m * l + t] = digit t of row m of the coefficient-form src[b], spread over every row.  flags =
+  // NFLHIP_FORM_COEFF or NFLHIP_FORM_NTT, | NFLHIP_DECOMP_SIGNED, | a plan flag.  assign_gadget_mul: the key-generation
+  // companion, src[b] * 2^(w t) in row m of the same term, zero elsewhere.  src must be another batch.
+  void assign_decompose(const device_batch &src, int w, int flags = NFLHIP_FORM_COEFF) {
+    decompose_sizes(src, w);
+    src.strict("decompose");
+    detail::check(ctx(), nflhip_decompose_dev(ctx(), d_, NFLHIP_FMT_WORDS, src.d_, src.n_, w, flags, queue()), "decompose");
+  }
+  void assign_gadget_mul(const device_batch &src, int w) {
+    decompose_sizes(src, w);
+    src.strict("gadget_mul");
+    detail::check(ctx(), nflhip_gadget_mul_dev(ctx(), d_, src.d_, src.n_, w, queue()), "gadget_mul");
+  }
   // CRT lift / project of the whole resident batch (gmp.hpp:183-219): out[(b*degree + i)*L .. +L) = little-endian limbs
   // of X_{b,i} in [0, Q), L = P::crt_limbs(); limbs2poly takes L_in limbs per coefficient
   void poly2limbs(std::vector<uint64_t> &out) const {
@@ -284,6 +298,12 @@ template <class P> class device_batch {
   void same_size(const device_batch &o) const {
     if (o.n_ != n_) throw std::runtime_error("nfl(hip): batch size mismatch");
     if (o.c_ != c_) throw std::runtime_error("nfl(hip): the batches of one operation must live on one device");
+  }
+  void decompose_sizes(const device_batch &src, int w) const {
+    same_device(src);
+    const size_t terms = nflhip_decompose_terms(ctx(), w);
+    if (terms == 0) throw std::runtime_error("nfl(hip): the digit width is out of range");
+    if (n_ != src.n_ * terms) throw std::runtime_error("nfl(hip): a decomposition holds src.size() * terms polynomials");
   }
   void same_device(const device_batch &o) const {
     if (o.c_ != c_) throw std::runtime_error("nfl(hip): the batches of one operation must live on one device");

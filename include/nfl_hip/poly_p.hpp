@@ -293,6 +293,41 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out._p = dst;
   }
 
+  // Gadget decomposition (nfl::decompose / nfl::decompose_ntt / nfl::gadget_mul below): the deferred queue of this ring type
+  // runs first (on the caller), then ONE launch on the queue's stream writes the dense [terms] block the entry produces into a
+  // device buffer of the call, and `terms` device copies hand its polynomials to fresh payloads -- so `in` may be an element of
+  // `out` and copy-on-write sharers of out's old values keep them.  The call returns once the stream has drained (the buffer
+  // is freed).  flags < 0: gadget_mul.  Never fused into the queue's rewrites.
+  static void decompose_into(poly_p *out, poly_p const &in, int w, int flags) {
+    const size_t terms = nflhip_decompose_terms(ctx_t::get(), w);
+    const char *what = flags < 0 ? "gadget_mul" : "decompose";
+    if (terms == 0) throw std::runtime_error(std::string("nfl(hip): ") + what + ": the digit width is out of range");
+    lazy_t::inst().flush();
+    ptr_type src = in._p;  // (holds the input while the launch is enqueued)
+    const void *s = src->dev_ro();
+    const size_t one = sizeof(T) * Degree * NbModuli;
+    void *block = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &block, terms * one), what);
+    int rc = flags < 0 ? nflhip_gadget_mul_dev(ctx_t::get(), block, s, 1, w, ctx_t::queue())
+                       : nflhip_decompose_dev(ctx_t::get(), block, NFLHIP_FMT_WORDS, s, 1, w, flags, ctx_t::queue());
+    std::vector<ptr_type> dst(rc ? 0 : terms);
+    try {
+      for (size_t j = 0; j < dst.size() && rc == 0; ++j) {
+        dst[j] = fresh();
+        rc = nflhip_memcpy_d2d(ctx_t::get(), dst[j]->dev_wo(), static_cast<const char *>(block) + j * one, one, ctx_t::queue());
+      }
+      if (rc == 0) rc = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());
+    } catch (...) {
+      nflhip_stream_sync(ctx_t::get(), ctx_t::queue());
+      nflhip_free(ctx_t::get(), block);
+      throw;
+    }
+    if (rc) nflhip_stream_sync(ctx_t::get(), ctx_t::queue());
+    nflhip_free(ctx_t::get(), block);
+    detail::check(ctx_t::get(), rc, what);
+    for (size_t j = 0; j < terms; ++j) out[j]._p = dst[j];
+  }
+
   /* ntt stuff - public API (poly_p.hpp:141-142): in place in HBM */
   void ntt_pow_phi() { transform(lazy_t::K_NTT_FWD); }
   void invntt_pow_invphi() { transform(lazy_t::K_NTT_INV); }
@@ -438,6 +473,61 @@ template <class T, size_t D, size_t M> void dot(poly_p<T, D, M> &out, poly_p<T, 
 template <class T, size_t D, size_t M> void dot_add(poly_p<T, D, M> &out, poly_p<T, D, M> const *a, poly_p<T, D, M> const *b, size_t terms) {
   poly_p<T, D, M>::dot_into(out, a, b, terms, true);
 }
+
+/* Gadget decomposition (include/nflhip.h): the base-2^w digits of every row of a COEFFICIENT-form polynomial.  `out` is an array of
+ * gadget_terms<P>(w) = nmoduli * ceil(modulus bits / w) polynomials of the same ring type: out[m * l + t] holds digit t of row m,
+ * spread over every row (balanced digits in [-B/2, B/2] with signed_digits).  decompose_ntt leaves the digit polynomials in the
+ * order ntt_pow_phi() produces.  gadget_mul is the key-generation companion: out[m * l + t] = in * 2^(w t) in row m, zero in the
+ * other rows, so that  sum_j decompose(x)[j] * gadget_mul(y)[j] = x * y  in every row (nfl::dot over NTT-form operands).
+ * `in` may be an element of `out`.  On poly the call goes through the staged host entry (gadget_mul: a device buffer of the
+ * call); on poly_p it runs on the resident value. */
+template <class P> inline size_t gadget_terms(int w) {
+  const int bits = int(8 * sizeof(typename P::value_type)) - 2;
+  return w < 1 || w > bits - 1 ? 0 : P::nmoduli * size_t((bits + w - 1) / w);
+}
+namespace detail {
+template <class T, size_t D, size_t M> void decompose_host(poly<T, D, M> *out, poly<T, D, M> const &in, int w, int flags) {
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  const size_t terms = gadget_terms<P>(w);
+  const char *what = flags < 0 ? "gadget_mul" : "decompose";
+  if (terms == 0) throw std::runtime_error(std::string("nfl(hip): ") + what + ": the digit width is out of range");
+  P *tmp = P::make_temp();  // (in may be an element of out)
+  std::memcpy(static_cast<void *>(tmp->data()), in.cdata(), sizeof(P));
+  int rc;
+  if (flags >= 0) {
+    rc = nflhip_decompose(P::ctx(), out->data(), NFLHIP_FMT_WORDS, tmp->cdata(), 1, w, flags);
+  } else {  // no staged entry: a device buffer of the call, on the null stream
+    void *d = nullptr;
+    rc = nflhip_malloc(P::ctx(), &d, (terms + 1) * sizeof(P));
+    if (rc == 0) {
+      void *o = static_cast<char *>(d) + sizeof(P);
+      rc = nflhip_memcpy_h2d(P::ctx(), d, tmp->cdata(), sizeof(P), nullptr);
+      if (rc == 0) rc = nflhip_gadget_mul_dev(P::ctx(), o, d, 1, w, nullptr);
+      if (rc == 0) rc = nflhip_memcpy_d2h(P::ctx(), out->data(), o, terms * sizeof(P), nullptr);
+      const int rs = nflhip_stream_sync(P::ctx(), nullptr);
+      if (rc == 0) rc = rs;
+      nflhip_free(P::ctx(), d);
+    }
+  }
+  P::drop_temp(tmp);
+  check(P::ctx(), rc, what);
+}
+}  // namespace detail
+template <class T, size_t D, size_t M> void decompose(poly<T, D, M> *out, poly<T, D, M> const &in, int w, bool signed_digits = false) {
+  detail::decompose_host(out, in, w, NFLHIP_FORM_COEFF | (signed_digits ? NFLHIP_DECOMP_SIGNED : 0));
+}
+template <class T, size_t D, size_t M> void decompose_ntt(poly<T, D, M> *out, poly<T, D, M> const &in, int w, bool signed_digits = false) {
+  detail::decompose_host(out, in, w, NFLHIP_FORM_NTT | (signed_digits ? NFLHIP_DECOMP_SIGNED : 0));
+}
+template <class T, size_t D, size_t M> void gadget_mul(poly<T, D, M> *out, poly<T, D, M> const &in, int w) { detail::decompose_host(out, in, w, -1); }
+template <class T, size_t D, size_t M> void decompose(poly_p<T, D, M> *out, poly_p<T, D, M> const &in, int w, bool signed_digits = false) {
+  poly_p<T, D, M>::decompose_into(out, in, w, NFLHIP_FORM_COEFF | (signed_digits ? NFLHIP_DECOMP_SIGNED : 0));
+}
+template <class T, size_t D, size_t M> void decompose_ntt(poly_p<T, D, M> *out, poly_p<T, D, M> const &in, int w, bool signed_digits = false) {
+  poly_p<T, D, M>::decompose_into(out, in, w, NFLHIP_FORM_NTT | (signed_digits ? NFLHIP_DECOMP_SIGNED : 0));
+}
+template <class T, size_t D, size_t M> void gadget_mul(poly_p<T, D, M> *out, poly_p<T, D, M> const &in, int w) { poly_p<T, D, M>::decompose_into(out, in, w, -1); }
 
 /* high level wrappers (poly.hpp:314-332) */
 template <class T, size_t D, size_t M> void sub(poly<T, D, M> &out, poly<T, D, M> const &a, poly<T, D, M> const &b) { out = a - b; }

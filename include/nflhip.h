@@ -224,6 +224,48 @@ int nflhip_dot_ptrs_dev(nflhip_ctx *ctx, void *d_out, const void *const *d_a, co
                         const void *d_addend, void *stream);
 int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, size_t groups, size_t terms, int b_shared);   /* staged host variant */
 
+/* ---- gadget decomposition: base-2^w digits of RNS rows ---------------------------------------
+ * The first step of every key switch (relinearisation, a rotation's Galois key, an XPIR / SealPIR reply): a coefficient-form
+ * polynomial is split into small "digit" polynomials whose sum of products against a key is what nflhip_dot_dev computes.
+ * Context with nm = nmoduli moduli of `bits` = limb_bits - 2 bits (2^(bits-1) < p < 2^bits); digit width w, B = 2^w,
+ * l = ceil(bits / w) digits per word, terms = nm * l (nflhip_decompose_terms).  Term j = m * l + t is digit t of row m.  For the
+ * canonical word x = in[b][m][i]:
+ *   unsigned (default)     d_t = (x >> w t) & (B - 1)
+ *   NFLHIP_DECOMP_SIGNED   c = x if x <= (p_m - 1) / 2 else x - p_m;  r_0 = c;  for t < l - 1: d_t = ((r_t + B/2) mod B) - B/2 in
+ *                          [-B/2, B/2), r_(t+1) = (r_t - d_t) / B;  the top digit d_(l-1) = r_(l-1) takes the carry and is not
+ *                          reduced: |d_(l-1)| <= B/2 (derived in nfllib_amd/csrc/kernels_decompose.hip)
+ * so that sum_t d_t B^t = x (unsigned) or c (signed), congruent to x mod p_m; B^t = 2^(w t) < p_m is its own residue.
+ *   input    [batch][nmoduli][degree] canonical words, always in COEFFICIENT form
+ *   output   NFLHIP_FMT_WORDS            dense [batch][terms][nmoduli][degree]: word (b, j, m', i) = d if d >= 0 else p_m' + d -- the
+ *                                        digit spread over every row as nflhip_expand_small_dev spreads a compact value; what
+ *                                        nflhip_dot_dev reads with {D, terms, 1}.  1 <= w <= bits - 1.
+ *            NFLHIP_FMT_I8 / I16 / I32   dense [batch][terms][degree], one signed integer per coefficient (the compact format of
+ *                                        nflhip_operand); additionally w <= 7 / 15 / 31, which holds the signed top digit +B/2 too
+ *   flags    NFLHIP_FORM_COEFF or NFLHIP_FORM_NTT, | NFLHIP_DECOMP_SIGNED, | one plan flag (NTT form only).
+ *            NFLHIP_FORM_NTT (words output only): each of the batch * terms digit polynomials is forward-transformed -- word for
+ *            word what nflhip_ntt_fwd_dev makes of the coefficient-form output.  Rows of up to 2048 words run in ONE launch (a workgroup
+ *            per digit polynomial, one row in LDS, 1x the output of traffic); longer rows, and contexts created under
+ *            NFLHIP_VARIANT=hipcc, write the digits and run the context's forward transform over them in place.
+ *            NFLHIP_DECOMP_COMPOSED selects the latter whatever the shape, NFLHIP_DECOMP_FUSED the one-launch kernel (rows up to
+ *            32 KiB, NFLHIP_ERR_UNSUPPORTED beyond): each is the other's cross-check, same words.
+ * nflhip_gadget_mul_dev is the key-generation companion: out[b][j = (m, t)][m'][i] = in[b][m][i] 2^(w t) mod p_m for m' = m, 0
+ * elsewhere; dense [batch][terms][nmoduli][degree].  A row-wise scalar: it does not look at the form of its input.  Per row m' of the
+ * ring product sum_j D_j(x) G_j(y) = sum_t d_t B^t y = x y, so
+ *     ntt_inv(dot(decompose(x, NTT), ntt_fwd(gadget_mul(y)), terms)) == polymul(x, y)     bit for bit.
+ * nflhip_decompose_terms returns 0 for an invalid w or context.  NFLHIP_ERR_INVALID: a NULL context or pointer, w outside the limits
+ * above, an unknown format or flag bit, the NTT form with a compact format, a plan flag without the NTT form or both plan flags, an
+ * output that overlaps the input, a size that overflows size_t, more than 65535 terms, or a cyclic row context; every argument is
+ * checked before the device is touched.  batch == 0 returns NFLHIP_OK and touches nothing.  The _dev entries allocate nothing and do
+ * not synchronise: they can be captured into a hipGraph wherever nflhip_ntt_fwd_dev can; the coefficient form and the one-launch
+ * kernel always can. */
+#define NFLHIP_DECOMP_COMPOSED 0x100
+#define NFLHIP_DECOMP_FUSED 0x200
+#define NFLHIP_DECOMP_SIGNED 0x400
+size_t nflhip_decompose_terms(const nflhip_ctx *ctx, int w);       /* nmoduli * ceil(bits / w); 0 for an invalid w or ctx */
+int nflhip_decompose_dev(nflhip_ctx *ctx, void *d_out, int out_format, const void *d_in, size_t batch, int w, int flags, void *stream);
+int nflhip_decompose(nflhip_ctx *ctx, void *h_out, int out_format, const void *h_in, size_t batch, int w, int flags);  /* staged host variant */
+int nflhip_gadget_mul_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, int w, void *stream);
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

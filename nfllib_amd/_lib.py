@@ -24,6 +24,7 @@ AUTOMORPHISM_MAX_OUTPUTS = 16
 RESCALE_COMPOSED, RESCALE_FUSED = 0x100, 0x200
 DOT_UNTILED = 0x100
 DOT_MAX_POINTERS = 16
+DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED = 0x100, 0x200, 0x400
 
 
 class DotOperand(C.Structure):
@@ -59,6 +60,10 @@ SYMBOLS = [
     ("nflhip_dot_dev", _i, [_vp, _vp, C.POINTER(DotOperand), C.POINTER(DotOperand), _vp, _sz, _sz, _i, _vp]),
     ("nflhip_dot_ptrs_dev", _i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _sz, _vp, _vp]),
     ("nflhip_dot", _i, [_vp, _vp, _vp, _vp, _sz, _sz, _i]),
+    ("nflhip_decompose_terms", _sz, [_vp, _i]),
+    ("nflhip_decompose_dev", _i, [_vp, _vp, _i, _vp, _sz, _i, _i, _vp]),
+    ("nflhip_decompose", _i, [_vp, _vp, _i, _vp, _sz, _i, _i]),
+    ("nflhip_gadget_mul_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),
     ("nflhip_eval_dev", _i, [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _vp]),

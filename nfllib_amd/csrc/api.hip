@@ -388,7 +388,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -781,6 +781,61 @@ int nflhip_dot_ptrs_dev(nflhip_ctx *ctx, void *d_out, const void *const *d_a, co
                               (hipStream_t)stream);
   });
   return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "dot (pointer form)");
+}
+
+// Gadget decomposition (kernels_decompose.hip).  The coefficient form is one streaming pass.  The NTT form has two plans with the
+// same words: composed -- the streaming pass into the output, then the context's own forward launcher in place over batch * terms
+// polynomials (every shape, the compiled kernels under NFLHIP_VARIANT=hipcc, no scratch of its own) -- and the one-launch kernel
+// (rows up to 32 KiB).  Default: the one-launch kernel for rows of up to 2048 words.  Measured against the composed plan in one run
+// (profiles/r11_decompose.txt), composed / fused: x1.17 at u64/1024/2, x1.08 at u64/2048/2, x1.02 at u32/1024/2, but
+// x0.70 at u64/4096/4 and x0.62 at u32/4096/3 -- at 4096 words the generated register-tiled transforms of the composed plan outrun
+// the radix-4 LDS transform by more than the two extra passes over the output cost, for 16 KiB and 32 KiB rows alike, so the rule
+// is in words, not bytes.
+static bool decompose_fused_on(const nflhip_ctx *ctx) {
+  return !ctx->shape.compiled_only && ctx->shape.n <= 2048;
+}
+size_t nflhip_decompose_terms(const nflhip_ctx *ctx, int w) { return decompose_terms(ctx, w); }
+int nflhip_decompose_dev(nflhip_ctx *ctx, void *d_out, int out_format, const void *d_in, size_t batch, int w, int flags, void *stream) {
+  if (out_format < 0) return fail(ctx, NFLHIP_ERR_INVALID, "decompose: unknown output format");
+  int rc = decompose_check(ctx, d_out, out_format, d_in, batch, w, flags, nullptr);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int sgn = (flags & NFLHIP_DECOMP_SIGNED) != 0;
+  const bool ntt = (flags & NFLHIP_FORM_NTT) != 0, forced = (flags & NFLHIP_DECOMP_FUSED) != 0;
+  hipError_t e;
+  if (out_format != NFLHIP_FMT_WORDS) {
+    e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_decompose_compact<T>(ctx->shape, ctx->tabs, d_out, out_format, (const T *)d_in, batch, w, sgn, st);
+    });
+    return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "decompose (compact)");
+  }
+  if (ntt && (forced || (!(flags & NFLHIP_DECOMP_COMPOSED) && decompose_fused_on(ctx)))) {
+    e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_decompose_ntt_fused<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *)d_in, batch, w, sgn, st);
+    });
+    if (e == hipSuccess) return NFLHIP_OK;
+    if (e != hipErrorNotSupported) return hipfail(ctx, e, "decompose (fused)");
+    if (forced) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "decompose: a row of this shape does not fit the one-launch kernel's LDS");
+  }
+  e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_decompose_words<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *)d_in, batch, w, sgn, st);
+  });
+  if (e != hipSuccess) return hipfail(ctx, e, "decompose");
+  return ntt ? nflhip_ntt_fwd_dev(ctx, d_out, batch * decompose_terms(ctx, w), stream) : NFLHIP_OK;
+}
+int nflhip_gadget_mul_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, int w, void *stream) {
+  int rc = decompose_check(ctx, d_out, -1, d_in, batch, w, 0, nullptr);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_gadget_mul<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *)d_in, batch, w, (hipStream_t)stream);
+  });
+  return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "gadget_mul");
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

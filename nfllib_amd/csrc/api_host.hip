@@ -412,6 +412,19 @@ int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, s
   });
 }
 
+// gadget decomposition: the result is `terms` times the input (or a compact fraction of that), so the call is staged whole
+int nflhip_decompose(nflhip_ctx *ctx, void *h_out, int out_format, const void *h_in, size_t batch, int w, int flags) {
+  if (out_format < 0) return fail(ctx, NFLHIP_ERR_INVALID, "decompose: unknown output format");
+  size_t obytes = 0;
+  int rc = decompose_check(ctx, h_out, out_format, h_in, batch, w, flags, &obytes);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const HostIn ins[] = {{0, h_in, poly_bytes(ctx, batch)}};
+  return staged_call(ctx, batch, false, ins, 1, {1, h_out, obytes}, [&](const void *const *d, void *o, size_t cnt, void *st) {
+    return nflhip_decompose_dev(ctx, o, out_format, d[0], cnt, w, flags, st);
+  });
+}
+
 int nflhip_ntt_row(nflhip_ctx *ctx, void *h_rows, size_t cm, int mode, size_t rows) {
   CHECK_CTX(ctx);
   if (rows == 0) return NFLHIP_OK;

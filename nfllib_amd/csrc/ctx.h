@@ -155,6 +155,42 @@ inline int dot_check(const nflhip_ctx *ctx, const void *out, const nflhip_dot_op
   }
   return dot_check_out(ctx, out, obytes, addend);
 }
+// nflhip_decompose_dev / nflhip_decompose / nflhip_gadget_mul_dev: every argument check, before any device use.  format < 0: gadget_mul
+// (words out, no flags).  *obytes: the size of the output.
+inline size_t decompose_terms(const nflhip_ctx *ctx, int w) {
+  if (!ctx || ctx->cyclic) return 0;
+  const int bits = ctx->shape.limb_bits - 2;
+  if (w < 1 || w > bits - 1) return 0;
+  return ctx->shape.nm * (size_t)((bits + w - 1) / w);
+}
+inline int decompose_check(const nflhip_ctx *ctx, const void *out, int format, const void *in, size_t batch, int w, int flags, size_t *obytes) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  const char *what = format < 0 ? "gadget_mul" : "decompose";
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": not on a cyclic row context");
+  if (format < 0) format = NFLHIP_FMT_WORDS;
+  if (format != NFLHIP_FMT_WORDS && format != NFLHIP_FMT_I8 && format != NFLHIP_FMT_I16 && format != NFLHIP_FMT_I32)
+    return fail(ctx, NFLHIP_ERR_INVALID, "decompose: unknown output format");
+  const int plan = flags & (NFLHIP_DECOMP_COMPOSED | NFLHIP_DECOMP_FUSED), form = flags & ~(plan | NFLHIP_DECOMP_SIGNED);
+  if (form != NFLHIP_FORM_COEFF && form != NFLHIP_FORM_NTT) return fail(ctx, NFLHIP_ERR_INVALID, "decompose: unknown flag bits");
+  if (plan == (NFLHIP_DECOMP_COMPOSED | NFLHIP_DECOMP_FUSED) || (plan && form != NFLHIP_FORM_NTT))  // a plan flag: NTT form only, one at most
+    return fail(ctx, NFLHIP_ERR_INVALID, "decompose: a plan flag goes with the NTT form, one at most");
+  if (form == NFLHIP_FORM_NTT && format != NFLHIP_FMT_WORDS) return fail(ctx, NFLHIP_ERR_INVALID, "decompose: the NTT form is for words output");
+  const size_t terms = decompose_terms(ctx, w);
+  const int wmax = format == NFLHIP_FMT_I8 ? 7 : format == NFLHIP_FMT_I16 ? 15 : format == NFLHIP_FMT_I32 ? 31 : ctx->shape.limb_bits - 3;
+  if (terms == 0 || w > wmax)
+    return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": the digit width is out of range (1 to modulus bits - 1; 7 / 15 / 31 for a compact format)");
+  if (terms > 65535 || ctx->shape.nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": more than 65535 terms");
+  if (batch == 0) return NFLHIP_OK;
+  if (!out || !in) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t esz = format == NFLHIP_FMT_WORDS ? ctx->word * ctx->shape.nm : (size_t)1 << (format - 1);  // bytes per coefficient of a term
+  size_t polys, ob, ib;
+  if (__builtin_mul_overflow(batch, terms, &polys) || __builtin_mul_overflow(polys, ctx->shape.n * esz, &ob) ||
+      __builtin_mul_overflow(batch, poly_bytes(ctx, 1), &ib))
+    return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": the output size overflows");
+  if (ranges_overlap(out, ob, in, ib)) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": the output overlaps the input");
+  if (obytes) *obytes = ob;
+  return NFLHIP_OK;
+}
 constexpr size_t kStageHostMax = (size_t)1 << 20;
 inline void free_stage(nflhip_ctx *ctx, int slot) {
   if (ctx->stage[slot]) (void)(ctx->stage_host[slot] ? hipHostFree(ctx->stage[slot]) : hipFree(ctx->stage[slot]));

@@ -108,6 +108,22 @@ hipError_t launch_dot(const Shape &s, const DevTables &t, T *out, const T *a, si
 template <typename T>
 hipError_t launch_dot_ptrs(const Shape &s, const DevTables &t, T *out, const T *const *a, const T *const *b, size_t terms, const T *addend,
                            hipStream_t st);
+// gadget decomposition (kernels_decompose.hip; include/nflhip.h "gadget decomposition"): in = [batch][nm][n] canonical words in
+// coefficient form, digit width 1 <= w <= limb_bits - 3, l = ceil((limb_bits - 2) / w), terms = nm l; sgn: balanced digits.
+// _words: out = [batch][terms][nm][n], the digit spread over every row (coefficient form).  _compact: out = [batch][terms][n] of
+// int8 / int16 / int32 (format 1 / 2 / 3; w <= 7 / 15 / 31).  _ntt_fused: the words output forward-transformed, ONE launch, a
+// workgroup per output polynomial with one row in LDS; hipErrorNotSupported for rows beyond 32 KiB (api.hip then runs _words and
+// the forward launcher in place).  launch_gadget_mul: out[b][(m, t)][m'] = in[b][m] 2^(w t) mod p_m for m' = m, else 0.
+// out must not overlap in (api.hip checks).
+template <typename T>
+hipError_t launch_decompose_words(const Shape &s, const DevTables &t, T *out, const T *in, size_t batch, int w, int sgn, hipStream_t st);
+template <typename T>
+hipError_t launch_decompose_compact(const Shape &s, const DevTables &t, void *out, int format, const T *in, size_t batch, int w, int sgn,
+                                    hipStream_t st);
+template <typename T>
+hipError_t launch_decompose_ntt_fused(const Shape &s, const DevTables &t, T *out, const T *in, size_t batch, int w, int sgn, hipStream_t st);
+template <typename T>
+hipError_t launch_gadget_mul(const Shape &s, const DevTables &t, T *out, const T *in, size_t batch, int w, hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);
@@ -256,6 +272,7 @@ hipError_t warm_wave(hipStream_t st);
 hipError_t warm_automorph(hipStream_t st);
 hipError_t warm_rescale(hipStream_t st);
 hipError_t warm_dot(hipStream_t st);
+hipError_t warm_decompose(hipStream_t st);
 int polymul_level();   // 0 / 1 / 2: transforms of the coefficient-form products complete / incomplete (asm_launch.hip, nflhip_debug_polymul_level)
 hipError_t launch_polymul_pipe64k_u64(const Shape &s, const DevTables &t, uint64_t *c_v, const uint64_t *a_v,
                                       const uint64_t *b_v, int cnt_v, const uint64_t *fa_src, uint64_t *fa_dst,

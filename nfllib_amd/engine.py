@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
+from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -232,6 +232,57 @@ class Engine:
         groups = self._hb(a) // terms
         out = np.empty((groups, self.nmoduli, self.degree), dtype=self.np_dtype)
         self._chk(self.lib.nflhip_dot(self.ctx, _vp(out), _vp(a), _vp(b), groups, terms, int(bool(b_shared))))
+        return out
+
+    # ---- gadget decomposition: base-2^w digits of RNS rows (include/nflhip.h "gadget decomposition") ----
+    _DECOMP_FMT = {"words": FMT_WORDS, "i8": FMT_I8, "i16": FMT_I16, "i32": FMT_I32}
+
+    def decompose_terms(self, w):
+        """nmoduli * ceil(modulus bits / w) digit polynomials per input polynomial"""
+        terms = self.lib.nflhip_decompose_terms(self.ctx, w)
+        if terms == 0:
+            raise ValueError("digit width %r is out of range (1 to %d)" % (w, self.limb_bits - 3))
+        return terms
+
+    def _decomp_flags(self, signed, ntt, plan):
+        if plan not in (None, "composed", "fused"):
+            raise ValueError("plan is None, 'composed' or 'fused'")
+        return ((FORM_NTT if ntt else FORM_COEFF) | (DECOMP_SIGNED if signed else 0) |
+                {None: 0, "composed": DECOMP_COMPOSED, "fused": DECOMP_FUSED}[plan])
+
+    def decompose(self, a, w, signed=False, ntt=False, fmt="words", out=None, plan=None, stream=None):
+        """the base-2^w digits of every row of the coefficient-form batch a = [batch, nm, n]: term j = m * l + t is digit t of row m.
+        fmt "words" -> [batch * terms, nm, n], the digit spread over every row (ntt=True: forward-transformed; plan "composed" /
+        "fused" forces a plan); fmt "i8" / "i16" / "i32" -> [batch * terms, n] signed integers.  signed=True: balanced digits."""
+        t = _torch()
+        batch, terms, f = self._batch(a), self.decompose_terms(w), self._DECOMP_FMT[fmt]
+        if out is None:
+            if f == FMT_WORDS:
+                out = t.empty((batch * terms, self.nmoduli, self.degree), dtype=self.torch_dtype, device=a.device)
+            else:
+                out = t.empty((batch * terms, self.degree), dtype={FMT_I8: t.int8, FMT_I16: t.int16, FMT_I32: t.int32}[f], device=a.device)
+        self._chk(self.lib.nflhip_decompose_dev(self.ctx, _vp(out), f, _vp(a), batch, w, self._decomp_flags(signed, ntt, plan),
+                                                self._stream(stream)))
+        return out
+
+    def h_decompose(self, a, w, signed=False, ntt=False, fmt="words"):
+        """host-pointer variant: a numpy [batch, nm, n] batch -> [batch * terms, nm, n] words or [batch * terms, n] integers"""
+        a = np.ascontiguousarray(a, dtype=self.np_dtype)
+        batch, terms, f = self._hb(a), self.decompose_terms(w), self._DECOMP_FMT[fmt]
+        if f == FMT_WORDS:
+            out = np.empty((batch * terms, self.nmoduli, self.degree), dtype=self.np_dtype)
+        else:
+            out = np.empty((batch * terms, self.degree), dtype={FMT_I8: np.int8, FMT_I16: np.int16, FMT_I32: np.int32}[f])
+        self._chk(self.lib.nflhip_decompose(self.ctx, _vp(out), f, _vp(a), batch, w, self._decomp_flags(signed, ntt, None)))
+        return out
+
+    def gadget_mul(self, a, w, out=None, stream=None):
+        """key-generation companion: [batch, nm, n] -> [batch * terms, nm, n], term (m, t) holds a[m] * 2^(w t) mod p_m in row m and
+        zeros elsewhere, so that sum_j decompose(x)[j] * gadget_mul(y)[j] = x * y in every row"""
+        batch, terms = self._batch(a), self.decompose_terms(w)
+        if out is None:
+            out = _torch().empty((batch * terms, self.nmoduli, self.degree), dtype=self.torch_dtype, device=a.device)
+        self._chk(self.lib.nflhip_gadget_mul_dev(self.ctx, _vp(out), _vp(a), batch, w, self._stream(stream)))
         return out
 
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
