@@ -268,6 +268,36 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out._p = dst;
   }
 
+  // RNS base conversion and mod-down (nfl::base_convert / nfl::mod_down below).  base_convert works in place on the handle: the
+  // deferred queue of this ring type runs first, the value is copied to a payload of its own and converted there on the queue's
+  // stream, so copy-on-write sharers of the old value keep it.  mod_down goes into the ring with K moduli less and orders the two
+  // ring types' queues and streams exactly as rescale_into does.  Never fused into a queue's rewrites.
+  static void base_convert_into(poly_p &p, size_t s0, size_t ks, size_t d0, size_t kd, bool centered) {
+    lazy_t::inst().flush();
+    ptr_type src = p._p;  // (holds the old value while the launches are enqueued)
+    ptr_type dst = fresh();
+    const void *s = src->dev_ro();
+    void *d = dst->dev_wo();
+    detail::check(ctx_t::get(), nflhip_memcpy_d2d(ctx_t::get(), d, s, sizeof(T) * Degree * NbModuli, ctx_t::queue()), "base_convert");
+    detail::check(ctx_t::get(), nflhip_baseconv_dev(ctx_t::get(), d, d, 1, s0, ks, d0, kd, centered ? NFLHIP_BASECONV_CENTERED : 0, ctx_t::queue()),
+                  "base_convert");
+    p._p = dst;
+  }
+  template <size_t MO> static void mod_down_into(poly_p<T, Degree, MO> &out, poly_p const &in, bool floor) {
+    static_assert(MO >= 1 && MO < NbModuli, "nfl::mod_down drops the last K >= 1 moduli and keeps at least one");
+    typedef poly_p<T, Degree, MO> out_t;
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    ptr_type src = in._p;  // (holds the input while the launch is enqueued)
+    typename out_t::ptr_type dst = out_t::fresh();
+    const void *s = src->dev_ro();
+    void *d = dst->dev_wo();
+    detail::check(out_t::ctx_t::get(), nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue()), "mod_down");
+    detail::check(ctx_t::get(), nflhip_moddown_dev(ctx_t::get(), d, s, 1, NbModuli - MO, floor ? NFLHIP_MODDOWN_FLOOR : 0, ctx_t::queue()), "mod_down");
+    detail::check(ctx_t::get(), nflhip_stream_sync(ctx_t::get(), ctx_t::queue()), "mod_down");
+    out._p = dst;
+  }
+
   // Sum of products (nfl::dot / nfl::dot_add below): the deferred queue of this ring type runs first (on the caller), then the
   // pointer form of the entry on the queue's stream, 16 terms per launch, chained through the addend.  The result gets a
   // payload of its own, so `out` may be one of the inputs and copy-on-write sharers of out's old value keep it.
@@ -441,6 +471,26 @@ template <class T, size_t D, size_t M> void rescale(poly_p<T, D, M - 1> &out, po
 }
 template <class T, size_t D, size_t M> void rescale_ntt(poly_p<T, D, M - 1> &out, poly_p<T, D, M> const &in) {
   poly_p<T, D, M>::rescale_into(out, in, NFLHIP_FORM_NTT);
+}
+
+/* RNS base conversion and mod-down by the last K moduli (include/nflhip.h), coefficient form.  base_convert works in place: rows
+ * [d0, d0 + kd) of p become the conversion of rows [s0, s0 + ks), the fast one (x + u Q) or, with centered, the centred
+ * representative of x.  mod_down: out = in / P rounded to nearest (floor: floor(in / P) - u), P the product of the last K moduli of
+ * in's ring; out lives in the ring over the first M - K moduli, K deduced from the two types. */
+template <class T, size_t D, size_t M> void base_convert(poly<T, D, M> &p, size_t s0, size_t ks, size_t d0, size_t kd, bool centered = false) {
+  typedef poly<T, D, M> P;
+  detail::check(P::ctx(), nflhip_baseconv(P::ctx(), p.data(), p.cdata(), 1, s0, ks, d0, kd, centered ? NFLHIP_BASECONV_CENTERED : 0), "base_convert");
+}
+template <class T, size_t D, size_t M> void base_convert(poly_p<T, D, M> &p, size_t s0, size_t ks, size_t d0, size_t kd, bool centered = false) {
+  poly_p<T, D, M>::base_convert_into(p, s0, ks, d0, kd, centered);
+}
+template <class T, size_t D, size_t MO, size_t MI> void mod_down(poly<T, D, MO> &out, poly<T, D, MI> const &in, bool floor = false) {
+  static_assert(MO >= 1 && MO < MI, "nfl::mod_down drops the last K >= 1 moduli and keeps at least one");
+  typedef poly<T, D, MI> P;
+  detail::check(P::ctx(), nflhip_moddown(P::ctx(), out.data(), in.cdata(), 1, MI - MO, floor ? NFLHIP_MODDOWN_FLOOR : 0), "mod_down");
+}
+template <class T, size_t D, size_t MO, size_t MI> void mod_down(poly_p<T, D, MO> &out, poly_p<T, D, MI> const &in, bool floor = false) {
+  poly_p<T, D, MI>::template mod_down_into<MO>(out, in, floor);
 }
 
 /* Sums of products across polynomials (include/nflhip.h): out = sum_{j < terms} a[j] * b[j], element-wise in every row -- the

@@ -266,6 +266,46 @@ int nflhip_decompose_dev(nflhip_ctx *ctx, void *d_out, int out_format, const voi
 int nflhip_decompose(nflhip_ctx *ctx, void *h_out, int out_format, const void *h_in, size_t batch, int w, int flags);  /* staged host variant */
 int nflhip_gadget_mul_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, int w, void *stream);
 
+/* ---- RNS base conversion and mod-down by the last k moduli ------------------------------------
+ * Base conversion carries a value from one set of RNS rows to another without forming it: the mod-up of hybrid key switching, BFV
+ * multiplication, the scale-down by a special modulus, bootstrapping.  Coefficient form only (re-reading a residue mod p_i as an
+ * integer mod p_j does not commute with the transforms).  Source rows S = [s0, s0 + ks), destination rows D = [d0, d0 + kd), both
+ * inside [0, nmoduli), overlapping or not; Q = prod_{i in S} p_i, the source moduli pairwise distinct.  Per coefficient position,
+ * x in [0, Q) the integer behind the canonical source words x_i:
+ *     y_i = x_i (Q/p_i)^-1 mod p_i,   c_ij = (Q/p_i) mod p_j,   Q_j = Q mod p_j,   u = floor(sum_i y_i / p_i) in [0, ks)
+ *   fast (flags 0)             out_j = (sum_i y_i c_ij) mod p_j = (x + u Q) mod p_j          -- x_j itself for j in S
+ *   NFLHIP_BASECONV_CENTERED   out_j = (sum_i y_i c_ij - v Q_j) mod p_j,  v = floor((sum_i f_i + 2^59) / 2^60), f_i the fixed-point
+ *                              image of y_i / p_i with 60 fraction bits: f_i = floor(y_i floor(2^124 / p_i) / 2^64) for 64-bit limbs,
+ *                              f_i = y_i floor(2^60 / p_i) for 32- and 16-bit limbs.  v - u is 0 or 1: the output is the centred
+ *                              representative of x (x below Q/2, x - Q from there on) reduced mod p_j, except that an x with
+ *                              x/Q in [1/2, 1/2 + ks e / 2^60), e = 5/4 (64-bit limbs) or 2^(limb_bits - 2), may come out as x
+ *                              itself.
+ *   input, output   [batch][nmoduli][degree] both; only rows S are read, only rows D are written.  d_out == d_in is allowed (the
+ *                   normal mod-up: every source word is read before a word of its position is written); any other overlap is refused.
+ * nflhip_moddown_dev divides and rounds by P = the product of the LAST k moduli, 1 <= k <= nmoduli - 1: X in [0, Q_all) the integer
+ * behind all rows, conv_j the conversion of the last k rows to row j,
+ *     Y_j = (x_j - conv_j) P^-1 mod p_j        for j < nmoduli - k
+ *   default               the centred conversion: Y = X / P rounded to nearest, except that a fraction in [1/2, 1/2 + k e / 2^60) may
+ *                         round down.  For k = 1 this is nflhip_rescale_dev (coefficient form) wherever the fraction is outside that band.
+ *   NFLHIP_MODDOWN_FLOOR  the fast conversion: Y = floor(X / P) - u, the approximate mod-down of the literature.
+ *   input [batch][nmoduli][degree]; output the dense [batch][nmoduli - k][degree], the layout of the context over the first
+ *   nmoduli - k moduli; the output never overlaps the input.  One pass: nmoduli rows read, nmoduli - k written.
+ * The tables of a pair of ranges are built and uploaded on the FIRST call that names it (that call allocates and synchronises: make
+ * it before capturing into a hipGraph; while capturing it is NFLHIP_ERR_UNSUPPORTED); later calls allocate nothing, do not
+ * synchronise and can be captured.  NFLHIP_ERR_INVALID: a NULL context or pointer, an empty range or one outside the context, k out
+ * of range, unknown flag bits, a repeated source modulus (for the mod-down also a kept modulus that repeats a dropped one), a
+ * refused overlap, a size that overflows size_t, or a cyclic row context; every argument is checked before the device is touched.
+ * batch == 0 returns NFLHIP_OK and touches nothing (it builds no tables: the warm-up before a capture is a call with batch >= 1).
+ * The host variants stage both sides.  nflhip_baseconv accepts h_out == h_in; with h_out != h_in it writes EVERY row of h_out --
+ * rows D converted, the other rows copied from h_in -- unlike the device entry, which leaves the rows of d_out outside D as they are. */
+#define NFLHIP_BASECONV_CENTERED 0x100
+#define NFLHIP_MODDOWN_FLOOR 0x100
+int nflhip_baseconv_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd,
+                        int flags, void *stream);
+int nflhip_baseconv(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd, int flags);   /* staged host variant */
+int nflhip_moddown_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t k, int flags, void *stream);
+int nflhip_moddown(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t k, int flags);   /* staged host variant */
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

@@ -25,6 +25,7 @@ RESCALE_COMPOSED, RESCALE_FUSED = 0x100, 0x200
 DOT_UNTILED = 0x100
 DOT_MAX_POINTERS = 16
 DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED = 0x100, 0x200, 0x400
+BASECONV_CENTERED, MODDOWN_FLOOR = 0x100, 0x100
 
 
 class DotOperand(C.Structure):
@@ -63,6 +64,10 @@ SYMBOLS = [
     ("nflhip_decompose_terms", _sz, [_vp, _i]),
     ("nflhip_decompose_dev", _i, [_vp, _vp, _i, _vp, _sz, _i, _i, _vp]),
     ("nflhip_decompose", _i, [_vp, _vp, _i, _vp, _sz, _i, _i]),
+    ("nflhip_baseconv_dev", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_baseconv", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i]),
+    ("nflhip_moddown_dev", _i, [_vp, _vp, _vp, _sz, _sz, _i, _vp]),
+    ("nflhip_moddown", _i, [_vp, _vp, _vp, _sz, _sz, _i]),
     ("nflhip_gadget_mul_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),

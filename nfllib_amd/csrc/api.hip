@@ -388,7 +388,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -489,6 +489,8 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->ev_resc) (void)hipEventDestroy(ctx->ev_resc);
   if (ctx->resc_scratch) (void)hipFree(ctx->resc_scratch);
+  for (auto &kv : ctx->bconv) (void)hipFree(kv.second);
+  ctx->bconv.clear();
   if (ctx->hstream) (void)hipStreamDestroy(ctx->hstream);
   for (int k = 0; k < 2; ++k) {
     if (ctx->aux[k]) { (void)hipStreamSynchronize(ctx->aux[k]); (void)hipStreamDestroy(ctx->aux[k]); }
@@ -836,6 +838,71 @@ int nflhip_gadget_mul_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t
     return launch_gadget_mul<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *)d_in, batch, w, (hipStream_t)stream);
   });
   return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "gadget_mul");
+}
+
+// RNS base conversion and mod-down (kernels_baseconv.hip).  The record of a pair of row ranges (host_tables.cpp
+// build_baseconv_record) is built and uploaded by the first call that names the pair and kept until the context goes: that call
+// allocates and copies synchronously, later calls only look the pointer up.  The record is complete before it enters the map, and the
+// kernels of any stream read it only after this function returned it.
+static int baseconv_record(nflhip_ctx *ctx, size_t s0, size_t ks, size_t d0, size_t kd, bool moddown, hipStream_t st, const uint64_t **rec) {
+  std::lock_guard<std::mutex> lk(ctx->bconv_mu);
+  const std::array<size_t, 5> key = {s0, ks, d0, kd, moddown ? (size_t)1 : (size_t)0};
+  auto it = ctx->bconv.find(key);
+  if (it != ctx->bconv.end()) {
+    *rec = (const uint64_t *)it->second;
+    return NFLHIP_OK;
+  }
+  std::vector<uint64_t> h;
+  std::string err;
+  int rc;
+  try {
+    rc = build_baseconv_record(ctx->shape.limb_bits, ctx->h_P, s0, ks, d0, kd, moddown, &h, &err);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory while building the base conversion tables");
+  }
+  if (rc) return fail(ctx, rc, err);  // (host arithmetic only: a repeated modulus is refused before any device use)
+  if (is_capturing(st))
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "baseconv: the first call for a pair of row ranges uploads its tables, which a stream capture cannot do");
+  if ((rc = set_device(ctx))) return rc;
+  void *d = nullptr;
+  HIPCHK(ctx, hipMalloc(&d, h.size() * sizeof(uint64_t)));
+  hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return hipfail(ctx, e, "baseconv: table upload");
+  }
+  try {
+    ctx->bconv[key] = d;
+  } catch (const std::bad_alloc &) {
+    (void)hipFree(d);
+    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+  }
+  *rec = (const uint64_t *)d;
+  return NFLHIP_OK;
+}
+static int baseconv_run(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd, bool centred,
+                        bool moddown, hipStream_t st) {
+  if (batch == 0) return NFLHIP_OK;  // (touches nothing: no record is built for an empty batch)
+  const uint64_t *rec = nullptr;
+  int rc = baseconv_record(ctx, s0, ks, d0, kd, moddown, st, &rec);
+  if (rc || (rc = set_device(ctx))) return rc;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_baseconv<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *)d_in, rec, batch, s0, ks, d0, kd, centred, moddown, st);
+  });
+  return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, moddown ? "moddown" : "baseconv");
+}
+int nflhip_baseconv_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd, int flags,
+                        void *stream) {
+  int rc = baseconv_check(ctx, d_out, d_in, batch, s0, ks, d0, kd, flags, false);  // in full, before any device use
+  if (rc) return rc;
+  return baseconv_run(ctx, d_out, d_in, batch, s0, ks, d0, kd, (flags & NFLHIP_BASECONV_CENTERED) != 0, false, (hipStream_t)stream);
+}
+int nflhip_moddown_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t k, int flags, void *stream) {
+  const size_t nm = ctx ? ctx->shape.nm : 0, kept = k < nm ? nm - k : 0;
+  int rc = baseconv_check(ctx, d_out, d_in, batch, kept, k, 0, kept, flags, true);  // in full, before any device use
+  if (rc) return rc;
+  return baseconv_run(ctx, d_out, d_in, batch, kept, k, 0, kept, !(flags & NFLHIP_MODDOWN_FLOOR), true, (hipStream_t)stream);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

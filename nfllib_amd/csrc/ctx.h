@@ -5,7 +5,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <atomic>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -69,6 +71,10 @@ struct nflhip_ctx {
   size_t resc_scratch_bytes = 0;
   hipEvent_t ev_resc = nullptr;
   bool ev_resc_valid = false;
+  // RNS base conversion / mod-down (api.hip baseconv_record): the device record of every pair of row ranges used so far, keyed by
+  // (s0, ks, d0, kd, moddown); built and uploaded on first use under bconv_mu, freed with the context
+  std::mutex bconv_mu;
+  std::map<std::array<size_t, 5>, void *> bconv;
 };
 
 void pipe_destroy(nflhip_ctx *ctx);  // api_host.hip: frees the context's host-pointer pipeline
@@ -189,6 +195,32 @@ inline int decompose_check(const nflhip_ctx *ctx, const void *out, int format, c
     return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": the output size overflows");
   if (ranges_overlap(out, ob, in, ib)) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": the output overlaps the input");
   if (obytes) *obytes = ob;
+  return NFLHIP_OK;
+}
+// nflhip_baseconv_dev / nflhip_baseconv / nflhip_moddown_dev / nflhip_moddown: every argument check, before any device use.
+// moddown: s0 = nm - k, ks = k, d0 = 0, kd = nm - k and the output is the dense [batch][kd][n], which may not overlap the input;
+// otherwise the output is [batch][nm][n]: the input itself or apart from it.  (A repeated source modulus, or for the mod-down a kept
+// modulus that repeats a dropped one, is found by the table builder, on the host as well: api.hip baseconv_record.)
+inline int baseconv_check(const nflhip_ctx *ctx, const void *out, const void *in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd,
+                          int flags, bool moddown) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  const char *what = moddown ? "moddown" : "baseconv";
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": a cyclic row context has no modulus chain");
+  if (flags & ~(moddown ? NFLHIP_MODDOWN_FLOOR : NFLHIP_BASECONV_CENTERED)) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": unknown flag bits");
+  const size_t nm = ctx->shape.nm;
+  if (moddown && (ks == 0 || ks >= nm)) return fail(ctx, NFLHIP_ERR_INVALID, "moddown: k is out of range (1 to nmoduli - 1)");
+  if (ks == 0 || kd == 0 || s0 >= nm || ks > nm - s0 || d0 >= nm || kd > nm - d0)
+    return fail(ctx, NFLHIP_ERR_INVALID, "baseconv: a row range is empty or outside the context");
+  if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": more than 65535 rows");
+  if (batch == 0) return NFLHIP_OK;
+  if (!out || !in) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t row = ctx->shape.n * ctx->word;
+  size_t ib, ob;
+  if (__builtin_mul_overflow(batch, nm * row, &ib) || __builtin_mul_overflow(batch, (moddown ? kd : nm) * row, &ob))
+    return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": the size overflows");
+  if ((moddown || out != in) && ranges_overlap(out, ob, in, ib))
+    return fail(ctx, NFLHIP_ERR_INVALID, moddown ? "moddown: the output overlaps the input (the strides differ: never in place)"
+                                                 : "baseconv: the output overlaps the input without being the input");
   return NFLHIP_OK;
 }
 constexpr size_t kStageHostMax = (size_t)1 << 20;

@@ -431,6 +431,51 @@ int build_host_tables(int limb_bits, size_t n, size_t nm, int cyclic, int kmax_l
   return build(*out, n, nm, cyclic, kmax_log2, (const uint64_t *)P, (const uint64_t *)roots, (const uint64_t *)invk, err);
 }
 
+// RNS base conversion: the record of one pair of row ranges (host_tables.h).  (Q/p_i) mod p_j from prefix and suffix products of the
+// source moduli mod p_j, so the cost is ks kd multiplications; inverses by Fermat (the moduli are prime).
+int build_baseconv_record(int limb_bits, const std::vector<uint64_t> &P, size_t s0, size_t ks, size_t d0, size_t kd, bool moddown,
+                          std::vector<uint64_t> *out, std::string *err) {
+  const size_t nm = P.size();
+  if (ks == 0 || kd == 0 || s0 >= nm || ks > nm - s0 || d0 >= nm || kd > nm - d0) return invalid(err, "baseconv: a row range is empty or outside the context");
+  if (moddown && (s0 + ks != nm || d0 != 0 || kd != s0)) return invalid(err, "moddown: the dropped rows are the last k, the kept rows the others");
+  out->assign(baseconv_record_words(ks, kd), 0);
+  uint64_t *src = out->data(), *dst = src + 4 * ks, *c = dst + 8 * kd;
+  std::vector<uint64_t> pre(ks + 1), suf(ks + 1);
+  // products of the source moduli mod p, without the i-th: pre[i] suf[i + 1]
+  auto products = [&](uint64_t p) {
+    pre[0] = suf[ks] = 1 % p;
+    for (size_t i = 0; i < ks; ++i) pre[i + 1] = mulmod_h(pre[i], P[s0 + i] % p, p);
+    for (size_t i = ks; i-- > 0;) suf[i] = mulmod_h(suf[i + 1], P[s0 + i] % p, p);
+  };
+  for (size_t i = 0; i < ks; ++i) {
+    const uint64_t p = P[s0 + i];
+    products(p);
+    const uint64_t qi = mulmod_h(pre[i], suf[i + 1], p);  // (Q/p_i) mod p_i
+    if (qi == 0) return invalid(err, "baseconv: a source modulus repeats");
+    const uint64_t inv = powmod_h(qi, p - 2, p);
+    src[4 * i] = inv;
+    src[4 * i + 1] = shoup_h(inv, p, limb_bits);
+    src[4 * i + 2] = p;
+    src[4 * i + 3] = (uint64_t)((((u128)1) << (limb_bits == 64 ? 124 : 60)) / p);
+  }
+  for (size_t j = 0; j < kd; ++j) {
+    const uint64_t p = P[d0 + j];
+    products(p);
+    const uint64_t Qj = pre[ks];
+    dst[8 * j] = p;
+    dst[8 * j + 1] = Qj;
+    dst[8 * j + 2] = shoup_h(Qj, p, limb_bits);
+    if (moddown) {
+      if (Qj == 0) return invalid(err, "moddown: a kept modulus repeats a dropped one");
+      const uint64_t inv = powmod_h(Qj, p - 2, p);
+      dst[8 * j + 3] = inv;
+      dst[8 * j + 4] = shoup_h(inv, p, limb_bits);
+    }
+    for (size_t i = 0; i < ks; ++i) c[j * ks + i] = mulmod_h(pre[i], suf[i + 1], p);
+  }
+  return NFLHIP_OK;
+}
+
 // the reference's own table layouts (poly.hpp:228-237), rebuilt on the host from phi: what a caller holding
 // core::base sees.  Host arithmetic, once per request; the device never reads these.
 std::vector<uint64_t> reference_table(uint64_t p, uint64_t phi, uint64_t invk, int kmax_log2, size_t n, int wb, int which) {

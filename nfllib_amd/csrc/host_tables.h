@@ -32,6 +32,21 @@ struct HostTables {
 int build_host_tables(int limb_bits, size_t n, size_t nm, int cyclic, int kmax_log2, const void *P, const void *roots,
                       const void *invk, HostTables *out, std::string *err);
 
+// RNS base conversion (kernels_baseconv.hip; include/nflhip.h "RNS base conversion"): the record of one pair of row ranges, source
+// rows S = [s0, s0 + ks) and destination rows D = [d0, d0 + kd) of the moduli P (nm words of limb_bits bits each, as uint64_t), as
+// 64-bit words whatever the limb width, Q = prod_{i in S} p_i:
+//   [4 ks]    per source row i:       (Q/p_i)^-1 mod p_i, its Shoup companion floor(w 2^W / p_i), p_i, the 60-bit reciprocal
+//                                     (floor(2^60 / p_i) for 16- / 32-bit limbs; floor(2^124 / p_i) = ModConst::mu for 64-bit limbs)
+//   [8 kd]    per destination row j:  p_j, Q mod p_j, its Shoup companion, Q^-1 mod p_j, its Shoup companion (both 0 unless
+//                                     `moddown`), three zero words
+//   [kd][ks]  c_ij = (Q/p_i) mod p_j, destination-major
+// moddown: S is the last ks rows, D the rows before them (s0 = nm - ks, d0 = 0, kd = nm - ks), and Q^-1 mod p_j must exist.
+// Returns NFLHIP_OK, or NFLHIP_ERR_INVALID with *err set: a range outside [0, nm), an empty range, a repeated source modulus, or
+// (moddown) a kept modulus that repeats a dropped one.
+int build_baseconv_record(int limb_bits, const std::vector<uint64_t> &P, size_t s0, size_t ks, size_t d0, size_t kd, bool moddown,
+                          std::vector<uint64_t> *out, std::string *err);
+inline size_t baseconv_record_words(size_t ks, size_t kd) { return 4 * ks + 8 * kd + ks * kd; }
+
 // nflhip_get_table, NFLHIP_TAB_PHIS .. NFLHIP_TAB_INVOMEGAS: one modulus's table in the reference's own layout (n words, 2 n for
 // the two omega tables), each word below 2^limb_bits
 std::vector<uint64_t> reference_table(uint64_t p, uint64_t phi, uint64_t invk, int kmax_log2, size_t n, int limb_bits, int which);

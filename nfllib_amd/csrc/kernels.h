@@ -124,6 +124,13 @@ template <typename T>
 hipError_t launch_decompose_ntt_fused(const Shape &s, const DevTables &t, T *out, const T *in, size_t batch, int w, int sgn, hipStream_t st);
 template <typename T>
 hipError_t launch_gadget_mul(const Shape &s, const DevTables &t, T *out, const T *in, size_t batch, int w, hipStream_t st);
+// RNS base conversion and mod-down (kernels_baseconv.hip; include/nflhip.h "RNS base conversion"): rows [s0, s0 + ks) of in =
+// [batch][nm][n] converted to rows [d0, d0 + kd) of out, coefficient form.  rec: the device copy of the pair's record
+// (host_tables.h build_baseconv_record).  moddown: s0 + ks = nm, d0 = 0, kd = s0, out is the dense [batch][kd][n] and must not
+// overlap in; otherwise out = [batch][nm][n], the same buffer as in or apart from it (api.hip checks).
+template <typename T>
+hipError_t launch_baseconv(const Shape &s, const DevTables &t, T *out, const T *in, const uint64_t *rec, size_t batch, size_t s0, size_t ks,
+                           size_t d0, size_t kd, int centred, int moddown, hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);
@@ -273,6 +280,7 @@ hipError_t warm_automorph(hipStream_t st);
 hipError_t warm_rescale(hipStream_t st);
 hipError_t warm_dot(hipStream_t st);
 hipError_t warm_decompose(hipStream_t st);
+hipError_t warm_baseconv(hipStream_t st);
 int polymul_level();   // 0 / 1 / 2: transforms of the coefficient-form products complete / incomplete (asm_launch.hip, nflhip_debug_polymul_level)
 hipError_t launch_polymul_pipe64k_u64(const Shape &s, const DevTables &t, uint64_t *c_v, const uint64_t *a_v,
                                       const uint64_t *b_v, int cnt_v, const uint64_t *fa_src, uint64_t *fa_dst,

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
+from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -283,6 +283,47 @@ class Engine:
         if out is None:
             out = _torch().empty((batch * terms, self.nmoduli, self.degree), dtype=self.torch_dtype, device=a.device)
         self._chk(self.lib.nflhip_gadget_mul_dev(self.ctx, _vp(out), _vp(a), batch, w, self._stream(stream)))
+        return out
+
+    # ---- RNS base conversion and mod-down by the last k moduli (include/nflhip.h "RNS base conversion") ----
+    def baseconv(self, a, src, dst, centered=False, out=None, stream=None):
+        """rows src = (first, count) of the coefficient-form batch a = [batch, nm, n] converted to rows dst = (first, count): the
+        fast conversion x + u Q, or with centered=True the centred representative of x.  out=None works in place on a (the
+        normal mod-up); another `out` = [batch, nm, n] must not overlap a, and only its rows dst are written.  The first call
+        for a pair of ranges uploads its tables: make it before a graph capture."""
+        out = a if out is None else out
+        self._chk(self.lib.nflhip_baseconv_dev(self.ctx, _vp(out), _vp(a), self._batch(a), src[0], src[1], dst[0], dst[1],
+                                               BASECONV_CENTERED if centered else 0, self._stream(stream)))
+        return out
+
+    def mod_up(self, a, src, stream=None):
+        """baseconv from rows src = (first, count) to every row, in place (the source rows keep their words)"""
+        return self.baseconv(a, src, (0, self.nmoduli), stream=stream)
+
+    def mod_down(self, a, k, floor=False, out=None, stream=None):
+        """X / P rounded to nearest, P the product of the last k moduli (floor=True: floor(X / P) - u, the approximate mod-down):
+        [batch, nm, n] -> a new [batch, nm - k, n] tensor (or `out`, which must not overlap a) in the layout of
+        Engine(limb_bits, degree, nm - k); coefficient form"""
+        batch = self._batch(a)
+        if out is None:
+            out = _torch().empty((batch, max(self.nmoduli - k, 0), self.degree), dtype=self.torch_dtype, device=a.device)
+        self._chk(self.lib.nflhip_moddown_dev(self.ctx, _vp(out), _vp(a), batch, k, MODDOWN_FLOOR if floor else 0, self._stream(stream)))
+        return out
+
+    def h_baseconv(self, a, src, dst, centered=False):
+        """host-pointer variant: a numpy [batch, nm, n] batch -> a new one with rows dst converted from rows src"""
+        a = np.ascontiguousarray(a, dtype=self.np_dtype)
+        out = np.empty_like(a)
+        self._chk(self.lib.nflhip_baseconv(self.ctx, _vp(out), _vp(a), self._hb(a), src[0], src[1], dst[0], dst[1],
+                                           BASECONV_CENTERED if centered else 0))
+        return out
+
+    def h_mod_down(self, a, k, floor=False):
+        """host-pointer variant: a numpy [batch, nm, n] batch -> [batch, nm - k, n]"""
+        a = np.ascontiguousarray(a, dtype=self.np_dtype)
+        batch = self._hb(a)
+        out = np.empty((batch, max(self.nmoduli - k, 0), self.degree), dtype=self.np_dtype)
+        self._chk(self.lib.nflhip_moddown(self.ctx, _vp(out), _vp(a), batch, k, MODDOWN_FLOOR if floor else 0))
         return out
 
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
