@@ -150,21 +150,25 @@ template <class P> class device_batch {
   // [s0, s0 + ks) of src -- this batch itself (in place, the mod-up) or another batch of the same ring, in which case the other
   // rows of this batch stay as they are.  assign_mod_down: *this = round(src / P) (floor: floor(src / P) - u), P the product of the
   // last K moduli of src's ring, K = the difference of the two rings' modulus counts; streams ordered as in assign_rescale.
-  void assign_base_convert(const device_batch &src, size_t s0, size_t ks, size_t d0, size_t kd, bool centered = false) {
+  // ntt_form: both batches hold NTT-form values (the NTT-form entries: the same maps between the transforms).
+  void assign_base_convert(const device_batch &src, size_t s0, size_t ks, size_t d0, size_t kd, bool centered = false, bool ntt_form = false) {
     same_size(src);
     if (&src != this) same_device(src);
     src.strict("base_convert");
-    detail::check(ctx(), nflhip_baseconv_dev(ctx(), d_, src.d_, n_, s0, ks, d0, kd, centered ? NFLHIP_BASECONV_CENTERED : 0, queue()), "base_convert");
+    const int flags = centered ? NFLHIP_BASECONV_CENTERED : 0;
+    if (ntt_form) detail::check(ctx(), nflhip_baseconv_ntt_dev(ctx(), d_, src.d_, n_, s0, ks, d0, kd, flags, queue()), "base_convert_ntt");
+    else detail::check(ctx(), nflhip_baseconv_dev(ctx(), d_, src.d_, n_, s0, ks, d0, kd, flags, queue()), "base_convert");
   }
-  template <class Q> void assign_mod_down(const device_batch<Q> &src, bool floor = false) {
+  template <class Q> void assign_mod_down(const device_batch<Q> &src, bool floor = false, bool ntt_form = false) {
     static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && Q::nmoduli > P::nmoduli,
                   "assign_mod_down: the source ring has the same limbs and degree and at least one modulus more");
     if (src.size() != n_) throw std::runtime_error("nfl(hip): batch sizes differ");
     if (src.device() != device()) throw std::runtime_error("nfl(hip): mod_down operands on different devices");
     sync();
     src.strict("mod_down");
-    detail::check(src.ctx(), nflhip_moddown_dev(src.ctx(), d_, src.data(), n_, Q::nmoduli - P::nmoduli, floor ? NFLHIP_MODDOWN_FLOOR : 0, src.queue()),
-                  "mod_down");
+    const int flags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
+    if (ntt_form) detail::check(src.ctx(), nflhip_moddown_ntt_dev(src.ctx(), d_, src.data(), n_, Q::nmoduli - P::nmoduli, flags, src.queue()), "mod_down_ntt");
+    else detail::check(src.ctx(), nflhip_moddown_dev(src.ctx(), d_, src.data(), n_, Q::nmoduli - P::nmoduli, flags, src.queue()), "mod_down");
     src.sync();
   }
   // Sums of products across polynomials (include/nflhip.h): this batch holds `groups` polynomials, a and b groups * terms each,
@@ -520,15 +524,24 @@ template <class P> class sharded_batch {
       if (src.count(r) != count(r) || src.shard(r).device() != shards_[r].device()) throw std::runtime_error("nfl(hip): sharded batches are split differently");
     for (size_t r = 0; r < shards(); ++r) if (count(r)) shards_[r].assign_rescale(src.shard(r), ntt_form);
   }
-  void assign_base_convert(const sharded_batch &src, size_t s0, size_t ks, size_t d0, size_t kd, bool centered = false) {  // whole polynomials per shard
+  void assign_base_convert(const sharded_batch &src, size_t s0, size_t ks, size_t d0, size_t kd, bool centered = false,
+                           bool ntt_form = false) {  // whole polynomials per shard
     same_split(src);
-    for (size_t r = 0; r < shards(); ++r) if (count(r)) shards_[r].assign_base_convert(src.shards_[r], s0, ks, d0, kd, centered);
+    for (size_t r = 0; r < shards(); ++r) {
+      if (!count(r)) continue;
+      if (ntt_form) shards_[r].assign_base_convert(src.shards_[r], s0, ks, d0, kd, centered, true);
+      else shards_[r].assign_base_convert(src.shards_[r], s0, ks, d0, kd, centered);
+    }
   }
-  template <class Q> void assign_mod_down(const sharded_batch<Q> &src, bool floor = false) {  // shard by shard
+  template <class Q> void assign_mod_down(const sharded_batch<Q> &src, bool floor = false, bool ntt_form = false) {  // shard by shard
     if (src.size() != n_ || src.shards() != shards()) throw std::runtime_error("nfl(hip): sharded batches are split differently");
     for (size_t r = 0; r < shards(); ++r)
       if (src.count(r) != count(r) || src.shard(r).device() != shards_[r].device()) throw std::runtime_error("nfl(hip): sharded batches are split differently");
-    for (size_t r = 0; r < shards(); ++r) if (count(r)) shards_[r].assign_mod_down(src.shard(r), floor);
+    for (size_t r = 0; r < shards(); ++r) {
+      if (!count(r)) continue;
+      if (ntt_form) shards_[r].assign_mod_down(src.shard(r), floor, true);
+      else shards_[r].assign_mod_down(src.shard(r), floor);
+    }
   }
   static void assign_automorphisms(sharded_batch *const *outs, const uint64_t *ks, size_t count, const sharded_batch &src,
                                    bool ntt_form = false) {

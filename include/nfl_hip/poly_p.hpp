@@ -272,18 +272,20 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
   // deferred queue of this ring type runs first, the value is copied to a payload of its own and converted there on the queue's
   // stream, so copy-on-write sharers of the old value keep it.  mod_down goes into the ring with K moduli less and orders the two
   // ring types' queues and streams exactly as rescale_into does.  Never fused into a queue's rewrites.
-  static void base_convert_into(poly_p &p, size_t s0, size_t ks, size_t d0, size_t kd, bool centered) {
+  // ntt_form: the NTT-form entries (nfl::base_convert_ntt / nfl::mod_down_ntt), same ordering.
+  static void base_convert_into(poly_p &p, size_t s0, size_t ks, size_t d0, size_t kd, bool centered, bool ntt_form = false) {
     lazy_t::inst().flush();
     ptr_type src = p._p;  // (holds the old value while the launches are enqueued)
     ptr_type dst = fresh();
     const void *s = src->dev_ro();
     void *d = dst->dev_wo();
     detail::check(ctx_t::get(), nflhip_memcpy_d2d(ctx_t::get(), d, s, sizeof(T) * Degree * NbModuli, ctx_t::queue()), "base_convert");
-    detail::check(ctx_t::get(), nflhip_baseconv_dev(ctx_t::get(), d, d, 1, s0, ks, d0, kd, centered ? NFLHIP_BASECONV_CENTERED : 0, ctx_t::queue()),
-                  "base_convert");
+    const int flags = centered ? NFLHIP_BASECONV_CENTERED : 0;
+    if (ntt_form) detail::check(ctx_t::get(), nflhip_baseconv_ntt_dev(ctx_t::get(), d, d, 1, s0, ks, d0, kd, flags, ctx_t::queue()), "base_convert_ntt");
+    else detail::check(ctx_t::get(), nflhip_baseconv_dev(ctx_t::get(), d, d, 1, s0, ks, d0, kd, flags, ctx_t::queue()), "base_convert");
     p._p = dst;
   }
-  template <size_t MO> static void mod_down_into(poly_p<T, Degree, MO> &out, poly_p const &in, bool floor) {
+  template <size_t MO> static void mod_down_into(poly_p<T, Degree, MO> &out, poly_p const &in, bool floor, bool ntt_form = false) {
     static_assert(MO >= 1 && MO < NbModuli, "nfl::mod_down drops the last K >= 1 moduli and keeps at least one");
     typedef poly_p<T, Degree, MO> out_t;
     lazy_t::inst().flush();
@@ -293,7 +295,9 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     const void *s = src->dev_ro();
     void *d = dst->dev_wo();
     detail::check(out_t::ctx_t::get(), nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue()), "mod_down");
-    detail::check(ctx_t::get(), nflhip_moddown_dev(ctx_t::get(), d, s, 1, NbModuli - MO, floor ? NFLHIP_MODDOWN_FLOOR : 0, ctx_t::queue()), "mod_down");
+    const int flags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
+    if (ntt_form) detail::check(ctx_t::get(), nflhip_moddown_ntt_dev(ctx_t::get(), d, s, 1, NbModuli - MO, flags, ctx_t::queue()), "mod_down_ntt");
+    else detail::check(ctx_t::get(), nflhip_moddown_dev(ctx_t::get(), d, s, 1, NbModuli - MO, flags, ctx_t::queue()), "mod_down");
     detail::check(ctx_t::get(), nflhip_stream_sync(ctx_t::get(), ctx_t::queue()), "mod_down");
     out._p = dst;
   }
@@ -491,6 +495,25 @@ template <class T, size_t D, size_t MO, size_t MI> void mod_down(poly<T, D, MO> 
 }
 template <class T, size_t D, size_t MO, size_t MI> void mod_down(poly_p<T, D, MO> &out, poly_p<T, D, MI> const &in, bool floor = false) {
   poly_p<T, D, MI>::template mod_down_into<MO>(out, in, floor);
+}
+
+/* The same on NTT-form values (include/nflhip.h "RNS base conversion and mod-down, NTT form"): what base_convert / mod_down make of
+ * the coefficient form, forward-transformed -- the mod-up of a digit and the final mod-down of a key switch without leaving the NTT
+ * form.  Queues and streams are ordered exactly as by base_convert / mod_down. */
+template <class T, size_t D, size_t M> void base_convert_ntt(poly<T, D, M> &p, size_t s0, size_t ks, size_t d0, size_t kd, bool centered = false) {
+  typedef poly<T, D, M> P;
+  detail::check(P::ctx(), nflhip_baseconv_ntt(P::ctx(), p.data(), p.cdata(), 1, s0, ks, d0, kd, centered ? NFLHIP_BASECONV_CENTERED : 0), "base_convert_ntt");
+}
+template <class T, size_t D, size_t M> void base_convert_ntt(poly_p<T, D, M> &p, size_t s0, size_t ks, size_t d0, size_t kd, bool centered = false) {
+  poly_p<T, D, M>::base_convert_into(p, s0, ks, d0, kd, centered, true);
+}
+template <class T, size_t D, size_t MO, size_t MI> void mod_down_ntt(poly<T, D, MO> &out, poly<T, D, MI> const &in, bool floor = false) {
+  static_assert(MO >= 1 && MO < MI, "nfl::mod_down_ntt drops the last K >= 1 moduli and keeps at least one");
+  typedef poly<T, D, MI> P;
+  detail::check(P::ctx(), nflhip_moddown_ntt(P::ctx(), out.data(), in.cdata(), 1, MI - MO, floor ? NFLHIP_MODDOWN_FLOOR : 0), "mod_down_ntt");
+}
+template <class T, size_t D, size_t MO, size_t MI> void mod_down_ntt(poly_p<T, D, MO> &out, poly_p<T, D, MI> const &in, bool floor = false) {
+  poly_p<T, D, MI>::template mod_down_into<MO>(out, in, floor, true);
 }
 
 /* Sums of products across polynomials (include/nflhip.h): out = sum_{j < terms} a[j] * b[j], element-wise in every row -- the

@@ -306,6 +306,45 @@ int nflhip_baseconv(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch
 int nflhip_moddown_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t k, int flags, void *stream);
 int nflhip_moddown(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t k, int flags);   /* staged host variant */
 
+/* ---- RNS base conversion and mod-down, NTT form ------------------------------------------------
+ * The same two maps on NTT-form data, so that a hybrid key switch never leaves the NTT form: the mod-up of a digit and the final
+ * mod-down are one call each, around nflhip_dot_dev.  Input and output words are in the order nflhip_ntt_fwd_dev produces; the
+ * semantics are those of the coefficient-form entries above, word for word (same ranges, same `flags` = NFLHIP_BASECONV_CENTERED /
+ * NFLHIP_MODDOWN_FLOOR, same rounding band, same first-call table upload, same errors):
+ *   nflhip_baseconv_ntt_dev   out row j = NTT_j(conv_j(INTT_i(in row i), i in S)) for j in D, conv the fast or the centred map of
+ *                             nflhip_baseconv_dev.  For j in D and S this is the input row itself (the words are canonical): in
+ *                             place (d_out == d_in, allowed; any other overlap is refused) the final words of those rows are the
+ *                             input's, out of place they are copied.  Rows of d_out outside D stay as they are.
+ *                                 ntt_inv(baseconv_ntt(ntt_fwd(x))) == baseconv(x)   on rows D, when D is the whole context;
+ *                             in general every written row is the forward transform of the coefficient-form entry's row.
+ *   nflhip_moddown_ntt_dev    Y_j = (x_j - NTT_j(conv_j(INTT(last k rows)))) P^-1 mod p_j, dense [batch][nmoduli - k][degree]:
+ *                                 ntt_inv'(moddown_ntt(ntt_fwd(x))) == moddown(x),   ntt_inv' of the context over the first
+ *                             nmoduli - k moduli.  For k = 1, outside the band, it equals nflhip_rescale_dev(..., NFLHIP_FORM_NTT).
+ * Two plans compute the same words, each the other's cross-check; `flags` may carry at most one plan flag:
+ *   NFLHIP_BASECONV_NTT_FUSED     ONE launch: a workgroup per polynomial keeps the ks inverse-transformed source rows, one work row
+ *                                 and (centred conversion, i.e. NFLHIP_BASECONV_CENTERED or the mod-down without
+ *                                 NFLHIP_MODDOWN_FLOOR) one row of corrections in LDS.  It needs
+ *                                     (ks + 1 + c) * degree * (limb_bits / 8) <= 65536 bytes,   c = 1 centred, 0 otherwise;
+ *                                 beyond that the flag gives NFLHIP_ERR_UNSUPPORTED.  ks rows read, the rows of D outside S written.
+ *   NFLHIP_BASECONV_NTT_COMPOSED  the source rows are gathered into context-owned scratch and inverse-transformed, the coefficient-
+ *                                 form kernel converts them, the result is forward-transformed (and, for the mod-down, combined
+ *                                 with the kept rows in one more pass): every shape, any transform launcher of the project.  In
+ *                                 place with D the whole context, the rows of S pass through their coefficient form on the way.
+ *   neither                       the one-launch kernel when it fits and a row has up to 2048 words, the composed plan otherwise
+ *                                 and for contexts created under NFLHIP_VARIANT=hipcc.
+ * Both plans can be captured into a hipGraph after a warm-up call: the first call for a pair of ranges uploads its tables, and the
+ * composed plan allocates its scratch and its child contexts on first use and whenever the batch grows -- while capturing each of
+ * these is NFLHIP_ERR_UNSUPPORTED and the stream stays usable.  A graph that replays the composed plan must not run concurrently
+ * with other composed calls on the same context (the scratch is shared; outside a capture calls on different streams are ordered by
+ * events).  NFLHIP_ERR_INVALID additionally for both plan flags at once.  batch == 0 returns NFLHIP_OK and touches nothing. */
+#define NFLHIP_BASECONV_NTT_COMPOSED 0x200
+#define NFLHIP_BASECONV_NTT_FUSED 0x400
+int nflhip_baseconv_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd,
+                            int flags, void *stream);
+int nflhip_baseconv_ntt(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd, int flags);   /* staged host variant */
+int nflhip_moddown_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t k, int flags, void *stream);
+int nflhip_moddown_ntt(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t k, int flags);   /* staged host variant */
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

@@ -26,6 +26,7 @@ DOT_UNTILED = 0x100
 DOT_MAX_POINTERS = 16
 DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED = 0x100, 0x200, 0x400
 BASECONV_CENTERED, MODDOWN_FLOOR = 0x100, 0x100
+BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED = 0x200, 0x400
 
 
 class DotOperand(C.Structure):
@@ -68,6 +69,10 @@ SYMBOLS = [
     ("nflhip_baseconv", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i]),
     ("nflhip_moddown_dev", _i, [_vp, _vp, _vp, _sz, _sz, _i, _vp]),
     ("nflhip_moddown", _i, [_vp, _vp, _vp, _sz, _sz, _i]),
+    ("nflhip_baseconv_ntt_dev", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_baseconv_ntt", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i]),
+    ("nflhip_moddown_ntt_dev", _i, [_vp, _vp, _vp, _sz, _sz, _i, _vp]),
+    ("nflhip_moddown_ntt", _i, [_vp, _vp, _vp, _sz, _sz, _i]),
     ("nflhip_gadget_mul_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),

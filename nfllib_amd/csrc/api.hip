@@ -388,7 +388,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -489,6 +489,12 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->ev_resc) (void)hipEventDestroy(ctx->ev_resc);
   if (ctx->resc_scratch) (void)hipFree(ctx->resc_scratch);
+  for (auto &kv : ctx->bcn_child) nflhip_ctx_destroy(kv.second);
+  ctx->bcn_child.clear();
+  (void)hipSetDevice(ctx->device);
+  if (ctx->ev_bcn) (void)hipEventDestroy(ctx->ev_bcn);
+  for (int k = 0; k < 2; ++k)
+    if (ctx->bcn_scratch[k]) (void)hipFree(ctx->bcn_scratch[k]);
   for (auto &kv : ctx->bconv) (void)hipFree(kv.second);
   ctx->bconv.clear();
   if (ctx->hstream) (void)hipStreamDestroy(ctx->hstream);
@@ -903,6 +909,145 @@ int nflhip_moddown_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t ba
   int rc = baseconv_check(ctx, d_out, d_in, batch, kept, k, 0, kept, flags, true);  // in full, before any device use
   if (rc) return rc;
   return baseconv_run(ctx, d_out, d_in, batch, kept, k, 0, kept, !(flags & NFLHIP_MODDOWN_FLOOR), true, (hipStream_t)stream);
+}
+
+// The same on NTT-form data (kernels_baseconv_ntt.hip).  Two plans with the same words, each the other's cross-check:
+//   fused     one launch, the source rows in LDS (launch_baseconv_ntt_fused); needs (ks + 1 + centred) rows within 64 KiB
+//   composed  the source rows gathered into context-owned scratch and inverse-transformed by a child context over the moduli of S;
+//             k_baseconv converts from the scratch (launch_baseconv_rows); the result is forward-transformed -- by the context
+//             itself when D is every row, else in a second scratch by a child context over the moduli of D and scattered to rows
+//             D; the mod-down converts into the dense output, transforms it with the child over the first nm - k moduli and
+//             combines it with the input's kept rows in one streaming pass.  Every transform launcher of the project serves it.
+// The child context over (first row, count): created on first use, never while capturing.  (0, nm) is the context itself.
+static int bcn_child(nflhip_ctx *ctx, size_t first, size_t count, bool cap, nflhip_ctx **out) {  // under bcn_mu
+  if (first == 0 && count == ctx->shape.nm) {
+    *out = ctx;
+    return NFLHIP_OK;
+  }
+  const std::array<size_t, 2> key = {first, count};
+  auto it = ctx->bcn_child.find(key);
+  if (it != ctx->bcn_child.end()) {
+    *out = it->second;
+    return NFLHIP_OK;
+  }
+  if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "baseconv_ntt: the composed plan's child context has to be created, which a stream capture cannot do");
+  nflhip_ctx *child = nullptr;
+  int rc = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    std::vector<T> P(count), roots(count), invk(count);
+    for (size_t i = 0; i < count; ++i) {
+      P[i] = (T)ctx->h_P[first + i];
+      roots[i] = (T)ctx->h_roots[first + i];
+      invk[i] = (T)ctx->h_invk[first + i];
+    }
+    return ctx_create_mode(&child, ctx->device, ctx->shape.limb_bits, ctx->shape.n, count, P.data(), roots.data(), invk.data(), ctx->kmax_log2, 0, ctx);
+  });
+  if (rc) return rc;
+  try {
+    ctx->bcn_child[key] = child;
+  } catch (const std::bad_alloc &) {
+    nflhip_ctx_destroy(child);
+    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+  }
+  *out = child;
+  return NFLHIP_OK;
+}
+static int bcn_scratch(nflhip_ctx *ctx, int slot, size_t need, bool cap) {  // under bcn_mu
+  if (ctx->bcn_scratch_bytes[slot] >= need) return NFLHIP_OK;
+  if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "baseconv_ntt: the composed plan's scratch has to grow, which a stream capture cannot do");
+  if (ctx->bcn_scratch[slot]) HIPCHK(ctx, hipFree(ctx->bcn_scratch[slot]));  // (synchronises: nothing still reads it)
+  ctx->bcn_scratch[slot] = nullptr;
+  ctx->bcn_scratch_bytes[slot] = 0;
+  HIPCHK(ctx, hipMalloc(&ctx->bcn_scratch[slot], need));
+  ctx->bcn_scratch_bytes[slot] = need;
+  return NFLHIP_OK;
+}
+static int baseconv_ntt_composed(nflhip_ctx *ctx, void *out, const void *in, const uint64_t *rec, size_t batch, size_t s0, size_t ks, size_t d0,
+                                 size_t kd, bool centred, bool moddown, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->bcn_mu);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t row = ctx->shape.n * ctx->word, nm = ctx->shape.nm;
+  const bool cap = is_capturing(st), whole = !moddown && d0 == 0 && kd == nm;
+  nflhip_ctx *cs = nullptr, *cd = nullptr;
+  int rc = bcn_child(ctx, s0, ks, cap, &cs);
+  if (!rc) rc = bcn_child(ctx, d0, kd, cap, &cd);
+  if (!rc) rc = bcn_scratch(ctx, 0, batch * ks * row, cap);
+  // (the second scratch starts d0 rows early: k_baseconv writes row d0 + j of a polynomial of kd rows, so the dense rows begin at
+  // row d0 of the buffer)
+  if (!rc && !moddown && !whole) rc = bcn_scratch(ctx, 1, (d0 + batch * kd) * row, cap);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (!ctx->ev_bcn) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_bcn, hipEventDisableTiming));
+  if (!cap && ctx->ev_bcn_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_bcn, 0));  // a previous call on another stream
+  void *src = ctx->bcn_scratch[0];
+  HIPCHK(ctx, hipMemcpy2DAsync(src, ks * row, (const char *)in + s0 * row, nm * row, ks * row, batch, hipMemcpyDeviceToDevice, st));
+  rc = nflhip_ntt_inv_dev(cs, src, batch, st);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  void *conv = moddown || whole ? out : ctx->bcn_scratch[1];  // where k_baseconv's polynomial 0, row 0 would be
+  const size_t onm = moddown || !whole ? kd : nm;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_baseconv_rows<T>(ctx->shape, ctx->tabs, (T *)conv, onm, (const T *)src, ks, rec, batch, ks, d0, kd, centred, st);
+  });
+  if (e != hipSuccess) return hipfail(ctx, e, "baseconv_ntt: conversion");
+  void *dense = moddown || whole ? out : (void *)((char *)conv + d0 * row);
+  rc = nflhip_ntt_fwd_dev(cd, dense, batch, st);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (moddown) {
+    e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_moddown_ntt_combine<T>(ctx->shape, (T *)out, (const T *)in, rec, batch, ks, st);
+    });
+    if (e != hipSuccess) return hipfail(ctx, e, "moddown_ntt: combine");
+  } else if (!whole) {
+    HIPCHK(ctx, hipMemcpy2DAsync((char *)out + d0 * row, nm * row, dense, kd * row, kd * row, batch, hipMemcpyDeviceToDevice, st));
+  }
+  if (!cap) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev_bcn, st));
+    ctx->ev_bcn_valid = true;
+  }
+  return NFLHIP_OK;
+}
+// Where the one-launch kernel serves by default: when its rows fit the LDS and a row has up to 2048 words.  Measured against the
+// composed plan in one run, alternated (profiles/r13_baseconv_ntt.txt), composed / fused: x1.43 - x1.78 for the mod-ups
+// 1 -> 4 and 2 -> 4 and x1.09 - x1.45 for the mod-downs k = 1, 2 at u64/1024/4 and u64/2048/4, but x0.82 / x0.73 at u32/4096/3 (rows of
+// 16 KiB) and x0.88 at u64/4096/4 (32 KiB) -- at 4096 words the generated register-tiled transforms of the composed plan outrun the
+// radix-4 LDS transforms by more than the gather and the extra passes cost, whatever the row's bytes: the rule is in words, as
+// decompose_fused_on.  Contexts created under NFLHIP_VARIANT=hipcc compose.
+static bool baseconv_ntt_fused_on(const nflhip_ctx *ctx) {
+  return !ctx->shape.compiled_only && ctx->shape.n <= 2048;
+}
+static int baseconv_ntt_run(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd, int flags,
+                            bool centred, bool moddown, hipStream_t st) {
+  if (batch == 0) return NFLHIP_OK;  // (touches nothing: no record is built for an empty batch)
+  const uint64_t *rec = nullptr;
+  int rc = baseconv_record(ctx, s0, ks, d0, kd, moddown, st, &rec);
+  if (rc || (rc = set_device(ctx))) return rc;
+  const bool forced = (flags & NFLHIP_BASECONV_NTT_FUSED) != 0;
+  if (forced || (!(flags & NFLHIP_BASECONV_NTT_COMPOSED) && baseconv_ntt_fused_on(ctx))) {
+    hipError_t e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_baseconv_ntt_fused<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *)d_in, rec, batch, s0, ks, d0, kd, centred, moddown, st);
+    });
+    if (e == hipSuccess) return NFLHIP_OK;
+    if (e != hipErrorNotSupported) return hipfail(ctx, e, moddown ? "moddown_ntt (fused)" : "baseconv_ntt (fused)");
+    if (forced) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "baseconv_ntt: the source rows of this call do not fit the one-launch kernel's LDS");
+  }
+  return baseconv_ntt_composed(ctx, d_out, d_in, rec, batch, s0, ks, d0, kd, centred, moddown, st);
+}
+int nflhip_baseconv_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd, int flags,
+                            void *stream) {
+  int rc = baseconv_ntt_check(ctx, d_out, d_in, batch, s0, ks, d0, kd, flags, false);  // in full, before any device use
+  if (rc) return rc;
+  return baseconv_ntt_run(ctx, d_out, d_in, batch, s0, ks, d0, kd, flags, (flags & NFLHIP_BASECONV_CENTERED) != 0, false, (hipStream_t)stream);
+}
+int nflhip_moddown_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t k, int flags, void *stream) {
+  const size_t nm = ctx ? ctx->shape.nm : 0, kept = k < nm ? nm - k : 0;
+  int rc = baseconv_ntt_check(ctx, d_out, d_in, batch, kept, k, 0, kept, flags, true);  // in full, before any device use
+  if (rc) return rc;
+  return baseconv_ntt_run(ctx, d_out, d_in, batch, kept, k, 0, kept, flags, !(flags & NFLHIP_MODDOWN_FLOOR), true, (hipStream_t)stream);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

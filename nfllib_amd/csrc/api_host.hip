@@ -416,6 +416,30 @@ int nflhip_moddown(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch,
   });
 }
 
+// the same on NTT-form data
+int nflhip_baseconv_ntt(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd, int flags) {
+  int rc = baseconv_ntt_check(ctx, h_out, h_in, batch, s0, ks, d0, kd, flags, false);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t bytes = poly_bytes(ctx, batch);
+  const HostIn ins[] = {{0, h_in, bytes}};
+  return staged_call(ctx, batch, false, ins, 1, {1, h_out, bytes}, [&](const void *const *d, void *o, size_t cnt, void *st) {
+    if (o != d[0]) HIPCHK(ctx, hipMemcpyAsync(o, d[0], poly_bytes(ctx, cnt), hipMemcpyDefault, (hipStream_t)st));
+    return nflhip_baseconv_ntt_dev(ctx, o, o, cnt, s0, ks, d0, kd, flags, st);
+  });
+}
+int nflhip_moddown_ntt(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t k, int flags) {
+  const size_t nm = ctx ? ctx->shape.nm : 0, kept = k < nm ? nm - k : 0;
+  int rc = baseconv_ntt_check(ctx, h_out, h_in, batch, kept, k, 0, kept, flags, true);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t bytes = poly_bytes(ctx, batch), obytes = batch * kept * ctx->shape.n * ctx->word;
+  const HostIn ins[] = {{0, h_in, bytes}};
+  return staged_call(ctx, batch, false, ins, 1, {1, h_out, obytes}, [&](const void *const *d, void *o, size_t cnt, void *st) {
+    return nflhip_moddown_ntt_dev(ctx, o, d[0], cnt, k, flags, st);
+  });
+}
+
 // sums of products across polynomials: the operands are `terms` times the size of the result, so the call is staged whole
 int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, size_t groups, size_t terms, int b_shared) {
   if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");

@@ -75,6 +75,15 @@ struct nflhip_ctx {
   // (s0, ks, d0, kd, moddown); built and uploaded on first use under bconv_mu, freed with the context
   std::mutex bconv_mu;
   std::map<std::array<size_t, 5>, void *> bconv;
+  // composed NTT-form base conversion / mod-down (api.hip baseconv_ntt_composed): child contexts over row ranges of this one,
+  // keyed by (first row, count) and created on first use; scratch 0 holds the gathered source rows [batch][ks][n], scratch 1 the
+  // converted rows of a destination range that is not the whole context; calls are ordered on both by ev_bcn.  All under bcn_mu.
+  std::mutex bcn_mu;
+  std::map<std::array<size_t, 2>, nflhip_ctx *> bcn_child;
+  void *bcn_scratch[2] = {nullptr, nullptr};
+  size_t bcn_scratch_bytes[2] = {0, 0};
+  hipEvent_t ev_bcn = nullptr;
+  bool ev_bcn_valid = false;
 };
 
 void pipe_destroy(nflhip_ctx *ctx);  // api_host.hip: frees the context's host-pointer pipeline
@@ -222,6 +231,15 @@ inline int baseconv_check(const nflhip_ctx *ctx, const void *out, const void *in
     return fail(ctx, NFLHIP_ERR_INVALID, moddown ? "moddown: the output overlaps the input (the strides differ: never in place)"
                                                  : "baseconv: the output overlaps the input without being the input");
   return NFLHIP_OK;
+}
+// the NTT-form entries: the same checks, after the plan flags (one at most) are taken off
+inline int baseconv_ntt_check(const nflhip_ctx *ctx, const void *out, const void *in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd,
+                              int flags, bool moddown) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  const int plan = flags & (NFLHIP_BASECONV_NTT_COMPOSED | NFLHIP_BASECONV_NTT_FUSED);
+  if (plan == (NFLHIP_BASECONV_NTT_COMPOSED | NFLHIP_BASECONV_NTT_FUSED))
+    return fail(ctx, NFLHIP_ERR_INVALID, moddown ? "moddown_ntt: one plan flag at most" : "baseconv_ntt: one plan flag at most");
+  return baseconv_check(ctx, out, in, batch, s0, ks, d0, kd, flags & ~plan, moddown);
 }
 constexpr size_t kStageHostMax = (size_t)1 << 20;
 inline void free_stage(nflhip_ctx *ctx, int slot) {

@@ -131,6 +131,23 @@ hipError_t launch_gadget_mul(const Shape &s, const DevTables &t, T *out, const T
 template <typename T>
 hipError_t launch_baseconv(const Shape &s, const DevTables &t, T *out, const T *in, const uint64_t *rec, size_t batch, size_t s0, size_t ks,
                            size_t d0, size_t kd, int centred, int moddown, hipStream_t st);
+// the same kernels on an input of `inm` rows per polynomial whose rows [0, ks) are the sources (a gathered, inverse-transformed
+// copy of rows S: the composed NTT-form plans of api.hip), written to rows [d0, d0 + kd) of out = [batch][onm][n]; rec is the record
+// of the pair in the CONTEXT's numbering (destination row j reduces under the context's modulus d0 + j).  out never is in.
+template <typename T>
+hipError_t launch_baseconv_rows(const Shape &s, const DevTables &t, T *out, size_t onm, const T *in, size_t inm, const uint64_t *rec, size_t batch,
+                                size_t ks, size_t d0, size_t kd, int centred, hipStream_t st);
+// NTT-form base conversion and mod-down (kernels_baseconv_ntt.hip; include/nflhip.h "RNS base conversion, NTT form").  _fused: ONE
+// launch, a workgroup per polynomial with ks + 1 rows in LDS, one more in centred mode; hipErrorNotSupported when that exceeds 64 KiB
+// or n < 4.  Operands as launch_baseconv.  _combine: the last pass of the composed mod-down, out row j = (in row j - out row j) P^-1
+// mod p_j over the dense out = [batch][nm - k][n]; rec the mod-down's record.
+static constexpr size_t kBaseconvNttLdsBytes = 65536;
+inline size_t baseconv_ntt_fused_lds(size_t ks, size_t n, size_t word, int centred) { return (ks + 1 + (centred ? 1 : 0)) * n * word; }
+template <typename T>
+hipError_t launch_baseconv_ntt_fused(const Shape &s, const DevTables &t, T *out, const T *in, const uint64_t *rec, size_t batch, size_t s0,
+                                     size_t ks, size_t d0, size_t kd, int centred, int moddown, hipStream_t st);
+template <typename T>
+hipError_t launch_moddown_ntt_combine(const Shape &s, T *out, const T *in, const uint64_t *rec, size_t batch, size_t k, hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);
@@ -281,6 +298,7 @@ hipError_t warm_rescale(hipStream_t st);
 hipError_t warm_dot(hipStream_t st);
 hipError_t warm_decompose(hipStream_t st);
 hipError_t warm_baseconv(hipStream_t st);
+hipError_t warm_baseconv_ntt(hipStream_t st);
 int polymul_level();   // 0 / 1 / 2: transforms of the coefficient-form products complete / incomplete (asm_launch.hip, nflhip_debug_polymul_level)
 hipError_t launch_polymul_pipe64k_u64(const Shape &s, const DevTables &t, uint64_t *c_v, const uint64_t *a_v,
                                       const uint64_t *b_v, int cnt_v, const uint64_t *fa_src, uint64_t *fa_dst,

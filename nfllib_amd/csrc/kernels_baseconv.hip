@@ -167,6 +167,31 @@ template hipError_t launch_baseconv<uint16_t>(const Shape &, const DevTables &, 
 template hipError_t launch_baseconv<uint32_t>(const Shape &, const DevTables &, uint32_t *, const uint32_t *, const uint64_t *, size_t, size_t, size_t, size_t, size_t, int, int, hipStream_t);
 template hipError_t launch_baseconv<uint64_t>(const Shape &, const DevTables &, uint64_t *, const uint64_t *, const uint64_t *, size_t, size_t, size_t, size_t, size_t, int, int, hipStream_t);
 
+// rows [0, ks) of in = [batch][inm][n] to rows [d0, d0 + kd) of out = [batch][onm][n]: the kernel takes `nm` only as the input's rows
+// per polynomial and `s0` only as the source row offset, so a gathered copy of the source rows is served by the same code
+template <typename T>
+hipError_t launch_baseconv_rows(const Shape &s, const DevTables &t, T *out, size_t onm, const T *in, size_t inm, const uint64_t *rec, size_t batch,
+                                size_t ks, size_t d0, size_t kd, int centred, hipStream_t st) {
+  if (!rec || ks == 0 || kd == 0 || ks > inm || d0 + kd > s.nm || inm > 65535 || onm > 65535 || (const T *)out == in) return hipErrorInvalidValue;
+  if (batch == 0) return hipSuccess;
+  constexpr int V = 16 / sizeof(T);
+  const bool vec = (((uintptr_t)out | (uintptr_t)in) & 15u) == 0 && s.n % V == 0;
+  unsigned logv = 0;
+  if (vec) while ((1u << logv) < (unsigned)V) ++logv;
+  const size_t total = (batch * s.n) >> logv;
+  size_t blocks = (total + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  const ModConst<T> *mc = (const ModConst<T> *)t.mc;
+  const unsigned mode = centred ? 1u : 0u;
+  const dim3 g((unsigned)blocks);
+  if (vec) baseconv_pick<T, V>(g, st, out, in, mc, rec, (unsigned)s.logn, (unsigned)inm, (unsigned)onm, 0u, (unsigned)ks, (unsigned)d0, (unsigned)kd, mode, total);
+  else baseconv_pick<T, 1>(g, st, out, in, mc, rec, (unsigned)s.logn, (unsigned)inm, (unsigned)onm, 0u, (unsigned)ks, (unsigned)d0, (unsigned)kd, mode, total);
+  return hipGetLastError();
+}
+template hipError_t launch_baseconv_rows<uint16_t>(const Shape &, const DevTables &, uint16_t *, size_t, const uint16_t *, size_t, const uint64_t *, size_t, size_t, size_t, size_t, int, hipStream_t);
+template hipError_t launch_baseconv_rows<uint32_t>(const Shape &, const DevTables &, uint32_t *, size_t, const uint32_t *, size_t, const uint64_t *, size_t, size_t, size_t, size_t, int, hipStream_t);
+template hipError_t launch_baseconv_rows<uint64_t>(const Shape &, const DevTables &, uint64_t *, size_t, const uint64_t *, size_t, const uint64_t *, size_t, size_t, size_t, size_t, int, hipStream_t);
+
 __global__ void k_warm_baseconv() {}
 hipError_t warm_baseconv(hipStream_t st) {
   hipLaunchKernelGGL(k_warm_baseconv, dim3(1), dim3(64), 0, st);

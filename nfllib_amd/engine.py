@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
+from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -324,6 +324,49 @@ class Engine:
         batch = self._hb(a)
         out = np.empty((batch, max(self.nmoduli - k, 0), self.degree), dtype=self.np_dtype)
         self._chk(self.lib.nflhip_moddown(self.ctx, _vp(out), _vp(a), batch, k, MODDOWN_FLOOR if floor else 0))
+        return out
+
+    # ---- the same on NTT-form data (include/nflhip.h "RNS base conversion and mod-down, NTT form") ----
+    _BCN_PLAN = {None: 0, "composed": BASECONV_NTT_COMPOSED, "fused": BASECONV_NTT_FUSED}
+
+    def baseconv_ntt(self, a, src, dst, centered=False, out=None, plan=None, stream=None):
+        """baseconv on the NTT-form batch a: every written row is the forward transform of what baseconv writes for the
+        coefficient form of a.  out=None works in place on a; plan="fused" / "composed" forces the one-launch kernel / the composed
+        plan.  The first call for a pair of ranges (and, composed, for a larger batch) allocates: make it before a graph capture."""
+        out = a if out is None else out
+        flags = (BASECONV_CENTERED if centered else 0) | self._BCN_PLAN[plan]
+        self._chk(self.lib.nflhip_baseconv_ntt_dev(self.ctx, _vp(out), _vp(a), self._batch(a), src[0], src[1], dst[0], dst[1], flags,
+                                                   self._stream(stream)))
+        return out
+
+    def mod_up_ntt(self, a, src, centered=False, plan=None, stream=None):
+        """baseconv_ntt from rows src = (first, count) to every row, in place (the source rows keep their words)"""
+        return self.baseconv_ntt(a, src, (0, self.nmoduli), centered=centered, plan=plan, stream=stream)
+
+    def mod_down_ntt(self, a, k, floor=False, out=None, plan=None, stream=None):
+        """mod_down on the NTT-form batch a: [batch, nm, n] -> a new [batch, nm - k, n] tensor (or `out`, which must not overlap a),
+        NTT form in the layout of Engine(limb_bits, degree, nm - k)"""
+        batch = self._batch(a)
+        if out is None:
+            out = _torch().empty((batch, max(self.nmoduli - k, 0), self.degree), dtype=self.torch_dtype, device=a.device)
+        flags = (MODDOWN_FLOOR if floor else 0) | self._BCN_PLAN[plan]
+        self._chk(self.lib.nflhip_moddown_ntt_dev(self.ctx, _vp(out), _vp(a), batch, k, flags, self._stream(stream)))
+        return out
+
+    def h_baseconv_ntt(self, a, src, dst, centered=False, plan=None):
+        """host-pointer variant: a numpy NTT-form [batch, nm, n] batch -> a new one with rows dst converted from rows src"""
+        a = np.ascontiguousarray(a, dtype=self.np_dtype)
+        out = np.empty_like(a)
+        self._chk(self.lib.nflhip_baseconv_ntt(self.ctx, _vp(out), _vp(a), self._hb(a), src[0], src[1], dst[0], dst[1],
+                                               (BASECONV_CENTERED if centered else 0) | self._BCN_PLAN[plan]))
+        return out
+
+    def h_mod_down_ntt(self, a, k, floor=False, plan=None):
+        """host-pointer variant: a numpy NTT-form [batch, nm, n] batch -> [batch, nm - k, n]"""
+        a = np.ascontiguousarray(a, dtype=self.np_dtype)
+        batch = self._hb(a)
+        out = np.empty((batch, max(self.nmoduli - k, 0), self.degree), dtype=self.np_dtype)
+        self._chk(self.lib.nflhip_moddown_ntt(self.ctx, _vp(out), _vp(a), batch, k, (MODDOWN_FLOOR if floor else 0) | self._BCN_PLAN[plan]))
         return out
 
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
