@@ -171,6 +171,28 @@ template <class P> class device_batch {
     else detail::check(src.ctx(), nflhip_moddown_dev(src.ctx(), d_, src.data(), n_, Q::nmoduli - P::nmoduli, flags, src.queue()), "mod_down");
     src.sync();
   }
+  // Hybrid key switch in NTT form (include/nflhip.h "hybrid key switching"): out0, out1 and src are batches of this ring (L
+  // moduli) of one size, key a batch of the ring with M > L moduli holding the 2 dnum key polynomials in [term][component] order,
+  // shared by the whole batch; K = M - L special moduli, dnum = ceil(L / alpha).  Streams as in assign_mod_down: this ring's work
+  // is awaited, the launches go on the key ring's stream, and the call returns once they have finished there.
+  template <class Q>
+  static void assign_key_switch(device_batch &out0, device_batch &out1, const device_batch &src, const device_batch<Q> &key, size_t alpha,
+                                bool centered = false, bool floor = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && Q::nmoduli > P::nmoduli,
+                  "assign_key_switch: the key's ring has the same limbs and degree and at least one modulus more");
+    if (alpha == 0 || alpha > P::nmoduli) throw std::runtime_error("nfl(hip): key_switch: alpha is out of range (1 to the input's moduli)");
+    if (out0.size() != src.size() || out1.size() != src.size()) throw std::runtime_error("nfl(hip): batch sizes differ");
+    if (key.size() != 2 * ((P::nmoduli + alpha - 1) / alpha)) throw std::runtime_error("nfl(hip): the key batch holds 2 * dnum polynomials");
+    if (out0.device() != key.device() || out1.device() != key.device() || src.device() != key.device())
+      throw std::runtime_error("nfl(hip): key_switch operands on different devices");
+    src.sync();
+    src.strict("key_switch");
+    key.strict("key_switch");
+    const int flags = (centered ? NFLHIP_KEYSWITCH_CENTERED : 0) | (floor ? NFLHIP_KEYSWITCH_FLOOR : 0);
+    detail::check(key.ctx(), nflhip_keyswitch_ntt_dev(key.ctx(), out0.d_, out1.d_, src.d_, key.data(), src.n_, Q::nmoduli - P::nmoduli, alpha, flags,
+                                                      key.queue()), "key_switch_ntt");
+    key.sync();
+  }
   // Sums of products across polynomials (include/nflhip.h): this batch holds `groups` polynomials, a and b groups * terms each,
   // term-minor: (*this)[g] = sum_j a[g * terms + j] * b[g * terms + j].  assign_matvec: v holds the `terms` polynomials every
   // group shares, (*this)[g] = sum_j m[g * terms + j] * v[j].  The operands must be other batches.

@@ -302,6 +302,45 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out._p = dst;
   }
 
+  // Hybrid key switch (nfl::key_switch_ntt below).  This ring type is the KEY's (NbModuli moduli, the last NbModuli - LO special);
+  // in, out0 and out1 live in the ring with LO moduli.  The 2 dnum key polynomials, [term][component], are gathered into one
+  // contiguous device buffer of this ring's context.  Both rings' queues run first, the other ring's stream is awaited (the input's
+  // pending work, earlier users of the pooled output buffers), the launches go on THIS ring's stream and the call returns once they
+  // have finished there -- the ordering of mod_down_into.  The results get payloads of their own: an output may be `in`, and
+  // copy-on-write sharers of the outputs' old values keep them.  Never fused into a queue's rewrites.
+  template <size_t LO> static void key_switch_into(poly_p<T, Degree, LO> &out0, poly_p<T, Degree, LO> &out1, poly_p<T, Degree, LO> const &in,
+                                                   poly_p const *key, size_t alpha, bool centered, bool floor) {
+    static_assert(LO >= 1 && LO < NbModuli, "nfl::key_switch_ntt: the key's ring has at least one special modulus more than the input's");
+    typedef poly_p<T, Degree, LO> out_t;
+    if (alpha == 0 || alpha > LO) throw std::runtime_error("nfl(hip): key_switch_ntt: alpha is out of range (1 to the input's moduli)");
+    const size_t dnum = (LO + alpha - 1) / alpha, pb = sizeof(T) * Degree * NbModuli;
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    typename out_t::ptr_type src = in._p;  // (holds the input while the launches are enqueued)
+    typename out_t::ptr_type d0 = out_t::fresh(), d1 = out_t::fresh();
+    std::vector<ptr_type> held;  // (and the key's payloads)
+    for (size_t t = 0; t < 2 * dnum; ++t) held.push_back(key[t]._p);
+    const void *s = src->dev_ro();
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo(), *kbuf = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &kbuf, 2 * dnum * pb), "key_switch_ntt");
+    int rc = NFLHIP_OK;
+    for (size_t t = 0; t < 2 * dnum && rc == NFLHIP_OK; ++t)
+      rc = nflhip_memcpy_d2d(ctx_t::get(), static_cast<char *>(kbuf) + t * pb, held[t]->dev_ro(), pb, ctx_t::queue());
+    if (rc == NFLHIP_OK) rc = nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue());
+    const int flags = (centered ? NFLHIP_KEYSWITCH_CENTERED : 0) | (floor ? NFLHIP_KEYSWITCH_FLOOR : 0);
+    if (rc == NFLHIP_OK) rc = nflhip_keyswitch_ntt_dev(ctx_t::get(), o0, o1, s, kbuf, 1, NbModuli - LO, alpha, flags, ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered key goes)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), kbuf);
+      throw std::runtime_error("nfl(hip): key_switch_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), kbuf);
+    detail::check(ctx_t::get(), rs, "key_switch_ntt");
+    out0._p = d0;
+    out1._p = d1;
+  }
+
   // Sum of products (nfl::dot / nfl::dot_add below): the deferred queue of this ring type runs first (on the caller), then the
   // pointer form of the entry on the queue's stream, 16 terms per launch, chained through the addend.  The result gets a
   // payload of its own, so `out` may be one of the inputs and copy-on-write sharers of out's old value keep it.
@@ -514,6 +553,36 @@ template <class T, size_t D, size_t MO, size_t MI> void mod_down_ntt(poly<T, D, 
 }
 template <class T, size_t D, size_t MO, size_t MI> void mod_down_ntt(poly_p<T, D, MO> &out, poly_p<T, D, MI> const &in, bool floor = false) {
   poly_p<T, D, MI>::template mod_down_into<MO>(out, in, floor, true);
+}
+
+/* Hybrid key switching in NTT form (include/nflhip.h "hybrid key switching"): in, out0, out1 in the ring with L moduli, the key in
+ * the ring with M > L moduli whose last K = M - L are the special ones; `key` is an array of 2 dnum polynomials in [term][component]
+ * order (key[2 d] and key[2 d + 1] belong to digit d), dnum = ceil(L / alpha).  (out0, out1) = the mod-down of sum_d modup(digit d of
+ * in) * key[d][c]: one call instead of base_convert_ntt per digit, dot twice and mod_down_ntt twice, with the same words.  An output
+ * may be `in`.  On poly the staged host entry; on poly_p the key is gathered into one device buffer and the queues and streams of the
+ * two ring types are ordered as nfl::mod_down_ntt orders them. */
+template <class T, size_t D, size_t L, size_t M>
+void key_switch_ntt(poly<T, D, L> &out0, poly<T, D, L> &out1, poly<T, D, L> const &in, poly<T, D, M> const *key, size_t alpha, bool centered = false,
+                    bool floor = false) {
+  static_assert(L >= 1 && L < M, "nfl::key_switch_ntt: the key's ring has at least one special modulus more than the input's");
+  typedef poly<T, D, L> S;
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  S *t0 = S::make_temp(), *t1 = S::make_temp();  // (an output may be `in`)
+  const int flags = (centered ? NFLHIP_KEYSWITCH_CENTERED : 0) | (floor ? NFLHIP_KEYSWITCH_FLOOR : 0);
+  const int rc = nflhip_keyswitch_ntt(P::ctx(), t0->data(), t1->data(), in.cdata(), key->cdata(), 1, M - L, alpha, flags);
+  if (rc == 0) {
+    std::memcpy(static_cast<void *>(out0.data()), t0->cdata(), sizeof(S));
+    std::memcpy(static_cast<void *>(out1.data()), t1->cdata(), sizeof(S));
+  }
+  S::drop_temp(t0);
+  S::drop_temp(t1);
+  detail::check(P::ctx(), rc, "key_switch_ntt");
+}
+template <class T, size_t D, size_t L, size_t M>
+void key_switch_ntt(poly_p<T, D, L> &out0, poly_p<T, D, L> &out1, poly_p<T, D, L> const &in, poly_p<T, D, M> const *key, size_t alpha,
+                    bool centered = false, bool floor = false) {
+  poly_p<T, D, M>::template key_switch_into<L>(out0, out1, in, key, alpha, centered, floor);
 }
 
 /* Sums of products across polynomials (include/nflhip.h): out = sum_{j < terms} a[j] * b[j], element-wise in every row -- the

@@ -345,6 +345,49 @@ int nflhip_baseconv_ntt(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t b
 int nflhip_moddown_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t k, int flags, void *stream);
 int nflhip_moddown_ntt(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t k, int flags);   /* staged host variant */
 
+/* ---- hybrid (RNS-digit) key switching, NTT form -------------------------------------------------
+ * The whole key switch around the entries above as ONE call: mod-up of every digit, the two inner products against the key, the
+ * mod-down of both sums.  The context has nm = nmoduli moduli of which the LAST k_special are the special ones, 1 <= k_special <=
+ * nm - 1; L = nm - k_special.  The digits are contiguous groups of alpha rows of the first L rows, 1 <= alpha <= L:
+ * dnum = ceil(L / alpha) (nflhip_keyswitch_digits), S_d = [d alpha, min((d + 1) alpha, L)) -- the last digit may be short.
+ *   in           [batch][L][degree], NTT form, the dense layout of the context over the first L moduli (what nflhip_moddown_ntt_dev returns)
+ *   key          [dnum][2][nmoduli][degree], NTT form over the full context, shared by the batch ([term][component])
+ *   out0, out1   [batch][L][degree], NTT form
+ * Definition, word for word: X = in embedded into the first L rows of an nm-row polynomial;
+ *     U_d   = nflhip_baseconv_ntt_dev(X, s0 = d alpha, ks = |S_d|, d0 = 0, kd = nm)       fast, or centred with NFLHIP_KEYSWITCH_CENTERED
+ *     acc_c = sum_d U_d (.) key[d][c]   row by row mod p_j                                what nflhip_dot_dev gives
+ *     out_c = nflhip_moddown_ntt_dev(acc_c, k_special)                                    rounding, or NFLHIP_KEYSWITCH_FLOOR
+ * including the centred band and the rescale-band behaviour of those entries: no new rounding rule.  Three plans give the same
+ * words, each the others' cross-check; `flags` may carry at most one plan flag:
+ *   NFLHIP_KEYSWITCH_SEQUENCE  the definition itself, run through the entries above over context-owned scratch: dnum base
+ *                              conversions, two inner products, one mod-down of 2 batch polynomials.  No kernel of its own.
+ *   NFLHIP_KEYSWITCH_COMPOSED  ONE inverse transform over the L rows, one streaming pass that writes every row of every U_d in
+ *                              coefficient form, one forward transform over batch dnum polynomials, then the inner products and
+ *                              the mod-down as above.  Every shape.
+ *   NFLHIP_KEYSWITCH_FUSED     ONE launch up to the two sums: a workgroup per polynomial keeps the L inverse-transformed rows and
+ *                              one work row in LDS and accumulates both components in registers; then the mod-down.  It needs
+ *                                  (L + 1) * degree * (limb_bits / 8) [+ 2 * dnum * degree, centred] <= 65536 bytes
+ *                              and rows of at most 2048 words; beyond that the flag gives NFLHIP_ERR_UNSUPPORTED.
+ *   none                       the one-launch kernel where it fits (not for contexts created under NFLHIP_VARIANT=hipcc); past it the
+ *                              composed plan for rows above 2048 words, the sequence for shorter ones.
+ * The first call for a (k_special, alpha), or for a larger batch, builds tables and allocates scratch (it synchronises): make it
+ * before capturing into a hipGraph; while capturing it is NFLHIP_ERR_UNSUPPORTED and the stream stays usable.  Calls on different
+ * streams are ordered on the scratch by an event; a replaying graph must not run concurrently with other key switches of the context.
+ * NFLHIP_ERR_INVALID, nothing enqueued: a NULL context, a NULL pointer with batch != 0, k_special or alpha out of range, unknown
+ * flag bits or two plan flags, a size that overflows size_t, any overlap among out0, out1, in and key, a cyclic row context, a
+ * repeated modulus inside a digit or among the special rows.  batch == 0 returns NFLHIP_OK and touches nothing.
+ * The host variant stages in, key and both outputs. */
+#define NFLHIP_KEYSWITCH_CENTERED 0x100
+#define NFLHIP_KEYSWITCH_FLOOR 0x200
+#define NFLHIP_KEYSWITCH_COMPOSED 0x400
+#define NFLHIP_KEYSWITCH_FUSED 0x800
+#define NFLHIP_KEYSWITCH_SEQUENCE 0x1000
+size_t nflhip_keyswitch_digits(const nflhip_ctx *ctx, size_t k_special, size_t alpha);   /* dnum; 0 for invalid arguments */
+int nflhip_keyswitch_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_in, const void *d_key, size_t batch,
+                             size_t k_special, size_t alpha, int flags, void *stream);
+int nflhip_keyswitch_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_in, const void *h_key, size_t batch,
+                         size_t k_special, size_t alpha, int flags);   /* staged host variant */
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

@@ -27,6 +27,7 @@ DOT_MAX_POINTERS = 16
 DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED = 0x100, 0x200, 0x400
 BASECONV_CENTERED, MODDOWN_FLOOR = 0x100, 0x100
 BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED = 0x200, 0x400
+KEYSWITCH_CENTERED, KEYSWITCH_FLOOR, KEYSWITCH_COMPOSED, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE = 0x100, 0x200, 0x400, 0x800, 0x1000
 
 
 class DotOperand(C.Structure):
@@ -73,6 +74,9 @@ SYMBOLS = [
     ("nflhip_baseconv_ntt", _i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i]),
     ("nflhip_moddown_ntt_dev", _i, [_vp, _vp, _vp, _sz, _sz, _i, _vp]),
     ("nflhip_moddown_ntt", _i, [_vp, _vp, _vp, _sz, _sz, _i]),
+    ("nflhip_keyswitch_digits", _sz, [_vp, _sz, _sz]),
+    ("nflhip_keyswitch_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_keyswitch_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i]),
     ("nflhip_gadget_mul_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),

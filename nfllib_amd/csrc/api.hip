@@ -388,7 +388,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -497,6 +497,10 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
     if (ctx->bcn_scratch[k]) (void)hipFree(ctx->bcn_scratch[k]);
   for (auto &kv : ctx->bconv) (void)hipFree(kv.second);
   ctx->bconv.clear();
+  if (ctx->ev_ks) (void)hipEventDestroy(ctx->ev_ks);
+  if (ctx->ks_scratch) (void)hipFree(ctx->ks_scratch);
+  for (auto &kv : ctx->ks_recs) (void)hipFree(kv.second);
+  ctx->ks_recs.clear();
   if (ctx->hstream) (void)hipStreamDestroy(ctx->hstream);
   for (int k = 0; k < 2; ++k) {
     if (ctx->aux[k]) { (void)hipStreamSynchronize(ctx->aux[k]); (void)hipStreamDestroy(ctx->aux[k]); }
@@ -1048,6 +1052,154 @@ int nflhip_moddown_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_
   int rc = baseconv_ntt_check(ctx, d_out, d_in, batch, kept, k, 0, kept, flags, true);  // in full, before any device use
   if (rc) return rc;
   return baseconv_ntt_run(ctx, d_out, d_in, batch, kept, k, 0, kept, flags, !(flags & NFLHIP_MODDOWN_FLOOR), true, (hipStream_t)stream);
+}
+
+// Hybrid key switching in NTT form (kernels_keyswitch.hip; include/nflhip.h "hybrid key switching"): the mod-up of every digit, the
+// two inner products against the key and the mod-down of both sums, defined as the composition of nflhip_baseconv_ntt_dev,
+// nflhip_dot_dev and nflhip_moddown_ntt_dev.  Three plans with the same words:
+//   sequence  that composition itself over context-owned scratch: X = the input embedded in nm rows, U = [dnum][batch][nm][n]
+//   composed  one inverse transform of the child context over rows [0, L), k_modup_digits into U = [batch][dnum][nm][n], one forward
+//             transform of the context over batch dnum polynomials
+//   fused     k_modup_dot_fused straight to the sums
+// then (sequence, composed) nflhip_dot_dev twice into acc = [2][batch][nm][n] and, for all, nflhip_moddown_ntt_dev -- one call of
+// 2 batch polynomials when out1 follows out0 in memory (Engine.key_switch_ntt allocates them so), else one per output.
+// The records are those of baseconv_record: every digit's and the mod-down's are built BEFORE anything is enqueued, so a repeated
+// modulus is refused with the builder's message and nothing written.
+static int keyswitch_records(nflhip_ctx *ctx, size_t K, size_t alpha, hipStream_t st, const uint64_t *const **recs) {  // under ks_mu
+  const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha;
+  std::vector<const uint64_t *> h(dnum);
+  const uint64_t *down = nullptr;
+  int rc = NFLHIP_OK;
+  for (size_t d = 0; d < dnum && !rc; ++d) rc = baseconv_record(ctx, d * alpha, std::min(alpha, L - d * alpha), 0, nm, false, st, &h[d]);
+  if (!rc) rc = baseconv_record(ctx, L, K, 0, L, true, st, &down);
+  if (rc) return rc;
+  const std::array<size_t, 2> key = {K, alpha};
+  auto it = ctx->ks_recs.find(key);
+  if (it == ctx->ks_recs.end()) {
+    if (is_capturing(st))
+      return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "keyswitch: the first call for a (k_special, alpha) uploads its tables, which a stream capture cannot do");
+    if ((rc = set_device(ctx))) return rc;
+    void *d = nullptr;
+    HIPCHK(ctx, hipMalloc(&d, dnum * sizeof(uint64_t *)));
+    hipError_t e = hipMemcpy(d, h.data(), dnum * sizeof(uint64_t *), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      return hipfail(ctx, e, "keyswitch: table upload");
+    }
+    it = ctx->ks_recs.emplace(key, d).first;
+  }
+  *recs = (const uint64_t *const *)it->second;
+  return NFLHIP_OK;
+}
+// Which plan serves by default.  Measured against the sequence in one run, alternated (profiles/r14_keyswitch.txt),
+// sequence / plan: the one-launch kernel x1.11 / x1.10 at u64/1024/4 (alpha 1 / 3) and x1.05 at u64/2048/4; the composed plan x0.84 /
+// x0.93 / x0.88 at those points -- the LDS transforms of the sequence's one-launch conversions beat its separate passes -- but x1.02 /
+// x1.04 / x1.02 at u64/4096/4 (K 1 / 2) and u32/4096/3, where the sequence composes as well and the composed plan saves dnum - 1
+// inverse transforms; every block of the run within 1.1 % of its median.  So: the one-launch kernel where it fits; past it the
+// composed plan for rows above 2048 words and the sequence for shorter ones, where the composed plan measured slower.
+static int keyswitch_default_plan(const nflhip_ctx *ctx, size_t L, size_t dnum, bool centred) {
+  if (!ctx->shape.compiled_only && keyswitch_fused_fits(L, dnum, ctx->shape.n, ctx->word, centred)) return NFLHIP_KEYSWITCH_FUSED;
+  return ctx->shape.n > 2048 ? NFLHIP_KEYSWITCH_COMPOSED : NFLHIP_KEYSWITCH_SEQUENCE;
+}
+static int keyswitch_run(nflhip_ctx *ctx, void *out0, void *out1, const void *in, const void *key, size_t batch, size_t K, size_t alpha, int flags,
+                         hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->ks_mu);
+  const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha, row = ctx->shape.n * ctx->word, pb = nm * row;
+  const bool centred = (flags & NFLHIP_KEYSWITCH_CENTERED) != 0, floor = (flags & NFLHIP_KEYSWITCH_FLOOR) != 0, cap = is_capturing(st);
+  const uint64_t *const *recs = nullptr;
+  int rc;
+  try {
+    rc = keyswitch_records(ctx, K, alpha, st, &recs);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+  }
+  if (rc) return rc;
+  int plan = flags & (NFLHIP_KEYSWITCH_COMPOSED | NFLHIP_KEYSWITCH_FUSED | NFLHIP_KEYSWITCH_SEQUENCE);
+  if (plan == NFLHIP_KEYSWITCH_FUSED && !keyswitch_fused_fits(L, dnum, ctx->shape.n, ctx->word, centred))
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "keyswitch: the rows of this call do not fit the one-launch kernel's LDS");
+  if (!plan) plan = keyswitch_default_plan(ctx, L, dnum, centred);
+  // what a call while capturing may do: repeat a (k_special, alpha, plan, modes) already served at this batch or a larger one
+  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | (flags & (NFLHIP_KEYSWITCH_CENTERED | NFLHIP_KEYSWITCH_FLOOR)))};
+  auto wit = ctx->ks_warm.find(wkey);
+  if (cap && (wit == ctx->ks_warm.end() || wit->second < batch))
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "keyswitch: the first call for a (k_special, alpha, plan), or for a larger batch, allocates, which a stream capture cannot do");
+  const size_t xb = plan == NFLHIP_KEYSWITCH_SEQUENCE ? batch * pb : plan == NFLHIP_KEYSWITCH_COMPOSED ? batch * L * row : 0;
+  const size_t ub = plan == NFLHIP_KEYSWITCH_FUSED ? 0 : batch * dnum * pb, ab = 2 * batch * pb, need = xb + ub + ab;
+  if ((rc = set_device(ctx))) return rc;
+  nflhip_ctx *child = nullptr;
+  if (plan == NFLHIP_KEYSWITCH_COMPOSED) {
+    std::lock_guard<std::mutex> l2(ctx->bcn_mu);
+    if ((rc = bcn_child(ctx, 0, L, cap, &child))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+  }
+  if (ctx->ks_scratch_bytes < need) {
+    if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "keyswitch: the scratch has to grow, which a stream capture cannot do");
+    if (ctx->ks_scratch) HIPCHK(ctx, hipFree(ctx->ks_scratch));  // (synchronises: nothing still reads it)
+    ctx->ks_scratch = nullptr;
+    ctx->ks_scratch_bytes = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->ks_scratch, need));
+    ctx->ks_scratch_bytes = need;
+  }
+  if (!ctx->ev_ks) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_ks, hipEventDisableTiming));
+  if (!cap && ctx->ev_ks_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_ks, 0));  // a previous call on another stream
+  char *X = (char *)ctx->ks_scratch, *U = X + xb, *acc = U + ub;
+  const int bcflags = centred ? NFLHIP_BASECONV_CENTERED : 0;
+  hipError_t e = hipSuccess;
+  if (plan == NFLHIP_KEYSWITCH_FUSED) {
+    e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_modup_dot_fused<T>(ctx->shape, ctx->tabs, (T *)acc, (const T *)in, (const T *)key, recs, batch, L, alpha, centred, st);
+    });
+    if (e == hipErrorNotSupported) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "keyswitch: the rows of this call do not fit the one-launch kernel's LDS");
+    if (e != hipSuccess) return hipfail(ctx, e, "keyswitch (fused)");
+  } else {
+    nflhip_dot_operand a;
+    if (plan == NFLHIP_KEYSWITCH_SEQUENCE) {
+      HIPCHK(ctx, hipMemcpy2DAsync(X, pb, in, L * row, L * row, batch, hipMemcpyDeviceToDevice, st));
+      for (size_t d = 0; d < dnum; ++d)
+        if ((rc = nflhip_baseconv_ntt_dev(ctx, U + d * batch * pb, X, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm, bcflags, st))) return rc;
+      a = {U, 1, batch};
+    } else {
+      HIPCHK(ctx, hipMemcpyAsync(X, in, batch * L * row, hipMemcpyDeviceToDevice, st));
+      if ((rc = nflhip_ntt_inv_dev(child, X, batch, st)) || (rc = set_device(ctx))) return rc;
+      e = with_limb(ctx, [&](auto z) {
+        typedef decltype(z) T;
+        return launch_modup_digits<T>(ctx->shape, ctx->tabs, (T *)U, (const T *)X, recs, batch, L, alpha, centred, st);
+      });
+      if (e != hipSuccess) return hipfail(ctx, e, "keyswitch: mod-up");
+      if ((rc = nflhip_ntt_fwd_dev(ctx, U, batch * dnum, st))) return rc;
+      a = {U, dnum, 1};
+    }
+    for (size_t c = 0; c < 2; ++c) {
+      const nflhip_dot_operand b = {(const char *)key + c * pb, 0, 2};
+      if ((rc = nflhip_dot_dev(ctx, acc + c * batch * pb, &a, &b, nullptr, batch, dnum, 0, st))) return rc;
+    }
+  }
+  const int mdflags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
+  if ((char *)out1 == (char *)out0 + batch * L * row) {
+    rc = nflhip_moddown_ntt_dev(ctx, out0, acc, 2 * batch, K, mdflags, st);
+  } else {
+    rc = nflhip_moddown_ntt_dev(ctx, out0, acc, batch, K, mdflags, st);
+    if (!rc) rc = nflhip_moddown_ntt_dev(ctx, out1, acc + batch * pb, batch, K, mdflags, st);
+  }
+  if (rc || (rc = set_device(ctx))) return rc;
+  if (!cap) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev_ks, st));
+    ctx->ev_ks_valid = true;
+    try {
+      size_t &w = ctx->ks_warm[wkey];
+      if (w < batch) w = batch;
+    } catch (const std::bad_alloc &) {
+    }
+  }
+  return NFLHIP_OK;
+}
+size_t nflhip_keyswitch_digits(const nflhip_ctx *ctx, size_t k_special, size_t alpha) { return keyswitch_digits(ctx, k_special, alpha); }
+int nflhip_keyswitch_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_in, const void *d_key, size_t batch, size_t k_special,
+                             size_t alpha, int flags, void *stream) {
+  int rc = keyswitch_check(ctx, d_out0, d_out1, d_in, d_key, batch, k_special, alpha, flags);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  return keyswitch_run(ctx, d_out0, d_out1, d_in, d_key, batch, k_special, alpha, flags, (hipStream_t)stream);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

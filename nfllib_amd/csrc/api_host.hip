@@ -440,6 +440,32 @@ int nflhip_moddown_ntt(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t ba
   });
 }
 
+// hybrid key switching: in, the key and both outputs are staged whole (the outputs share one slot, out1 behind out0, so that the
+// mod-down runs as one batch)
+int nflhip_keyswitch_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_in, const void *h_key, size_t batch, size_t k_special,
+                         size_t alpha, int flags) {
+  int rc = keyswitch_check(ctx, h_out0, h_out1, h_in, h_key, batch, k_special, alpha, flags);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * (nm - k_special) * row;
+  const size_t kb = 2 * keyswitch_digits(ctx, k_special, alpha) * nm * row;
+  Staged s(ctx);
+  if ((rc = s.in(0, h_in, ob)) || (rc = s.in(1, h_key, kb)) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
+  char *o = (char *)ctx->stage[2];
+  if ((rc = nflhip_keyswitch_ntt_dev(ctx, o, o + ob, ctx->stage[0], ctx->stage[1], batch, k_special, alpha, flags, (void *)ctx->hstream))) return rc;
+  if (!ctx->stage_host[2]) {
+    HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out1, o + ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
+  s.pending = false;
+  if (ctx->stage_host[2]) {
+    std::memcpy(h_out0, o, ob);
+    std::memcpy(h_out1, o + ob, ob);
+  }
+  return NFLHIP_OK;
+}
+
 // sums of products across polynomials: the operands are `terms` times the size of the result, so the call is staged whole
 int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, size_t groups, size_t terms, int b_shared) {
   if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");

@@ -84,6 +84,16 @@ struct nflhip_ctx {
   size_t bcn_scratch_bytes[2] = {0, 0};
   hipEvent_t ev_bcn = nullptr;
   bool ev_bcn_valid = false;
+  // hybrid key switching (api.hip keyswitch_run): per (k_special, alpha) the device array of its digits' record pointers; per
+  // (k_special, alpha, plan) the largest batch served so far (what a call while capturing may repeat); one scratch for the embedded /
+  // inverse-transformed input, the mod-upped digits and the two sums, calls ordered on it by ev_ks.  All under ks_mu.
+  std::mutex ks_mu;
+  std::map<std::array<size_t, 2>, void *> ks_recs;
+  std::map<std::array<size_t, 3>, size_t> ks_warm;
+  void *ks_scratch = nullptr;
+  size_t ks_scratch_bytes = 0;
+  hipEvent_t ev_ks = nullptr;
+  bool ev_ks_valid = false;
 };
 
 void pipe_destroy(nflhip_ctx *ctx);  // api_host.hip: frees the context's host-pointer pipeline
@@ -240,6 +250,40 @@ inline int baseconv_ntt_check(const nflhip_ctx *ctx, const void *out, const void
   if (plan == (NFLHIP_BASECONV_NTT_COMPOSED | NFLHIP_BASECONV_NTT_FUSED))
     return fail(ctx, NFLHIP_ERR_INVALID, moddown ? "moddown_ntt: one plan flag at most" : "baseconv_ntt: one plan flag at most");
   return baseconv_check(ctx, out, in, batch, s0, ks, d0, kd, flags & ~plan, moddown);
+}
+// nflhip_keyswitch_ntt_dev / nflhip_keyswitch_ntt: every argument check short of the tables (a repeated modulus is found by their
+// builder, api.hip keyswitch_records), before any device use
+inline size_t keyswitch_digits(const nflhip_ctx *ctx, size_t k_special, size_t alpha) {
+  if (!ctx || ctx->cyclic) return 0;
+  const size_t nm = ctx->shape.nm;
+  if (k_special == 0 || k_special >= nm || alpha == 0 || alpha > nm - k_special) return 0;
+  return (nm - k_special + alpha - 1) / alpha;
+}
+inline int keyswitch_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *in, const void *key, size_t batch,
+                           size_t k_special, size_t alpha, int flags) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: a cyclic row context has no modulus chain");
+  const int plans = NFLHIP_KEYSWITCH_COMPOSED | NFLHIP_KEYSWITCH_FUSED | NFLHIP_KEYSWITCH_SEQUENCE, plan = flags & plans;
+  if (flags & ~(plans | NFLHIP_KEYSWITCH_CENTERED | NFLHIP_KEYSWITCH_FLOOR)) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: unknown flag bits");
+  if (plan & (plan - 1)) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: one plan flag at most");
+  const size_t nm = ctx->shape.nm, dnum = keyswitch_digits(ctx, k_special, alpha);
+  if (k_special == 0 || k_special >= nm) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: k_special is out of range (1 to nmoduli - 1)");
+  if (dnum == 0) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: alpha is out of range (1 to nmoduli - k_special)");
+  if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: more than 65535 rows");
+  if (batch == 0) return NFLHIP_OK;
+  if (!out0 || !out1 || !in || !key) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t row = ctx->shape.n * ctx->word, L = nm - k_special;
+  size_t ob, sb, kb, polys;
+  // (sb: the largest scratch of any plan -- the embedded input, the digits and the two sums, [batch][1 + dnum + 2][nm][n])
+  if (__builtin_mul_overflow(batch, L * row, &ob) || __builtin_mul_overflow(batch, dnum + 3, &polys) || __builtin_mul_overflow(polys, nm * row, &sb) ||
+      __builtin_mul_overflow(2 * dnum, nm * row, &kb))
+    return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: the size overflows");
+  const void *const ptr[4] = {out0, out1, in, key};
+  const size_t len[4] = {ob, ob, ob, kb};
+  for (int a = 0; a < 4; ++a)
+    for (int b = a + 1; b < 4; ++b)
+      if (ranges_overlap(ptr[a], len[a], ptr[b], len[b])) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: out0, out1, in and key may not overlap");
+  return NFLHIP_OK;
 }
 constexpr size_t kStageHostMax = (size_t)1 << 20;
 inline void free_stage(nflhip_ctx *ctx, int slot) {

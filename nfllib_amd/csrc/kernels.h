@@ -148,6 +148,25 @@ hipError_t launch_baseconv_ntt_fused(const Shape &s, const DevTables &t, T *out,
                                      size_t ks, size_t d0, size_t kd, int centred, int moddown, hipStream_t st);
 template <typename T>
 hipError_t launch_moddown_ntt_combine(const Shape &s, T *out, const T *in, const uint64_t *rec, size_t batch, size_t k, hipStream_t st);
+// hybrid key switching, NTT form (kernels_keyswitch.hip; include/nflhip.h "hybrid key switching"): the mod-up of EVERY digit in one
+// streaming pass.  in = [batch][L][n] coefficient form (the inverse-transformed input), digits of alpha rows (the last may be short),
+// dnum = ceil(L / alpha); out = [batch][dnum][nm][n]: polynomial (b, d) holds the conversion of digit d to every row of the context,
+// rows of the digit itself as the input has them.  recs: device array of the dnum device records of (d alpha, |S_d|) -> (0, nm).
+// out never is in (api.hip: both are context-owned scratch).
+template <typename T>
+hipError_t launch_modup_digits(const Shape &s, const DevTables &t, T *out, const T *in, const uint64_t *const *recs, size_t batch, size_t L,
+                               size_t alpha, int centred, hipStream_t st);
+// the one-launch plan up to the two sums: in = [batch][L][n] NTT form, key = [dnum][2][nm][n], acc = [2][batch][nm][n] canonical
+// (acc[c][b] = sum_d U_d key[d][c]).  A workgroup per polynomial; LDS: the L source rows, one work row and, in centred mode, the
+// corrections v of every digit as 16-bit words (v <= alpha <= 1024) -- keyswitch_fused_lds.  hipErrorNotSupported beyond 64 KiB, for
+// rows above 2048 words or below 4 (keyswitch_fused_fits).
+inline size_t keyswitch_fused_lds(size_t L, size_t dnum, size_t n, size_t word, int centred) { return (L + 1) * n * word + (centred ? dnum * n * 2 : 0); }
+inline bool keyswitch_fused_fits(size_t L, size_t dnum, size_t n, size_t word, int centred) {
+  return n >= 4 && n <= 2048 && keyswitch_fused_lds(L, dnum, n, word, centred) <= kBaseconvNttLdsBytes;
+}
+template <typename T>
+hipError_t launch_modup_dot_fused(const Shape &s, const DevTables &t, T *acc, const T *in, const T *key, const uint64_t *const *recs, size_t batch,
+                                  size_t L, size_t alpha, int centred, hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);
@@ -299,6 +318,7 @@ hipError_t warm_dot(hipStream_t st);
 hipError_t warm_decompose(hipStream_t st);
 hipError_t warm_baseconv(hipStream_t st);
 hipError_t warm_baseconv_ntt(hipStream_t st);
+hipError_t warm_keyswitch(hipStream_t st);
 int polymul_level();   // 0 / 1 / 2: transforms of the coefficient-form products complete / incomplete (asm_launch.hip, nflhip_debug_polymul_level)
 hipError_t launch_polymul_pipe64k_u64(const Shape &s, const DevTables &t, uint64_t *c_v, const uint64_t *a_v,
                                       const uint64_t *b_v, int cnt_v, const uint64_t *fa_src, uint64_t *fa_dst,

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
+from ._lib import (KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -368,6 +368,51 @@ class Engine:
         out = np.empty((batch, max(self.nmoduli - k, 0), self.degree), dtype=self.np_dtype)
         self._chk(self.lib.nflhip_moddown_ntt(self.ctx, _vp(out), _vp(a), batch, k, (MODDOWN_FLOOR if floor else 0) | self._BCN_PLAN[plan]))
         return out
+
+    # ---- hybrid key switching, NTT form (include/nflhip.h "hybrid key switching") ----
+    _KS_PLAN = {None: 0, "sequence": KEYSWITCH_SEQUENCE, "composed": KEYSWITCH_COMPOSED, "fused": KEYSWITCH_FUSED}
+
+    def keyswitch_digits(self, k_special, alpha):
+        """dnum = ceil((nm - k_special) / alpha), the number of digits (and of key terms) of a key switch"""
+        dnum = self.lib.nflhip_keyswitch_digits(self.ctx, k_special, alpha)
+        if dnum == 0:
+            raise ValueError("k_special %r (1 to nm - 1) or alpha %r (1 to nm - k_special) is out of range" % (k_special, alpha))
+        return dnum
+
+    def _ks_flags(self, centered, floor, plan):
+        return (KEYSWITCH_CENTERED if centered else 0) | (KEYSWITCH_FLOOR if floor else 0) | self._KS_PLAN[plan]
+
+    def key_switch_ntt(self, a, key, k_special, alpha, centered=False, floor=False, out=None, plan=None, stream=None):
+        """the hybrid key switch of the NTT-form batch a = [batch, L, n], L = nm - k_special (the layout of Engine(limb_bits, degree, L)),
+        against key = [dnum, 2, nm, n] (NTT form over this context, shared by the batch): mod-up of every digit of alpha rows (fast,
+        or centered=True), the two sums of products, mod-down by the last k_special moduli (rounding, or floor=True).  Returns
+        (out0, out1), each [batch, L, n]; `out` = a pair of such tensors, else both are views of one new [2, batch, L, n] tensor.
+        plan "sequence" / "composed" / "fused" forces a plan.  The first call for a (k_special, alpha), or a larger batch,
+        allocates: make it before a graph capture."""
+        L = self.nmoduli - k_special
+        if L <= 0 or a.numel() % (L * self.degree) or not a.is_contiguous() or not key.is_contiguous():
+            raise ValueError("a is a contiguous [batch, nm - k_special, n] tensor")
+        batch = a.numel() // (L * self.degree)
+        if key.numel() != 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly:
+            raise ValueError("key holds dnum * 2 polynomials of this context")
+        if out is None:
+            both = _torch().empty((2, batch, L, self.degree), dtype=self.torch_dtype, device=a.device)
+            out = (both[0], both[1])
+        self._chk(self.lib.nflhip_keyswitch_ntt_dev(self.ctx, _vp(out[0]), _vp(out[1]), _vp(a), _vp(key), batch, k_special, alpha,
+                                                    self._ks_flags(centered, floor, plan), self._stream(stream)))
+        return out
+
+    def h_key_switch_ntt(self, a, key, k_special, alpha, centered=False, floor=False, plan=None):
+        """host-pointer variant: numpy a = [batch, L, n] and key = [dnum, 2, nm, n] -> (out0, out1)"""
+        a, key = np.ascontiguousarray(a, dtype=self.np_dtype), np.ascontiguousarray(key, dtype=self.np_dtype)
+        L = self.nmoduli - k_special
+        if L <= 0 or a.size % (L * self.degree) or key.size != 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly:
+            raise ValueError("a is [batch, nm - k_special, n], key [dnum, 2, nm, n]")
+        batch = a.size // (L * self.degree)
+        out0, out1 = (np.empty((batch, L, self.degree), dtype=self.np_dtype) for _ in range(2))
+        self._chk(self.lib.nflhip_keyswitch_ntt(self.ctx, _vp(out0), _vp(out1), _vp(a), _vp(key), batch, k_special, alpha,
+                                                self._ks_flags(centered, floor, plan)))
+        return out0, out1
 
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
         out = out if out is not None else _torch().empty_like(a)
