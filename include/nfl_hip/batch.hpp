@@ -193,6 +193,42 @@ template <class P> class device_batch {
                                                       key.queue()), "key_switch_ntt");
     key.sync();
   }
+  // Hoisted rotations (include/nflhip.h "hoisted rotations"): c0 (may be NULL), c1 and every out0s[m], out1s[m] are batches of this
+  // ring (L moduli) of one size; key_batches[m] is a batch of the ring with M > L moduli holding the 2 dnum polynomials of the key of
+  // rotation m in [term][component] order, shared by the whole batch; K = M - L special moduli, dnum = ceil(L / alpha); m < count
+  // <= 16.  Streams as in assign_key_switch: this ring's work is awaited, the launches go on the key ring's stream (that of
+  // key_batches[0]), and the call returns once they have finished there.
+  template <class Q>
+  static void assign_rotations(device_batch *const *out0s, device_batch *const *out1s, const device_batch *c0, const device_batch &c1,
+                               const device_batch<Q> *const *key_batches, const uint64_t *ks, size_t count, size_t alpha, bool centered = false,
+                               bool floor = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && Q::nmoduli > P::nmoduli,
+                  "assign_rotations: the keys' ring has the same limbs and degree and at least one modulus more");
+    if (alpha == 0 || alpha > P::nmoduli) throw std::runtime_error("nfl(hip): rotations: alpha is out of range (1 to the ciphertext's moduli)");
+    if (count == 0 || count > NFLHIP_ROTATE_MAX_OUTPUTS) throw std::runtime_error("nfl(hip): rotations: 1 to 16 rotations");
+    const device_batch<Q> &key0 = *key_batches[0];
+    void *o0[NFLHIP_ROTATE_MAX_OUTPUTS], *o1[NFLHIP_ROTATE_MAX_OUTPUTS];
+    const void *kp[NFLHIP_ROTATE_MAX_OUTPUTS];
+    if (c0 && c0->size() != c1.size()) throw std::runtime_error("nfl(hip): batch sizes differ");
+    if ((c0 && c0->device() != key0.device()) || c1.device() != key0.device()) throw std::runtime_error("nfl(hip): rotation operands on different devices");
+    for (size_t m = 0; m < count; ++m) {
+      if (out0s[m]->size() != c1.size() || out1s[m]->size() != c1.size()) throw std::runtime_error("nfl(hip): batch sizes differ");
+      if (key_batches[m]->size() != 2 * ((P::nmoduli + alpha - 1) / alpha)) throw std::runtime_error("nfl(hip): a key batch holds 2 * dnum polynomials");
+      if (out0s[m]->device() != key0.device() || out1s[m]->device() != key0.device() || key_batches[m]->device() != key0.device())
+        throw std::runtime_error("nfl(hip): rotation operands on different devices");
+      o0[m] = out0s[m]->d_;
+      o1[m] = out1s[m]->d_;
+      kp[m] = key_batches[m]->data();
+    }
+    c1.sync();
+    c1.strict("rotations");
+    if (c0) c0->strict("rotations");
+    for (size_t m = 0; m < count; ++m) key_batches[m]->strict("rotations");
+    const int flags = (centered ? NFLHIP_ROTATE_CENTERED : 0) | (floor ? NFLHIP_ROTATE_FLOOR : 0);
+    detail::check(key0.ctx(), nflhip_rotate_hoisted_ntt_dev(key0.ctx(), o0, o1, c0 ? c0->d_ : nullptr, c1.d_, kp, ks, count, c1.n_,
+                                                            Q::nmoduli - P::nmoduli, alpha, flags, key0.queue()), "rotate_hoisted_ntt");
+    key0.sync();
+  }
   // Sums of products across polynomials (include/nflhip.h): this batch holds `groups` polynomials, a and b groups * terms each,
   // term-minor: (*this)[g] = sum_j a[g * terms + j] * b[g * terms + j].  assign_matvec: v holds the `terms` polynomials every
   // group shares, (*this)[g] = sum_j m[g * terms + j] * v[j].  The operands must be other batches.

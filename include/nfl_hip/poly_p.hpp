@@ -341,6 +341,60 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out1._p = d1;
   }
 
+  // Hoisted rotations (nfl::rotate_hoisted_ntt below).  This ring type is the KEYS' (NbModuli moduli, the last NbModuli - LO special);
+  // c0, c1 and the outputs live in the ring with LO moduli.  keys[m] is an array of 2 dnum polynomials, [term][component]; every
+  // key is gathered into one contiguous device buffer of this ring's context, key m at polynomial m * 2 dnum.  The ordering is that
+  // of key_switch_into: both rings' queues run first, the other ring's stream is awaited, the launches go on THIS ring's stream and
+  // the call returns once they have finished there.  The results get payloads of their own: an output may be c0 or c1, and
+  // copy-on-write sharers of the outputs' old values keep them.  Never fused into a queue's rewrites.
+  template <size_t LO> static void rotate_into(poly_p<T, Degree, LO> *out0s, poly_p<T, Degree, LO> *out1s, poly_p<T, Degree, LO> const *c0,
+                                               poly_p<T, Degree, LO> const &c1, poly_p const *const *keys, const uint64_t *ks, size_t count,
+                                               size_t alpha, bool centered, bool floor) {
+    static_assert(LO >= 1 && LO < NbModuli, "nfl::rotate_hoisted_ntt: the keys' ring has at least one special modulus more than the ciphertext's");
+    typedef poly_p<T, Degree, LO> out_t;
+    if (alpha == 0 || alpha > LO) throw std::runtime_error("nfl(hip): rotate_hoisted_ntt: alpha is out of range (1 to the ciphertext's moduli)");
+    if (count == 0 || count > NFLHIP_ROTATE_MAX_OUTPUTS) throw std::runtime_error("nfl(hip): rotate_hoisted_ntt: 1 to 16 rotations");
+    const size_t dnum = (LO + alpha - 1) / alpha, pb = sizeof(T) * Degree * NbModuli, kpolys = 2 * dnum;
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    typename out_t::ptr_type s0 = c0 ? c0->_p : typename out_t::ptr_type(), s1 = c1._p;  // (hold the inputs while the launches are enqueued)
+    std::vector<typename out_t::ptr_type> d0, d1;
+    std::vector<ptr_type> held;  // (and the keys' payloads)
+    void *o0[NFLHIP_ROTATE_MAX_OUTPUTS], *o1[NFLHIP_ROTATE_MAX_OUTPUTS];
+    const void *kp[NFLHIP_ROTATE_MAX_OUTPUTS];
+    for (size_t m = 0; m < count; ++m) {
+      d0.push_back(out_t::fresh());
+      d1.push_back(out_t::fresh());
+      o0[m] = d0[m]->dev_wo();
+      o1[m] = d1[m]->dev_wo();
+      for (size_t t = 0; t < kpolys; ++t) held.push_back(keys[m][t]._p);
+    }
+    const void *p0 = c0 ? s0->dev_ro() : nullptr, *p1 = s1->dev_ro();
+    void *kbuf = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &kbuf, count * kpolys * pb), "rotate_hoisted_ntt");
+    int rc = NFLHIP_OK;
+    for (size_t m = 0; m < count; ++m) {
+      kp[m] = static_cast<char *>(kbuf) + m * kpolys * pb;
+      for (size_t t = 0; t < kpolys && rc == NFLHIP_OK; ++t)
+        rc = nflhip_memcpy_d2d(ctx_t::get(), static_cast<char *>(kbuf) + (m * kpolys + t) * pb, held[m * kpolys + t]->dev_ro(), pb, ctx_t::queue());
+    }
+    if (rc == NFLHIP_OK) rc = nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue());
+    const int flags = (centered ? NFLHIP_ROTATE_CENTERED : 0) | (floor ? NFLHIP_ROTATE_FLOOR : 0);
+    if (rc == NFLHIP_OK) rc = nflhip_rotate_hoisted_ntt_dev(ctx_t::get(), o0, o1, p0, p1, kp, ks, count, 1, NbModuli - LO, alpha, flags, ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered keys go)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), kbuf);
+      throw std::runtime_error("nfl(hip): rotate_hoisted_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), kbuf);
+    detail::check(ctx_t::get(), rs, "rotate_hoisted_ntt");
+    for (size_t m = 0; m < count; ++m) {
+      out0s[m]._p = d0[m];
+      out1s[m]._p = d1[m];
+    }
+  }
+
   // Sum of products (nfl::dot / nfl::dot_add below): the deferred queue of this ring type runs first (on the caller), then the
   // pointer form of the entry on the queue's stream, 16 terms per launch, chained through the addend.  The result gets a
   // payload of its own, so `out` may be one of the inputs and copy-on-write sharers of out's old value keep it.
@@ -583,6 +637,49 @@ template <class T, size_t D, size_t L, size_t M>
 void key_switch_ntt(poly_p<T, D, L> &out0, poly_p<T, D, L> &out1, poly_p<T, D, L> const &in, poly_p<T, D, M> const *key, size_t alpha,
                     bool centered = false, bool floor = false) {
   poly_p<T, D, M>::template key_switch_into<L>(out0, out1, in, key, alpha, centered, floor);
+}
+
+/* Hoisted rotations (include/nflhip.h "hoisted rotations"): the ciphertext (c0, c1) in the ring with L moduli rotated by ks[m], m <
+ * count <= 16, against keys[m] -- an array of 2 dnum polynomials in [term][component] order, dnum = ceil(L / alpha), in the ring with
+ * M > L moduli whose last K = M - L are the special ones (K is deduced from the types, as in key_switch_ntt).  For every m
+ * (out0s[m], out1s[m]) = sigma^NTT_ks[m] of (key_switch_ntt(c1, keys[m]) + (c0, 0)): one mod-up of c1 serves every rotation.  keys[m]
+ * switches from s to sigma_(ks[m]^-1)(s): the usual Galois key for ks[m] with automorphism_ntt by ks[m]^-1 applied to every polynomial.
+ * c0 may be NULL; an output may be c0 or c1.  On poly the staged host entry; on poly_p the keys are gathered into one device buffer
+ * and the queues and streams of the two ring types are ordered as nfl::key_switch_ntt orders them. */
+template <class T, size_t D, size_t L, size_t M>
+void rotate_hoisted_ntt(poly<T, D, L> *out0s, poly<T, D, L> *out1s, poly<T, D, L> const *c0, poly<T, D, L> const &c1, poly<T, D, M> const *const *keys,
+                        const uint64_t *ks, size_t count, size_t alpha, bool centered = false, bool floor = false) {
+  static_assert(L >= 1 && L < M, "nfl::rotate_hoisted_ntt: the keys' ring has at least one special modulus more than the ciphertext's");
+  typedef poly<T, D, L> S;
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  if (count == 0 || count > NFLHIP_ROTATE_MAX_OUTPUTS) throw std::runtime_error("nfl(hip): rotate_hoisted_ntt: 1 to 16 rotations");
+  S *t0[NFLHIP_ROTATE_MAX_OUTPUTS], *t1[NFLHIP_ROTATE_MAX_OUTPUTS];  // (an output may be an input)
+  void *o0[NFLHIP_ROTATE_MAX_OUTPUTS], *o1[NFLHIP_ROTATE_MAX_OUTPUTS];
+  const void *kp[NFLHIP_ROTATE_MAX_OUTPUTS];
+  for (size_t m = 0; m < count; ++m) {
+    t0[m] = S::make_temp();
+    t1[m] = S::make_temp();
+    o0[m] = t0[m]->data();
+    o1[m] = t1[m]->data();
+    kp[m] = keys[m]->cdata();
+  }
+  const int flags = (centered ? NFLHIP_ROTATE_CENTERED : 0) | (floor ? NFLHIP_ROTATE_FLOOR : 0);
+  const int rc = nflhip_rotate_hoisted_ntt(P::ctx(), o0, o1, c0 ? c0->cdata() : nullptr, c1.cdata(), kp, ks, count, 1, M - L, alpha, flags);
+  for (size_t m = 0; m < count; ++m) {
+    if (rc == 0) {
+      std::memcpy(static_cast<void *>(out0s[m].data()), t0[m]->cdata(), sizeof(S));
+      std::memcpy(static_cast<void *>(out1s[m].data()), t1[m]->cdata(), sizeof(S));
+    }
+    S::drop_temp(t0[m]);
+    S::drop_temp(t1[m]);
+  }
+  detail::check(P::ctx(), rc, "rotate_hoisted_ntt");
+}
+template <class T, size_t D, size_t L, size_t M>
+void rotate_hoisted_ntt(poly_p<T, D, L> *out0s, poly_p<T, D, L> *out1s, poly_p<T, D, L> const *c0, poly_p<T, D, L> const &c1,
+                        poly_p<T, D, M> const *const *keys, const uint64_t *ks, size_t count, size_t alpha, bool centered = false, bool floor = false) {
+  poly_p<T, D, M>::template rotate_into<L>(out0s, out1s, c0, c1, keys, ks, count, alpha, centered, floor);
 }
 
 /* Sums of products across polynomials (include/nflhip.h): out = sum_{j < terms} a[j] * b[j], element-wise in every row -- the

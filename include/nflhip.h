@@ -224,6 +224,25 @@ int nflhip_dot_ptrs_dev(nflhip_ctx *ctx, void *d_out, const void *const *d_a, co
                         const void *d_addend, void *stream);
 int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, size_t groups, size_t terms, int b_shared);   /* staged host variant */
 
+/* ---- sums of products, several outputs: a small matrix product over polynomials ---------------
+ * One first operand against `outputs` second operands, each shared by every group:
+ *     d_outs[o][g][m][i] = (sum_{j < terms} a(g,j)[m][i] * b_o(j)[m][i]) mod p_m          o < outputs <= NFLHIP_DOT_MULTI_MAX_OUTPUTS
+ * as the canonical word; b_o(j) starts j * b_term_stride polynomials after d_bs[o]; every d_outs[o] is dense
+ * [groups][nmoduli][degree].  Word for word nflhip_dot_dev(d_outs[o], a, {d_bs[o], 0, b_term_stride}, NULL, groups, terms) for
+ * every o, in ONE launch: replies to several XPIR queries, a linear layer with several output channels, the inner products of a
+ * hoisted rotation (a = the digits, b_o = a component of a Galois key).  Up to 8 terms a thread loads its words of `a` once and
+ * walks the outputs, so `a` is read once per call and b_o once per two groups; with more terms the terms are walked per output
+ * as nflhip_dot_dev does.  d_outs and d_bs are HOST arrays of device pointers, which travel to the kernel by value: nothing is
+ * allocated, no scratch, no synchronisation, and the call can be captured into a hipGraph.
+ *   flags    0, or NFLHIP_DOT_UNTILED: one group per pass instead of two -- each plan is the other's cross-check, same words.
+ * NFLHIP_ERR_INVALID, nothing enqueued: a NULL context or pointer, outputs == 0 or > 32, terms == 0 or > 2^31, unknown flag bits,
+ * an extent that overflows, an output that overlaps any byte of the extent of `a`, of ANY b_o -- the (terms - 1) * b_term_stride
+ * + 1 polynomials from d_bs[o] -- or of another output, or a cyclic row context.  The b pointers may alias each other.
+ * groups == 0 returns NFLHIP_OK and touches nothing. */
+#define NFLHIP_DOT_MULTI_MAX_OUTPUTS 32
+int nflhip_dot_multi_dev(nflhip_ctx *ctx, void *const *d_outs, const nflhip_dot_operand *a, const void *const *d_bs,
+                         size_t b_term_stride, size_t outputs, size_t groups, size_t terms, int flags, void *stream);
+
 /* ---- gadget decomposition: base-2^w digits of RNS rows ---------------------------------------
  * The first step of every key switch (relinearisation, a rotation's Galois key, an XPIR / SealPIR reply): a coefficient-form
  * polynomial is split into small "digit" polynomials whose sum of products against a key is what nflhip_dot_dev computes.
@@ -387,6 +406,58 @@ int nflhip_keyswitch_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const 
                              size_t k_special, size_t alpha, int flags, void *stream);
 int nflhip_keyswitch_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_in, const void *h_key, size_t batch,
                          size_t k_special, size_t alpha, int flags);   /* staged host variant */
+
+/* ---- hoisted rotations: one mod-up shared by many Galois key switches ---------------------------
+ * A ciphertext (c0, c1) rotated by `count` amounts in one call -- the linear transforms over slots (matrix-vector products, the
+ * baby steps of BSGS, traces, CoeffToSlot) rotate one ciphertext many times, and every key switch of c1 repeats the same mod-up.
+ * The context is that of the key switch above: nm moduli, the last k_special special, L = nm - k_special, digits of alpha rows,
+ * dnum = nflhip_keyswitch_digits.
+ *   c0, c1        [batch][L][degree], NTT form; c0 may be NULL
+ *   keys[m]       [dnum][2][nmoduli][degree], NTT form, shared by the batch; one device pointer per rotation (a HOST array)
+ *   ks[m]         odd, taken mod 2 degree (a HOST array); m < count <= NFLHIP_ROTATE_MAX_OUTPUTS
+ *   out0s[m], out1s[m]   [batch][L][degree], NTT form (HOST arrays of device pointers)
+ * Definition, word for word, for every m:
+ *     (d0, d1) = nflhip_keyswitch_ntt_dev(c1, keys[m], k_special, alpha)    NFLHIP_ROTATE_CENTERED / _FLOOR as NFLHIP_KEYSWITCH_*
+ *     y0       = d0 + c0   row by row mod p_j, canonical                    (y0 = d0 when c0 is NULL)
+ *     out0s[m] = sigma^NTT_ks[m](y0),   out1s[m] = sigma^NTT_ks[m](d1)      nflhip_automorphism_dev, NFLHIP_FORM_NTT
+ * THE PERMUTATION COMES LAST, after the mod-down: the mod-up U_d of c1 then does not depend on m, so it is computed once, every
+ * plan gives the same words as the sequence, and only 2 L rows per rotation are permuted instead of dnum nm.
+ * The key convention that goes with it: keys[m] switches from s to sigma_(k^-1)(s),
+ *     key[d][0] = -a_d sigma_(k^-1)(s) + e_d + P g_d s,   key[d][1] = a_d       (g_d, P as for the key switch),
+ * which is the usual Galois key for k with the NTT-form automorphism by k^-1 mod 2 degree applied to both components of every
+ * term, once at key generation.  Then out0 + out1 s ~ sigma_k(c0 + c1 s), with the noise of one key switch.
+ * Plans, same words; `flags` may carry at most one plan flag:
+ *   NFLHIP_ROTATE_SEQUENCE  the definition itself per rotation: nflhip_keyswitch_ntt_dev (its default plan) into scratch, the
+ *                           element-wise ADD of c0 (nflhip_pointwise_dev; for buffers off 16 bytes or of no whole number of
+ *                           16-byte groups nflhip_dot_dev as c0 + d0 (.) 1), two nflhip_automorphism_dev.  No kernel of its own.
+ *   NFLHIP_ROTATE_HOISTED   the mod-up ONCE (per-digit nflhip_baseconv_ntt_dev for rows up to 2048 words; above that, or for a
+ *                           context created under NFLHIP_VARIANT=hipcc, one inverse transform, the all-digit mod-up pass and one
+ *                           forward transform); ONE nflhip_dot_multi_dev-style launch for the 2 count inner products, the digits
+ *                           read once; ONE nflhip_moddown_ntt_dev of 2 count batch polynomials; ONE launch that adds c0 and permutes.
+ *   none                    hoisted for count >= 2, the sequence for count == 1.
+ * Scratch of the hoisted plan, context-owned, in polynomials of nm rows (p) and of L rows (q):
+ *     batch (1 p | 1 q) [the embedded | inverse-transformed c1]  +  batch dnum p [U]  +  2 count batch p [S]  +  2 count batch q [Y];
+ * of the sequence 3 batch q + 1 q, besides the key switch's own.
+ * The first call for a (k_special, alpha, plan, modes), or for a larger batch or count * batch, builds tables and allocates (it
+ * synchronises): make it before capturing into a hipGraph; while capturing it is NFLHIP_ERR_UNSUPPORTED and the stream stays
+ * usable.  Calls on different streams are ordered on the scratch by an event; a replaying graph must not run concurrently with
+ * other rotations or key switches of the context.
+ * NFLHIP_ERR_INVALID, nothing enqueued: a NULL context, a NULL pointer with batch != 0 (except c0), count == 0 or > 16, an even k,
+ * k_special or alpha out of range, unknown flag bits or two plan flags, a size that overflows size_t, any overlap among the
+ * 2 count outputs or of an output with c0, c1 or a key, a cyclic row context, a repeated modulus inside a digit or among the
+ * special rows.  Keys may repeat, a k may repeat, k = 1 is allowed.  batch == 0 returns NFLHIP_OK and touches nothing.
+ * The host variant stages c0, c1, every key and every output. */
+#define NFLHIP_ROTATE_MAX_OUTPUTS 16
+#define NFLHIP_ROTATE_CENTERED 0x100
+#define NFLHIP_ROTATE_FLOOR 0x200
+#define NFLHIP_ROTATE_SEQUENCE 0x1000
+#define NFLHIP_ROTATE_HOISTED 0x2000
+int nflhip_rotate_hoisted_ntt_dev(nflhip_ctx *ctx, void *const *d_out0s, void *const *d_out1s, const void *d_c0, const void *d_c1,
+                                  const void *const *d_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special,
+                                  size_t alpha, int flags, void *stream);
+int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const *h_out1s, const void *h_c0, const void *h_c1,
+                              const void *const *h_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special,
+                              size_t alpha, int flags);   /* staged host variant */
 
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by

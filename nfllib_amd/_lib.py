@@ -28,6 +28,9 @@ DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED = 0x100, 0x200, 0x400
 BASECONV_CENTERED, MODDOWN_FLOOR = 0x100, 0x100
 BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED = 0x200, 0x400
 KEYSWITCH_CENTERED, KEYSWITCH_FLOOR, KEYSWITCH_COMPOSED, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE = 0x100, 0x200, 0x400, 0x800, 0x1000
+DOT_MULTI_MAX_OUTPUTS = 32
+ROTATE_MAX_OUTPUTS = 16
+ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_SEQUENCE, ROTATE_HOISTED = 0x100, 0x200, 0x1000, 0x2000
 
 
 class DotOperand(C.Structure):
@@ -63,6 +66,7 @@ SYMBOLS = [
     ("nflhip_dot_dev", _i, [_vp, _vp, C.POINTER(DotOperand), C.POINTER(DotOperand), _vp, _sz, _sz, _i, _vp]),
     ("nflhip_dot_ptrs_dev", _i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _sz, _vp, _vp]),
     ("nflhip_dot", _i, [_vp, _vp, _vp, _vp, _sz, _sz, _i]),
+    ("nflhip_dot_multi_dev", _i, [_vp, C.POINTER(_vp), C.POINTER(DotOperand), C.POINTER(_vp), _sz, _sz, _sz, _sz, _i, _vp]),
     ("nflhip_decompose_terms", _sz, [_vp, _i]),
     ("nflhip_decompose_dev", _i, [_vp, _vp, _i, _vp, _sz, _i, _i, _vp]),
     ("nflhip_decompose", _i, [_vp, _vp, _i, _vp, _sz, _i, _i]),
@@ -77,6 +81,8 @@ SYMBOLS = [
     ("nflhip_keyswitch_digits", _sz, [_vp, _sz, _sz]),
     ("nflhip_keyswitch_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _vp]),
     ("nflhip_keyswitch_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i]),
+    ("nflhip_rotate_hoisted_ntt_dev", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_rotate_hoisted_ntt", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i]),
     ("nflhip_gadget_mul_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),

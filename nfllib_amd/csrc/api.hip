@@ -388,7 +388,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch, nflhip::warm_dot_multi, nflhip::warm_rotate};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -498,6 +498,8 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   for (auto &kv : ctx->bconv) (void)hipFree(kv.second);
   ctx->bconv.clear();
   if (ctx->ev_ks) (void)hipEventDestroy(ctx->ev_ks);
+  if (ctx->ev_rot) (void)hipEventDestroy(ctx->ev_rot);
+  if (ctx->rot_scratch) (void)hipFree(ctx->rot_scratch);
   if (ctx->ks_scratch) (void)hipFree(ctx->ks_scratch);
   for (auto &kv : ctx->ks_recs) (void)hipFree(kv.second);
   ctx->ks_recs.clear();
@@ -793,6 +795,20 @@ int nflhip_dot_ptrs_dev(nflhip_ctx *ctx, void *d_out, const void *const *d_a, co
                               (hipStream_t)stream);
   });
   return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "dot (pointer form)");
+}
+
+// Several outputs against one first operand (kernels_dot_multi.hip).  Two groups per load of b's words unless NFLHIP_DOT_UNTILED.
+int nflhip_dot_multi_dev(nflhip_ctx *ctx, void *const *d_outs, const nflhip_dot_operand *a, const void *const *d_bs, size_t b_term_stride,
+                         size_t outputs, size_t groups, size_t terms, int flags, void *stream) {
+  int rc = dot_multi_check(ctx, d_outs, a, d_bs, b_term_stride, outputs, groups, terms, flags);  // in full, before any device use
+  if (rc || groups == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)d_outs, (const T *)a->ptr, a->group_stride, a->term_stride,
+                               (const T *const *)d_bs, b_term_stride, outputs, groups, terms, !(flags & NFLHIP_DOT_UNTILED), (hipStream_t)stream);
+  });
+  return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "dot_multi");
 }
 
 // Gadget decomposition (kernels_decompose.hip).  The coefficient form is one streaming pass.  The NTT form has two plans with the
@@ -1200,6 +1216,157 @@ int nflhip_keyswitch_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const 
   int rc = keyswitch_check(ctx, d_out0, d_out1, d_in, d_key, batch, k_special, alpha, flags);  // in full, before any device use
   if (rc || batch == 0) return rc;
   return keyswitch_run(ctx, d_out0, d_out1, d_in, d_key, batch, k_special, alpha, flags, (hipStream_t)stream);
+}
+
+// Hoisted rotations (kernels_rotate.hip, kernels_dot_multi.hip; include/nflhip.h "hoisted rotations"): count key switches of one c1, each
+// followed by the addition of c0 and the NTT-form automorphism -- the permutation LAST, so that the mod-up is shared.  Two plans with
+// the same words:
+//   sequence  per rotation nflhip_keyswitch_ntt_dev (its default plan) into T0, T1 = [batch][L][n], c0 added by nflhip_pointwise_dev on
+//             the child context over rows [0, L) -- or, where that entry cannot serve (a pointer off 16 bytes, a batch that is no whole
+//             number of 16-byte groups), by nflhip_dot_dev as c0 + T0 (.) 1 into T2 --, then nflhip_automorphism_dev twice
+//   hoisted   the mod-up once into U, by the two routes of keyswitch_run (per-digit nflhip_baseconv_ntt_dev from X = c1 embedded in nm
+//             rows, U = [dnum][batch][nm][n]; or X = c1 inverse-transformed, k_modup_digits, one forward transform, U =
+//             [batch][dnum][nm][n]); k_dot_multi into S = [2 count][batch][nm][n]; one mod-down into Y = [2 count][batch][L][n];
+//             k_permute_add_ntt
+// Default: hoisted for count >= 2, the sequence for count == 1 (a single rotation has no mod-up to share and the key switch's own
+// default plan is the measured best there).
+// Lock order: rot_mu, then ks_mu, then bcn_mu.
+static int rotate_run(nflhip_ctx *ctx, void *const *out0s, void *const *out1s, const void *c0, const void *c1, const void *const *keys,
+                      const uint64_t *ks, size_t count, size_t batch, size_t K, size_t alpha, int flags, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->rot_mu);
+  const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha, row = ctx->shape.n * ctx->word, pb = nm * row, qb = L * row;
+  const bool centred = (flags & NFLHIP_ROTATE_CENTERED) != 0, floor = (flags & NFLHIP_ROTATE_FLOOR) != 0, cap = is_capturing(st);
+  const uint64_t *const *recs = nullptr;
+  int rc;
+  {  // the tables first: a repeated modulus is refused with the builder's message before anything is enqueued
+    std::lock_guard<std::mutex> l2(ctx->ks_mu);
+    try {
+      rc = keyswitch_records(ctx, K, alpha, st, &recs);
+    } catch (const std::bad_alloc &) {
+      return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+    }
+  }
+  if (rc) return rc;
+  int plan = flags & (NFLHIP_ROTATE_SEQUENCE | NFLHIP_ROTATE_HOISTED);
+  if (!plan) plan = count >= 2 ? NFLHIP_ROTATE_HOISTED : NFLHIP_ROTATE_SEQUENCE;
+  const int modes = flags & (NFLHIP_ROTATE_CENTERED | NFLHIP_ROTATE_FLOOR);
+  // what a call while capturing may do: repeat a (k_special, alpha, plan, modes) already served at this batch and count * batch or larger
+  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes)};
+  auto wit = ctx->rot_warm.find(wkey);
+  if (cap && (wit == ctx->rot_warm.end() || wit->second[0] < batch || wit->second[1] < count * batch))
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "rotate: the first call for a (k_special, alpha, plan), or for a larger batch, allocates, which a stream capture cannot do");
+  const bool seq = plan == NFLHIP_ROTATE_SEQUENCE, perdigit = !ctx->shape.compiled_only && ctx->shape.n <= 2048;
+  // sequence: T0, T1, T2 and a polynomial of ones; hoisted: X, U, S, Y
+  const size_t xb = seq ? 3 * batch * qb + qb : perdigit ? batch * pb : batch * qb;
+  const size_t ub = seq ? 0 : batch * dnum * pb, sb = seq ? 0 : 2 * count * batch * pb, yb = seq ? 0 : 2 * count * batch * qb;
+  const size_t need = xb + ub + sb + yb;
+  if ((rc = set_device(ctx))) return rc;
+  nflhip_ctx *child = nullptr;
+  {
+    std::lock_guard<std::mutex> l2(ctx->bcn_mu);
+    if ((rc = bcn_child(ctx, 0, L, cap, &child))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+  }
+  if (ctx->rot_scratch_bytes < need) {
+    if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "rotate: the scratch has to grow, which a stream capture cannot do");
+    if (ctx->rot_scratch) HIPCHK(ctx, hipFree(ctx->rot_scratch));  // (synchronises: nothing still reads it)
+    ctx->rot_scratch = nullptr;
+    ctx->rot_scratch_bytes = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->rot_scratch, need));
+    ctx->rot_scratch_bytes = need;
+  }
+  if (!ctx->ev_rot) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_rot, hipEventDisableTiming));
+  if (!cap && ctx->ev_rot_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_rot, 0));  // a previous call on another stream
+  char *X = (char *)ctx->rot_scratch;
+  if (seq) {
+    char *T0 = X, *T1 = T0 + batch * qb, *T2 = T1 + batch * qb, *ones = T2 + batch * qb;
+    const bool pw = (((uintptr_t)T0 | (uintptr_t)c0) & 15u) == 0 && (batch * qb) % 16 == 0;  // what nflhip_pointwise_dev serves
+    if (c0 && !pw) {  // a polynomial of ones: every byte 0, then the low byte of every word 1
+      HIPCHK(ctx, hipMemsetAsync(ones, 0, qb, st));
+      HIPCHK(ctx, hipMemset2DAsync(ones, ctx->word, 1, 1, L * ctx->shape.n, st));
+    }
+    for (size_t m = 0; m < count; ++m) {
+      if ((rc = nflhip_keyswitch_ntt_dev(ctx, T0, T1, c1, keys[m], batch, K, alpha, modes, st))) return rc;  // (the mode bits are the key switch's)
+      const char *y0 = T0;
+      if (c0 && pw) {
+        if ((rc = nflhip_pointwise_dev(child, NFLHIP_OP_ADD, T0, T0, c0, nullptr, batch, st))) return rc;
+      } else if (c0) {
+        const nflhip_dot_operand a = {T0, 1, 1}, b = {ones, 0, 0};
+        if ((rc = nflhip_dot_dev(child, T2, &a, &b, c0, batch, 1, 0, st))) return rc;
+        y0 = T2;
+      }
+      if ((rc = nflhip_automorphism_dev(child, out0s[m], y0, batch, ks[m], NFLHIP_FORM_NTT, st))) return rc;
+      if ((rc = nflhip_automorphism_dev(child, out1s[m], T1, batch, ks[m], NFLHIP_FORM_NTT, st))) return rc;
+    }
+    if ((rc = set_device(ctx))) return rc;
+  } else {
+    char *U = X + xb, *S = U + ub, *Y = S + sb;
+    size_t a_gs, a_ts;
+    if (perdigit) {
+      HIPCHK(ctx, hipMemcpy2DAsync(X, pb, c1, qb, qb, batch, hipMemcpyDeviceToDevice, st));
+      for (size_t d = 0; d < dnum; ++d)
+        if ((rc = nflhip_baseconv_ntt_dev(ctx, U + d * batch * pb, X, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm,
+                                          centred ? NFLHIP_BASECONV_CENTERED : 0, st)))
+          return rc;
+      a_gs = 1, a_ts = batch;
+    } else {
+      HIPCHK(ctx, hipMemcpyAsync(X, c1, batch * qb, hipMemcpyDeviceToDevice, st));
+      if ((rc = nflhip_ntt_inv_dev(child, X, batch, st)) || (rc = set_device(ctx))) return rc;
+      hipError_t e = with_limb(ctx, [&](auto z) {
+        typedef decltype(z) T;
+        return launch_modup_digits<T>(ctx->shape, ctx->tabs, (T *)U, (const T *)X, recs, batch, L, alpha, centred, st);
+      });
+      if (e != hipSuccess) return hipfail(ctx, e, "rotate: mod-up");
+      if ((rc = nflhip_ntt_fwd_dev(ctx, U, batch * dnum, st))) return rc;
+      a_gs = dnum, a_ts = 1;
+    }
+    if ((rc = set_device(ctx))) return rc;
+    void *douts[2 * NFLHIP_ROTATE_MAX_OUTPUTS], *pouts[2 * NFLHIP_ROTATE_MAX_OUTPUTS];
+    const void *dbs[2 * NFLHIP_ROTATE_MAX_OUTPUTS], *pins[2 * NFLHIP_ROTATE_MAX_OUTPUTS];
+    uint64_t pks[2 * NFLHIP_ROTATE_MAX_OUTPUTS];
+    unsigned add_mask = 0;
+    for (size_t m = 0; m < count; ++m)
+      for (size_t c = 0; c < 2; ++c) {
+        const size_t p = 2 * m + c;
+        douts[p] = S + p * batch * pb;
+        dbs[p] = (const char *)keys[m] + c * pb;
+        pins[p] = Y + p * batch * qb;
+        pouts[p] = c ? out1s[m] : out0s[m];
+        pks[p] = ks[m];
+        if (c == 0) add_mask |= 1u << p;
+      }
+    hipError_t e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, a_gs, a_ts, (const T *const *)dbs, 2, 2 * count, batch,
+                                 dnum, 1, st);
+    });
+    if (e != hipSuccess) return hipfail(ctx, e, "rotate: inner products");
+    if ((rc = nflhip_moddown_ntt_dev(ctx, Y, S, 2 * count * batch, K, floor ? NFLHIP_MODDOWN_FLOOR : 0, st)) || (rc = set_device(ctx))) return rc;
+    e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_permute_add_ntt<T>(ctx->shape, ctx->tabs, (T *const *)pouts, (const T *const *)pins, pks, add_mask, (int)(2 * count),
+                                       (const T *)c0, L, batch, st);
+    });
+    if (e != hipSuccess) return hipfail(ctx, e, "rotate: permutation");
+  }
+  if (!cap) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev_rot, st));
+    ctx->ev_rot_valid = true;
+    try {
+      std::array<size_t, 2> &w = ctx->rot_warm[wkey];
+      if (w[0] < batch) w[0] = batch;
+      if (w[1] < count * batch) w[1] = count * batch;
+    } catch (const std::bad_alloc &) {
+    }
+  }
+  return NFLHIP_OK;
+}
+int nflhip_rotate_hoisted_ntt_dev(nflhip_ctx *ctx, void *const *d_out0s, void *const *d_out1s, const void *d_c0, const void *d_c1,
+                                  const void *const *d_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha,
+                                  int flags, void *stream) {
+  int rc = rotate_check(ctx, d_out0s, d_out1s, d_c0, d_c1, d_keys, ks, count, batch, k_special, alpha, flags);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  return rotate_run(ctx, d_out0s, d_out1s, d_c0, d_c1, d_keys, ks, count, batch, k_special, alpha, flags, (hipStream_t)stream);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

@@ -466,6 +466,48 @@ int nflhip_keyswitch_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void
   return NFLHIP_OK;
 }
 
+// hoisted rotations: c1 (and c0 behind it), every key and every output are staged whole (the outputs share one slot, out0s then out1s)
+int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const *h_out1s, const void *h_c0, const void *h_c1,
+                              const void *const *h_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
+  int rc = rotate_check(ctx, h_out0s, h_out1s, h_c0, h_c1, h_keys, ks, count, batch, k_special, alpha, flags);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * (nm - k_special) * row;
+  const size_t kb = 2 * keyswitch_digits(ctx, k_special, alpha) * nm * row;
+  Staged s(ctx);
+  if ((rc = s.in(0, nullptr, 2 * ob)) || (rc = s.in(1, nullptr, count * kb)) || (rc = s.in(2, nullptr, 2 * count * ob))) return rc;
+  char *c = (char *)ctx->stage[0], *k = (char *)ctx->stage[1], *o = (char *)ctx->stage[2];
+  const bool hc = ctx->stage_host[0], hk = ctx->stage_host[1], ho = ctx->stage_host[2];
+  if (hc) std::memcpy(c, h_c1, ob);
+  else HIPCHK(ctx, hipMemcpyAsync(c, h_c1, ob, hipMemcpyHostToDevice, ctx->hstream));
+  if (h_c0 && hc) std::memcpy(c + ob, h_c0, ob);
+  else if (h_c0) HIPCHK(ctx, hipMemcpyAsync(c + ob, h_c0, ob, hipMemcpyHostToDevice, ctx->hstream));
+  void *o0[NFLHIP_ROTATE_MAX_OUTPUTS], *o1[NFLHIP_ROTATE_MAX_OUTPUTS];
+  const void *keys[NFLHIP_ROTATE_MAX_OUTPUTS];
+  for (size_t m = 0; m < count; ++m) {
+    if (hk) std::memcpy(k + m * kb, h_keys[m], kb);
+    else HIPCHK(ctx, hipMemcpyAsync(k + m * kb, h_keys[m], kb, hipMemcpyHostToDevice, ctx->hstream));
+    keys[m] = k + m * kb;
+    o0[m] = o + m * ob;
+    o1[m] = o + (count + m) * ob;
+  }
+  if ((rc = nflhip_rotate_hoisted_ntt_dev(ctx, o0, o1, h_c0 ? c + ob : nullptr, c, keys, ks, count, batch, k_special, alpha, flags, (void *)ctx->hstream)))
+    return rc;
+  if (!ho)
+    for (size_t m = 0; m < count; ++m) {
+      HIPCHK(ctx, hipMemcpyAsync(h_out0s[m], o0[m], ob, hipMemcpyDeviceToHost, ctx->hstream));
+      HIPCHK(ctx, hipMemcpyAsync(h_out1s[m], o1[m], ob, hipMemcpyDeviceToHost, ctx->hstream));
+    }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
+  s.pending = false;
+  if (ho)
+    for (size_t m = 0; m < count; ++m) {
+      std::memcpy(h_out0s[m], o0[m], ob);
+      std::memcpy(h_out1s[m], o1[m], ob);
+    }
+  return NFLHIP_OK;
+}
+
 // sums of products across polynomials: the operands are `terms` times the size of the result, so the call is staged whole
 int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, size_t groups, size_t terms, int b_shared) {
   if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");

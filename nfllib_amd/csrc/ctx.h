@@ -94,6 +94,16 @@ struct nflhip_ctx {
   size_t ks_scratch_bytes = 0;
   hipEvent_t ev_ks = nullptr;
   bool ev_ks_valid = false;
+  // hoisted rotations (api.hip rotate_run): per (k_special, alpha, plan | modes) the largest batch and the largest count * batch served
+  // so far (what a call while capturing may repeat); one scratch for the mod-up's input, the digits, the sums and the mod-down's
+  // result (the sequence: one key switch's two results), calls ordered on it by ev_rot.  All under rot_mu, which is taken BEFORE
+  // ks_mu and bcn_mu.
+  std::mutex rot_mu;
+  std::map<std::array<size_t, 3>, std::array<size_t, 2>> rot_warm;
+  void *rot_scratch = nullptr;
+  size_t rot_scratch_bytes = 0;
+  hipEvent_t ev_rot = nullptr;
+  bool ev_rot_valid = false;
 };
 
 void pipe_destroy(nflhip_ctx *ctx);  // api_host.hip: frees the context's host-pointer pipeline
@@ -283,6 +293,73 @@ inline int keyswitch_check(const nflhip_ctx *ctx, const void *out0, const void *
   for (int a = 0; a < 4; ++a)
     for (int b = a + 1; b < 4; ++b)
       if (ranges_overlap(ptr[a], len[a], ptr[b], len[b])) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: out0, out1, in and key may not overlap");
+  return NFLHIP_OK;
+}
+// nflhip_dot_multi_dev: every argument check, before any device use.  Every output against the extent of a, of every b_o and against
+// every other output; the b pointers may alias each other.
+inline int dot_multi_check(const nflhip_ctx *ctx, void *const *outs, const nflhip_dot_operand *a, const void *const *bs, size_t b_ts,
+                           size_t outputs, size_t groups, size_t terms, int flags) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "dot_multi: not on a cyclic row context");
+  if (flags & ~NFLHIP_DOT_UNTILED) return fail(ctx, NFLHIP_ERR_INVALID, "dot_multi: unknown flag bits");
+  if (outputs == 0 || outputs > NFLHIP_DOT_MULTI_MAX_OUTPUTS) return fail(ctx, NFLHIP_ERR_INVALID, "dot_multi: the number of outputs is out of range (1 to 32)");
+  if (terms == 0 || terms > nflhip::kDotMaxTerms) return fail(ctx, NFLHIP_ERR_INVALID, "dot_multi: the number of terms is out of range (1 to 2^31)");
+  if (!a || !outs || !bs) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  if (groups == 0) return NFLHIP_OK;
+  if (!a->ptr) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  for (size_t o = 0; o < outputs; ++o)
+    if (!outs[o] || !bs[o]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t pb = poly_bytes(ctx, 1);
+  size_t obytes, g, t, polys, abytes, bbytes;
+  if (__builtin_mul_overflow(groups, pb, &obytes)) return fail(ctx, NFLHIP_ERR_INVALID, "dot_multi: the output size overflows");
+  if (__builtin_mul_overflow(groups - 1, a->group_stride, &g) || __builtin_mul_overflow(terms - 1, a->term_stride, &t) ||
+      __builtin_add_overflow(g, t, &polys) || __builtin_add_overflow(polys, (size_t)1, &polys) || __builtin_mul_overflow(polys, pb, &abytes) ||
+      __builtin_mul_overflow(terms - 1, b_ts, &t) || __builtin_add_overflow(t, (size_t)1, &polys) || __builtin_mul_overflow(polys, pb, &bbytes))
+    return fail(ctx, NFLHIP_ERR_INVALID, "dot_multi: an operand's extent overflows");
+  for (size_t o = 0; o < outputs; ++o) {
+    if (ranges_overlap(outs[o], obytes, a->ptr, abytes)) return fail(ctx, NFLHIP_ERR_INVALID, "dot_multi: an output overlaps an operand");
+    for (size_t q = 0; q < outputs; ++q) {
+      if (ranges_overlap(outs[o], obytes, bs[q], bbytes)) return fail(ctx, NFLHIP_ERR_INVALID, "dot_multi: an output overlaps an operand");
+      if (q < o && ranges_overlap(outs[o], obytes, outs[q], obytes)) return fail(ctx, NFLHIP_ERR_INVALID, "dot_multi: two outputs overlap");
+    }
+  }
+  return NFLHIP_OK;
+}
+// nflhip_rotate_hoisted_ntt_dev / nflhip_rotate_hoisted_ntt: every argument check short of the tables (a repeated modulus is found by
+// their builder, api.hip keyswitch_records), before any device use
+inline int rotate_check(const nflhip_ctx *ctx, void *const *out0s, void *const *out1s, const void *c0, const void *c1, const void *const *keys,
+                        const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: a cyclic row context has no modulus chain");
+  const int plans = NFLHIP_ROTATE_SEQUENCE | NFLHIP_ROTATE_HOISTED, plan = flags & plans;
+  if (flags & ~(plans | NFLHIP_ROTATE_CENTERED | NFLHIP_ROTATE_FLOOR)) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: unknown flag bits");
+  if (plan == plans) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: one plan flag at most");
+  if (count == 0 || count > NFLHIP_ROTATE_MAX_OUTPUTS) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: the number of rotations is out of range (1 to 16)");
+  const size_t nm = ctx->shape.nm, dnum = keyswitch_digits(ctx, k_special, alpha);
+  if (k_special == 0 || k_special >= nm) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: k_special is out of range (1 to nmoduli - 1)");
+  if (dnum == 0) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: alpha is out of range (1 to nmoduli - k_special)");
+  if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: more than 65535 rows");
+  if (batch == 0) return NFLHIP_OK;
+  if (!ks) return fail(ctx, NFLHIP_ERR_INVALID, "NULL multiplier array");
+  for (size_t m = 0; m < count; ++m)
+    if ((ks[m] & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: the exponent k must be odd");
+  if (!out0s || !out1s || !c1 || !keys) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  for (size_t m = 0; m < count; ++m)
+    if (!out0s[m] || !out1s[m] || !keys[m]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t row = ctx->shape.n * ctx->word, L = nm - k_special;
+  size_t ob, sb, kb, polys;
+  // (sb: the largest scratch of either plan -- [batch][1 + dnum + 4 count][nm][n] -- on top of the key switch's own)
+  if (__builtin_mul_overflow(batch, L * row, &ob) || __builtin_mul_overflow(batch, dnum + 3 + 4 * count, &polys) ||
+      __builtin_mul_overflow(polys, nm * row, &sb) || __builtin_mul_overflow(2 * dnum, nm * row, &kb))
+    return fail(ctx, NFLHIP_ERR_INVALID, "rotate: the size overflows");
+  for (size_t m = 0; m < 2 * count; ++m) {
+    const void *o = m < count ? out0s[m] : out1s[m - count];
+    if ((c0 && ranges_overlap(o, ob, c0, ob)) || ranges_overlap(o, ob, c1, ob)) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: an output overlaps c0 or c1");
+    for (size_t q = 0; q < count; ++q)
+      if (ranges_overlap(o, ob, keys[q], kb)) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: an output overlaps a key");
+    for (size_t q = 0; q < m; ++q)
+      if (ranges_overlap(o, ob, q < count ? out0s[q] : out1s[q - count], ob)) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: two outputs overlap");
+  }
   return NFLHIP_OK;
 }
 constexpr size_t kStageHostMax = (size_t)1 << 20;

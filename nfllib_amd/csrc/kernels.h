@@ -108,6 +108,22 @@ hipError_t launch_dot(const Shape &s, const DevTables &t, T *out, const T *a, si
 template <typename T>
 hipError_t launch_dot_ptrs(const Shape &s, const DevTables &t, T *out, const T *const *a, const T *const *b, size_t terms, const T *addend,
                            hipStream_t st);
+// several outputs against one first operand (kernels_dot_multi.hip; include/nflhip.h "sums of products, several outputs"):
+// outs[o][g] = sum_j a(g,j) b_o(j), a(g,j) at a + (g a_gs + j a_ts) polynomials, b_o(j) at bs[o] + j b_ts polynomials, every outs[o]
+// dense [groups][nm][n]; outs / bs are HOST arrays of `outputs` <= kDotMultiMaxOutputs device pointers, which travel in the kernel
+// arguments.  No output may overlap an operand or another output (api.hip checks).  tiled: two groups per load of b's words.
+constexpr int kDotMultiMaxOutputs = 32;
+template <typename T>
+hipError_t launch_dot_multi(const Shape &s, const DevTables &t, T *const *outs, const T *a, size_t a_gs, size_t a_ts, const T *const *bs,
+                            size_t b_ts, size_t outputs, size_t groups, size_t terms, int tiled, hipStream_t st);
+// the last step of a hoisted rotation (kernels_rotate.hip; include/nflhip.h "hoisted rotations"): outs[p] = sigma^NTT_{ks[p]}(ins[p]
+// [+ c0 when bit p of add_mask is set]) for p < pairs <= kRotateMaxPairs, every block [batch][L][n] in the dense layout over the
+// first L moduli of the context (the sum is mod p_(row mod L)); c0 may be nullptr.  HOST arrays of device pointers, which travel in
+// the kernel arguments.  No output may overlap an input, c0 or another output (api.hip checks).  hipErrorInvalidValue for an even k
+constexpr int kRotateMaxPairs = 32;
+template <typename T>
+hipError_t launch_permute_add_ntt(const Shape &s, const DevTables &t, T *const *outs, const T *const *ins, const uint64_t *ks, unsigned add_mask,
+                                  int pairs, const T *c0, size_t L, size_t batch, hipStream_t st);
 // gadget decomposition (kernels_decompose.hip; include/nflhip.h "gadget decomposition"): in = [batch][nm][n] canonical words in
 // coefficient form, digit width 1 <= w <= limb_bits - 3, l = ceil((limb_bits - 2) / w), terms = nm l; sgn: balanced digits.
 // _words: out = [batch][terms][nm][n], the digit spread over every row (coefficient form).  _compact: out = [batch][terms][n] of
@@ -315,6 +331,8 @@ hipError_t warm_wave(hipStream_t st);
 hipError_t warm_automorph(hipStream_t st);
 hipError_t warm_rescale(hipStream_t st);
 hipError_t warm_dot(hipStream_t st);
+hipError_t warm_dot_multi(hipStream_t st);
+hipError_t warm_rotate(hipStream_t st);
 hipError_t warm_decompose(hipStream_t st);
 hipError_t warm_baseconv(hipStream_t st);
 hipError_t warm_baseconv_ntt(hipStream_t st);

@@ -17,11 +17,11 @@
 //            contiguous output chunk and gathers its words straight from global memory; the grid is remapped so that all
 //            chunks of a row run on ONE XCD, whose 4 MiB L2 then holds the row while its scattered reads are served.
 #include "kernels.h"
+#include "automorph_index.h"  // aut_rev, aut_ntt_src, aut_inverse_mod_2n, kNttChunkBytes
 
 namespace nflhip {
 
 static constexpr int kAutMaxOut = 16;            // include/nflhip.h NFLHIP_AUTOMORPHISM_MAX_OUTPUTS
-static constexpr size_t kNttChunkBytes = 16384;  // staged input chunk of the NTT-form tile plan
 static constexpr size_t kCoeffStageBytes = 65536;  // largest row the coefficient-form tile plan stages whole
 static constexpr size_t kL2ChunkBytes = 16384;   // output chunk of one workgroup of the l2 plan
 
@@ -31,13 +31,6 @@ template <typename T> struct AutOuts {
   unsigned kinv[kAutMaxOut];  // its inverse mod 2n
   int count;
 };
-
-__device__ __forceinline__ unsigned aut_rev(unsigned x, unsigned logn) { return __brev(x) >> (32u - logn); }
-
-// source slot of NTT-form output slot j
-__device__ __forceinline__ unsigned aut_ntt_src(unsigned j, unsigned k, unsigned logn, unsigned mask2n) {
-  return aut_rev(((k * (2u * aut_rev(j, logn) + 1u)) & mask2n) >> 1, logn);
-}
 
 template <typename T> __device__ __forceinline__ T aut_neg(T x, T p) { return x ? (T)(p - x) : (T)0; }
 
@@ -161,12 +154,6 @@ __global__ void __launch_bounds__(256) k_automorph_l2(const T *__restrict__ in, 
       reinterpret_cast<uint4 *>(out)[v] = pk.u;
     }
   }
-}
-
-static unsigned aut_inverse_mod_2n(unsigned k, unsigned mask2n) {  // k odd: Newton's iteration doubles the correct low bits
-  unsigned x = k;  // correct to 3 bits
-  for (int i = 0; i < 5; ++i) x *= 2u - k * x;
-  return x & mask2n;
 }
 
 template <typename T>

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
+from ._lib import (DOT_MULTI_MAX_OUTPUTS, ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_HOISTED, ROTATE_MAX_OUTPUTS, ROTATE_SEQUENCE, KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -224,6 +224,22 @@ class Engine:
                                                    self._stream(stream)))
         return out
 
+    def dot_multi(self, a, a_strides, bs, b_term_stride, groups, terms, outs=None, untiled=False, stream=None):
+        """outs[o][g] = sum_j a(g, j) * bs[o](j) for every o in ONE launch that reads `a` once (at most 32 outputs): polynomial (g, j)
+        of a starts g * a_strides[0] + j * a_strides[1] polynomials after its first word, term j of bs[o] j * b_term_stride after
+        its first word, shared by every group; a and every bs[o] are tensors (views allowed) or device addresses.  Returns the
+        list of dense [groups, nm, n] tensors; untiled=True forces one group per pass"""
+        bs = list(bs)
+        outs = list(outs) if outs is not None else [self.empty(groups) for _ in bs]
+        if len(outs) != len(bs):
+            raise ValueError("one output per second operand")
+        oa = _lib.DotOperand(a if isinstance(a, int) else a.data_ptr(), a_strides[0], a_strides[1])
+        po = (C.c_void_p * max(len(outs), 1))(*[o if isinstance(o, int) else o.data_ptr() for o in outs])
+        pb = (C.c_void_p * max(len(bs), 1))(*[b if isinstance(b, int) else b.data_ptr() for b in bs])
+        self._chk(self.lib.nflhip_dot_multi_dev(self.ctx, po, C.byref(oa), pb, b_term_stride, len(bs), groups, terms,
+                                                DOT_UNTILED if untiled else 0, self._stream(stream)))
+        return outs
+
     def h_dot(self, a, b, terms, b_shared=False):
         """host-pointer variant: numpy a = [groups * terms, nm, n], b alike or [terms, nm, n] with b_shared; -> [groups, nm, n]"""
         a, b = np.ascontiguousarray(a, dtype=self.np_dtype), np.ascontiguousarray(b, dtype=self.np_dtype)
@@ -413,6 +429,62 @@ class Engine:
         self._chk(self.lib.nflhip_keyswitch_ntt(self.ctx, _vp(out0), _vp(out1), _vp(a), _vp(key), batch, k_special, alpha,
                                                 self._ks_flags(centered, floor, plan)))
         return out0, out1
+
+    # ---- hoisted rotations: one mod-up shared by many Galois key switches (include/nflhip.h "hoisted rotations") ----
+    _ROT_PLAN = {None: 0, "sequence": ROTATE_SEQUENCE, "hoisted": ROTATE_HOISTED}
+
+    def _rot_flags(self, centered, floor, plan):
+        return (ROTATE_CENTERED if centered else 0) | (ROTATE_FLOOR if floor else 0) | self._ROT_PLAN[plan]
+
+    def rotate_hoisted_ntt(self, c0, c1, keys, ks, k_special, alpha, centered=False, floor=False, outs=None, plan=None, stream=None):
+        """the ciphertext (c0, c1), each an NTT-form [batch, L, n] batch with L = nm - k_special (c0 may be None), rotated by every
+        k of ks (odd, at most 16) in one call: for each m the key switch of c1 against keys[m] = [dnum, 2, nm, n], + c0, then the
+        NTT-form automorphism by ks[m] -- the permutation last, so the mod-up of c1 is shared.  keys[m] switches from s to
+        sigma_(k^-1)(s): a standard Galois key for k becomes it by e.automorphism(key.view(-1, nm, n), kinv, ntt=True).  Returns a
+        list of (out0, out1), each [batch, L, n]; `outs` = such a list, else all are views of one new tensor.  plan "sequence" /
+        "hoisted" forces a plan.  The first call for a (k_special, alpha), or a larger batch or count, allocates: make it
+        before a graph capture."""
+        L = self.nmoduli - k_special
+        keys, ks = list(keys), [self._k(k) for k in ks]
+        if L <= 0 or c1.numel() % (L * self.degree) or not c1.is_contiguous() or (c0 is not None and (c0.shape != c1.shape or not c0.is_contiguous())):
+            raise ValueError("c0 and c1 are contiguous [batch, nm - k_special, n] tensors")
+        if len(keys) != len(ks) or not 1 <= len(ks) <= ROTATE_MAX_OUTPUTS:
+            raise ValueError("one key per rotation, 1 to 16 rotations")
+        batch = c1.numel() // (L * self.degree)
+        kwords = 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly
+        if any(k.numel() != kwords or not k.is_contiguous() for k in keys):
+            raise ValueError("every key holds dnum * 2 polynomials of this context")
+        if outs is None:
+            both = _torch().empty((len(ks), 2, batch, L, self.degree), dtype=self.torch_dtype, device=c1.device)
+            outs = [(both[m, 0], both[m, 1]) for m in range(len(ks))]
+        p0 = (C.c_void_p * len(ks))(*[o[0].data_ptr() for o in outs])
+        p1 = (C.c_void_p * len(ks))(*[o[1].data_ptr() for o in outs])
+        pk = (C.c_void_p * len(ks))(*[k.data_ptr() for k in keys])
+        kv = (C.c_uint64 * len(ks))(*ks)
+        self._chk(self.lib.nflhip_rotate_hoisted_ntt_dev(self.ctx, p0, p1, _vp(c0), _vp(c1), pk, kv, len(ks), batch, k_special, alpha,
+                                                         self._rot_flags(centered, floor, plan), self._stream(stream)))
+        return list(outs)
+
+    def h_rotate_hoisted_ntt(self, c0, c1, keys, ks, k_special, alpha, centered=False, floor=False, plan=None):
+        """host-pointer variant: numpy c0 (or None), c1 = [batch, L, n] and keys[m] = [dnum, 2, nm, n] -> a list of (out0, out1)"""
+        c1 = np.ascontiguousarray(c1, dtype=self.np_dtype)
+        c0 = None if c0 is None else np.ascontiguousarray(c0, dtype=self.np_dtype)
+        keys, ks = [np.ascontiguousarray(k, dtype=self.np_dtype) for k in keys], [self._k(k) for k in ks]
+        L = self.nmoduli - k_special
+        kwords = 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly
+        if L <= 0 or c1.size % (L * self.degree) or (c0 is not None and c0.shape != c1.shape) or any(k.size != kwords for k in keys):
+            raise ValueError("c0, c1 are [batch, nm - k_special, n], every key [dnum, 2, nm, n]")
+        if len(keys) != len(ks) or not 1 <= len(ks) <= ROTATE_MAX_OUTPUTS:
+            raise ValueError("one key per rotation, 1 to 16 rotations")
+        batch = c1.size // (L * self.degree)
+        outs = [tuple(np.empty((batch, L, self.degree), dtype=self.np_dtype) for _ in range(2)) for _ in ks]
+        p0 = (C.c_void_p * len(ks))(*[o[0].ctypes.data for o in outs])
+        p1 = (C.c_void_p * len(ks))(*[o[1].ctypes.data for o in outs])
+        pk = (C.c_void_p * len(ks))(*[k.ctypes.data for k in keys])
+        kv = (C.c_uint64 * len(ks))(*ks)
+        self._chk(self.lib.nflhip_rotate_hoisted_ntt(self.ctx, p0, p1, _vp(c0), _vp(c1), pk, kv, len(ks), batch, k_special, alpha,
+                                                     self._rot_flags(centered, floor, plan)))
+        return outs
 
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
         out = out if out is not None else _torch().empty_like(a)
