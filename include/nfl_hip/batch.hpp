@@ -229,6 +229,44 @@ template <class P> class device_batch {
                                                             Q::nmoduli - P::nmoduli, alpha, flags, key0.queue()), "rotate_hoisted_ntt");
     key0.sync();
   }
+  // Slot linear transforms (include/nflhip.h "slot linear transforms"): c0 (may be NULL), c1, out0 and out1 are batches of this ring (L
+  // moduli) of one size; key_batches[m] as for assign_rotations, or NULL for the unrotated diagonal (ks[m] = 1); weight_batches[m] is a
+  // batch of the keys' ring holding the one polynomial of diagonal m, shared by the whole batch; m < count <= 16.  Streams as in
+  // assign_rotations: the launches go on the key ring's stream (that of weight_batches[0]), and the call returns once they have
+  // finished there.
+  template <class Q>
+  static void assign_linear_transform(device_batch &out0, device_batch &out1, const device_batch *c0, const device_batch &c1,
+                                      const device_batch<Q> *const *key_batches, const device_batch<Q> *const *weight_batches, const uint64_t *ks,
+                                      size_t count, size_t alpha, bool centered = false, bool floor = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && Q::nmoduli > P::nmoduli,
+                  "assign_linear_transform: the keys' ring has the same limbs and degree and at least one modulus more");
+    if (alpha == 0 || alpha > P::nmoduli) throw std::runtime_error("nfl(hip): linear transform: alpha is out of range (1 to the ciphertext's moduli)");
+    if (count == 0 || count > NFLHIP_LINTRANS_MAX_TERMS) throw std::runtime_error("nfl(hip): linear transform: 1 to 16 terms");
+    const device_batch<Q> &w0 = *weight_batches[0];
+    const void *kp[NFLHIP_LINTRANS_MAX_TERMS], *wp[NFLHIP_LINTRANS_MAX_TERMS];
+    if ((c0 && c0->size() != c1.size()) || out0.size() != c1.size() || out1.size() != c1.size()) throw std::runtime_error("nfl(hip): batch sizes differ");
+    if ((c0 && c0->device() != w0.device()) || c1.device() != w0.device() || out0.device() != w0.device() || out1.device() != w0.device())
+      throw std::runtime_error("nfl(hip): linear transform operands on different devices");
+    for (size_t m = 0; m < count; ++m) {
+      if (key_batches[m] && key_batches[m]->size() != 2 * ((P::nmoduli + alpha - 1) / alpha)) throw std::runtime_error("nfl(hip): a key batch holds 2 * dnum polynomials");
+      if (weight_batches[m]->size() != 1) throw std::runtime_error("nfl(hip): a weight batch holds one polynomial");
+      if ((key_batches[m] && key_batches[m]->device() != w0.device()) || weight_batches[m]->device() != w0.device())
+        throw std::runtime_error("nfl(hip): linear transform operands on different devices");
+      kp[m] = key_batches[m] ? key_batches[m]->data() : nullptr;
+      wp[m] = weight_batches[m]->data();
+    }
+    c1.sync();
+    c1.strict("linear transform");
+    if (c0) c0->strict("linear transform");
+    for (size_t m = 0; m < count; ++m) {
+      if (key_batches[m]) key_batches[m]->strict("linear transform");
+      weight_batches[m]->strict("linear transform");
+    }
+    const int flags = (centered ? NFLHIP_LINTRANS_CENTERED : 0) | (floor ? NFLHIP_LINTRANS_FLOOR : 0);
+    detail::check(w0.ctx(), nflhip_lintrans_ntt_dev(w0.ctx(), out0.d_, out1.d_, c0 ? c0->d_ : nullptr, c1.d_, kp, wp, ks, count, c1.n_,
+                                                    Q::nmoduli - P::nmoduli, alpha, flags, w0.queue()), "linear_transform_ntt");
+    w0.sync();
+  }
   // Sums of products across polynomials (include/nflhip.h): this batch holds `groups` polynomials, a and b groups * terms each,
   // term-minor: (*this)[g] = sum_j a[g * terms + j] * b[g * terms + j].  assign_matvec: v holds the `terms` polynomials every
   // group shares, (*this)[g] = sum_j m[g * terms + j] * v[j].  The operands must be other batches.

@@ -395,6 +395,57 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     }
   }
 
+  // Slot linear transforms (nfl::linear_transform_ntt below).  This ring type is the KEYS' and the diagonals'; c0, c1 and the two
+  // outputs live in the ring with LO moduli.  keys[m] is an array of 2 dnum polynomials, [term][component], or NULL for the unrotated
+  // diagonal (ks[m] = 1); weights[m] is one polynomial.  Every key and every diagonal is gathered into one contiguous device buffer of
+  // this ring's context: term m at polynomial m * (2 dnum + 1), its key first, its diagonal behind it.  The ordering is that of
+  // rotate_into.  The results get payloads of their own: an output may be c0 or c1, and copy-on-write sharers of the outputs' old
+  // values keep them.  Never fused into a queue's rewrites.
+  template <size_t LO> static void linear_transform_into(poly_p<T, Degree, LO> &out0, poly_p<T, Degree, LO> &out1, poly_p<T, Degree, LO> const *c0,
+                                                         poly_p<T, Degree, LO> const &c1, poly_p const *const *keys, poly_p const *const *weights,
+                                                         const uint64_t *ks, size_t count, size_t alpha, bool centered, bool floor) {
+    static_assert(LO >= 1 && LO < NbModuli, "nfl::linear_transform_ntt: the keys' ring has at least one special modulus more than the ciphertext's");
+    typedef poly_p<T, Degree, LO> out_t;
+    if (alpha == 0 || alpha > LO) throw std::runtime_error("nfl(hip): linear_transform_ntt: alpha is out of range (1 to the ciphertext's moduli)");
+    if (count == 0 || count > NFLHIP_LINTRANS_MAX_TERMS) throw std::runtime_error("nfl(hip): linear_transform_ntt: 1 to 16 terms");
+    const size_t dnum = (LO + alpha - 1) / alpha, pb = sizeof(T) * Degree * NbModuli, kpolys = 2 * dnum, tpolys = kpolys + 1;
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    typename out_t::ptr_type s0 = c0 ? c0->_p : typename out_t::ptr_type(), s1 = c1._p;  // (hold the inputs while the launches are enqueued)
+    typename out_t::ptr_type d0 = out_t::fresh(), d1 = out_t::fresh();
+    std::vector<ptr_type> held;  // (and the keys' and the diagonals' payloads: tpolys slots per term, a NULL key's left empty)
+    for (size_t m = 0; m < count; ++m) {
+      for (size_t t = 0; t < kpolys; ++t) held.push_back(keys[m] ? keys[m][t]._p : ptr_type());
+      held.push_back(weights[m]->_p);
+    }
+    const void *p0 = c0 ? s0->dev_ro() : nullptr, *p1 = s1->dev_ro();
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo();
+    void *kbuf = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &kbuf, count * tpolys * pb), "linear_transform_ntt");
+    const void *kp[NFLHIP_LINTRANS_MAX_TERMS], *wp[NFLHIP_LINTRANS_MAX_TERMS];
+    int rc = NFLHIP_OK;
+    for (size_t m = 0; m < count; ++m) {
+      kp[m] = keys[m] ? static_cast<char *>(kbuf) + m * tpolys * pb : nullptr;
+      wp[m] = static_cast<char *>(kbuf) + (m * tpolys + kpolys) * pb;
+      for (size_t t = 0; t < tpolys && rc == NFLHIP_OK; ++t)
+        if (held[m * tpolys + t])
+          rc = nflhip_memcpy_d2d(ctx_t::get(), static_cast<char *>(kbuf) + (m * tpolys + t) * pb, held[m * tpolys + t]->dev_ro(), pb, ctx_t::queue());
+    }
+    if (rc == NFLHIP_OK) rc = nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue());
+    const int flags = (centered ? NFLHIP_LINTRANS_CENTERED : 0) | (floor ? NFLHIP_LINTRANS_FLOOR : 0);
+    if (rc == NFLHIP_OK) rc = nflhip_lintrans_ntt_dev(ctx_t::get(), o0, o1, p0, p1, kp, wp, ks, count, 1, NbModuli - LO, alpha, flags, ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered keys go)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), kbuf);
+      throw std::runtime_error("nfl(hip): linear_transform_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), kbuf);
+    detail::check(ctx_t::get(), rs, "linear_transform_ntt");
+    out0._p = d0;
+    out1._p = d1;
+  }
+
   // Sum of products (nfl::dot / nfl::dot_add below): the deferred queue of this ring type runs first (on the caller), then the
   // pointer form of the entry on the queue's stream, 16 terms per launch, chained through the addend.  The result gets a
   // payload of its own, so `out` may be one of the inputs and copy-on-write sharers of out's old value keep it.
@@ -680,6 +731,44 @@ template <class T, size_t D, size_t L, size_t M>
 void rotate_hoisted_ntt(poly_p<T, D, L> *out0s, poly_p<T, D, L> *out1s, poly_p<T, D, L> const *c0, poly_p<T, D, L> const &c1,
                         poly_p<T, D, M> const *const *keys, const uint64_t *ks, size_t count, size_t alpha, bool centered = false, bool floor = false) {
   poly_p<T, D, M>::template rotate_into<L>(out0s, out1s, c0, c1, keys, ks, count, alpha, centered, floor);
+}
+
+/* Slot linear transforms (include/nflhip.h "slot linear transforms"): (out0, out1) = sum_m weights[m] * sigma_ks[m](c0, c1) for m < count
+ * <= 16 with ONE mod-down: the key-switch sums of c1 against keys[m] are permuted, multiplied by the diagonals and added up on all M
+ * rows, then modded down once; the c0 terms and the unrotated diagonals are added on the L rows.  keys[m] as for rotate_hoisted_ntt, or
+ * NULL for the unrotated diagonal (ks[m] = 1 mod 2 D); weights[m] one polynomial of the ring with M moduli, the diagonal in NTT form.
+ * Not the words of a weighted sum of rotate_hoisted_ntt results: one rounding instead of `count`.  c0 may be NULL; an output may be c0
+ * or c1.  On poly the staged host entry, the outputs through temporaries; on poly_p the ordering of rotate_hoisted_ntt. */
+template <class T, size_t D, size_t L, size_t M>
+void linear_transform_ntt(poly<T, D, L> &out0, poly<T, D, L> &out1, poly<T, D, L> const *c0, poly<T, D, L> const &c1, poly<T, D, M> const *const *keys,
+                          poly<T, D, M> const *const *weights, const uint64_t *ks, size_t count, size_t alpha, bool centered = false,
+                          bool floor = false) {
+  static_assert(L >= 1 && L < M, "nfl::linear_transform_ntt: the keys' ring has at least one special modulus more than the ciphertext's");
+  typedef poly<T, D, L> S;
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  if (count == 0 || count > NFLHIP_LINTRANS_MAX_TERMS) throw std::runtime_error("nfl(hip): linear_transform_ntt: 1 to 16 terms");
+  const void *kp[NFLHIP_LINTRANS_MAX_TERMS], *wp[NFLHIP_LINTRANS_MAX_TERMS];
+  for (size_t m = 0; m < count; ++m) {
+    kp[m] = keys[m] ? keys[m]->cdata() : nullptr;
+    wp[m] = weights[m]->cdata();
+  }
+  S *t0 = S::make_temp(), *t1 = S::make_temp();  // (an output may be an input)
+  const int flags = (centered ? NFLHIP_LINTRANS_CENTERED : 0) | (floor ? NFLHIP_LINTRANS_FLOOR : 0);
+  const int rc = nflhip_lintrans_ntt(P::ctx(), t0->data(), t1->data(), c0 ? c0->cdata() : nullptr, c1.cdata(), kp, wp, ks, count, 1, M - L, alpha, flags);
+  if (rc == 0) {
+    std::memcpy(static_cast<void *>(out0.data()), t0->cdata(), sizeof(S));
+    std::memcpy(static_cast<void *>(out1.data()), t1->cdata(), sizeof(S));
+  }
+  S::drop_temp(t0);
+  S::drop_temp(t1);
+  detail::check(P::ctx(), rc, "linear_transform_ntt");
+}
+template <class T, size_t D, size_t L, size_t M>
+void linear_transform_ntt(poly_p<T, D, L> &out0, poly_p<T, D, L> &out1, poly_p<T, D, L> const *c0, poly_p<T, D, L> const &c1,
+                          poly_p<T, D, M> const *const *keys, poly_p<T, D, M> const *const *weights, const uint64_t *ks, size_t count, size_t alpha,
+                          bool centered = false, bool floor = false) {
+  poly_p<T, D, M>::template linear_transform_into<L>(out0, out1, c0, c1, keys, weights, ks, count, alpha, centered, floor);
 }
 
 /* Sums of products across polynomials (include/nflhip.h): out = sum_{j < terms} a[j] * b[j], element-wise in every row -- the

@@ -459,6 +459,89 @@ int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const
                               const void *const *h_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special,
                               size_t alpha, int flags);   /* staged host variant */
 
+/* ---- weighted sums of automorphisms: several permuted inputs, each times a weight, into ONE output -------------
+ * The primitive behind linear transforms over slots (a matrix-vector product by diagonals, the inner sums of BSGS, CoeffToSlot):
+ *     out[g][j][i] = addend[g][j][i] + sum_{t < terms} w_t[j][i] * in_t[g][j][src_{k_t}(i)]      mod p_j, canonical,
+ * where in_t[..][src_k(i)] is what nflhip_automorphism_dev with NFLHIP_FORM_NTT writes at i (2 rev(src_k(i)) + 1 =
+ * k (2 rev(i) + 1) mod 2 degree), g < batch, j < rows, i < degree.
+ *   rows          the number of leading moduli the layout covers, 1 <= rows <= nmoduli
+ *   ins[t], out, addend   [batch][rows][degree], canonical words
+ *   weights[t]    [>= rows][degree] with row stride degree, shared by the batch; rows past `rows` are not read
+ *   ins, weights, ks      HOST arrays; 1 <= terms <= NFLHIP_MAC_MAX_TERMS; every ks[t] odd, taken mod 2 degree; k = 1 is allowed;
+ *                 ins may repeat, weights may repeat
+ *   addend        may be NULL, and may be `out` exactly (accumulation in place)
+ * The products are accumulated unreduced in a double-width word and reduced once (16 terms never wrap it, see "sums of
+ * products"); the result is exact.  One launch; the pointers travel by value in the kernel arguments, nothing is allocated and
+ * the call can be captured into a hipGraph.  flags: 0, or NFLHIP_MAC_DOUBLE_BUFFER (two staging buffers, the next term's loads in
+ * flight while a term is consumed, instead of one: the alternative the default was measured against and ahead of; same words).
+ * NFLHIP_ERR_INVALID, nothing enqueued: a NULL context or pointer with batch != 0 (except addend), terms == 0 or > 16, rows == 0
+ * or > nmoduli, an even k, unknown flag bits, a size that overflows size_t, a cyclic row context, the addend overlapping `out`
+ * without being `out`, `out` overlapping an input or a weight.  batch == 0 returns NFLHIP_OK and touches nothing.
+ * The host variant stages every input, every weight, the addend and the output. */
+#define NFLHIP_MAC_MAX_TERMS 16
+#define NFLHIP_MAC_DOUBLE_BUFFER 0x1
+int nflhip_automorphism_mac_dev(nflhip_ctx *ctx, void *d_out, const void *d_addend, const void *const *d_ins,
+                                const void *const *d_weights, const uint64_t *ks, size_t terms, size_t batch, size_t rows,
+                                int flags, void *stream);
+int nflhip_automorphism_mac(nflhip_ctx *ctx, void *h_out, const void *h_addend, const void *const *h_ins,
+                            const void *const *h_weights, const uint64_t *ks, size_t terms, size_t batch, size_t rows,
+                            int flags);   /* staged host variant */
+
+/* ---- slot linear transforms: weighted sums of rotations, one mod-down ---------------------------
+ * sum_m pt_m (.) sigma_{k_m}(ct) for plaintext diagonals pt_m in one call: what the callers of hoisted rotations want, without
+ * the rotations themselves.  The key-switch sums are multiplied by the diagonals and added up while they are still in the
+ * extended basis (all nmoduli rows), then modded down ONCE ("double hoisting"): 2 batch polynomials for any count.
+ * The context, k_special, L = nmoduli - k_special, the digits of alpha rows and dnum are those of the key switch above.
+ *   c0, c1, out0, out1   [batch][L][degree], NTT form; c0 may be NULL
+ *   keys[m]       [dnum][2][nmoduli][degree], the key convention of the hoisted rotations (from s to sigma_(k^-1)(s)); NULL if
+ *                 and only if ks[m] = 1 mod 2 degree is meant as the unrotated diagonal, which needs no key switch (a HOST array)
+ *   weights[m]    [nmoduli][degree], the diagonal in NTT form over ALL nmoduli moduli, shared by the batch (a HOST array)
+ *   ks[m]         odd, taken mod 2 degree (a HOST array); m < count <= NFLHIP_LINTRANS_MAX_TERMS
+ * Definition, word for word ("keyed": keys[m] != NULL):
+ *     U_d     as nflhip_keyswitch_ntt_dev forms it from c1                                 (nmoduli rows)
+ *     S_{m,c} = sum_d U_d (.) keys[m][d][c]                 for keyed m                    nflhip_dot_dev, nmoduli rows
+ *     A_c     = sum_{keyed m} w_m (.) sigma^NTT_{k_m}(S_{m,c})                             nflhip_automorphism_mac_dev, rows = nmoduli
+ *     Y_c     = nflhip_moddown_ntt_dev(A_c, k_special)      (zero when no m is keyed)      NFLHIP_LINTRANS_FLOOR as NFLHIP_MODDOWN_FLOOR
+ *     out0    = Y_0 + sum_{all m} w_m (.) sigma^NTT_{k_m}(c0)     (the sum absent when c0 is NULL)      rows = L
+ *     out1    = Y_1 + sum_{unkeyed m} w_m (.) c1                                           rows = L
+ * THESE ARE NOT THE WORDS OF sum_m w_m (.) nflhip_rotate_hoisted_ntt_dev(...): one rounding of the sum replaces `count`
+ * roundings of its terms.  It is the same function of the plaintext with less noise: out0 + out1 s = sum_m pt_m sigma_{k_m}(c0 +
+ * c1 s) + e with |e| at most keyed * degree * |pt|_inf times the bound of one key switch (tests/test_lintrans_cpu.py).
+ * Plans, same words; `flags` may carry at most one plan flag:
+ *   NFLHIP_LINTRANS_SEQUENCE  the definition through existing entries: per-digit nflhip_baseconv_ntt_dev; per keyed (m, c)
+ *                             nflhip_dot_dev, nflhip_automorphism_dev on the nmoduli-row sum, nflhip_dot_dev of one term against
+ *                             the weight with the addend in place; the mod-down; nflhip_automorphism_dev and nflhip_dot_dev with
+ *                             the addend in place on the L-row child context.  No kernel of its own: the cross-check.
+ *   NFLHIP_LINTRANS_HOISTED   the mod-up once (the two routes of the hoisted rotations); ONE nflhip_dot_multi_dev-style launch into
+ *                             S = [2 keyed][batch][nmoduli][degree]; ONE launch of the weighted-sum kernel for both A_c; ONE
+ *                             nflhip_moddown_ntt_dev of 2 batch polynomials straight into out0 / out1 when out1 follows out0 in
+ *                             memory, else two; the weighted-sum kernel on L rows with the addend in place, once for out0 (the
+ *                             c0 terms) and once for out1 (the unkeyed terms), where there are any.
+ *   none                      hoisted (measured ahead of the sequence for any number of keyed terms).
+ * Scratch, context-owned, in polynomials of nmoduli rows (p) and of L rows (q): hoisted
+ *     batch (1 p | 1 q) [the embedded | inverse-transformed c1]  +  batch dnum p [U]  +  2 keyed batch p [S]  +  2 batch p [A];
+ * the sequence batch (1 + dnum + 2 + 2) p + batch q; nothing when no term is keyed (the sequence: batch q when c0 is given).
+ * The first call for a (k_special, alpha, plan, modes), or for a larger batch, keyed * batch or mod-down, builds tables and
+ * allocates (it synchronises): make it before capturing into a hipGraph; while capturing it is NFLHIP_ERR_UNSUPPORTED, nothing
+ * is enqueued and the stream stays usable.  Calls on different streams are ordered on the scratch by an event; a replaying graph
+ * must not run concurrently with other linear transforms, rotations or key switches of the context.
+ * NFLHIP_ERR_INVALID, nothing enqueued: a NULL context, a NULL pointer with batch != 0 (except c0, and keys[m] where ks[m] = 1
+ * mod 2 degree), a NULL key with another k, a NULL weight, count == 0 or > 16, an even k, k_special or alpha out of range, unknown
+ * flag bits or two plan flags, a size that overflows size_t, out0 overlapping out1, an output overlapping c0, c1, a key or a
+ * weight, a cyclic row context, a repeated modulus inside a digit or among the special rows.  Keys, weights and ks may repeat.
+ * batch == 0 returns NFLHIP_OK and touches nothing.  The host variant stages c0, c1, every key, every weight and both outputs. */
+#define NFLHIP_LINTRANS_MAX_TERMS 16
+#define NFLHIP_LINTRANS_CENTERED 0x100
+#define NFLHIP_LINTRANS_FLOOR 0x200
+#define NFLHIP_LINTRANS_SEQUENCE 0x1000
+#define NFLHIP_LINTRANS_HOISTED 0x2000
+int nflhip_lintrans_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_c0, const void *d_c1,
+                            const void *const *d_keys, const void *const *d_weights, const uint64_t *ks, size_t count,
+                            size_t batch, size_t k_special, size_t alpha, int flags, void *stream);
+int nflhip_lintrans_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_c0, const void *h_c1,
+                        const void *const *h_keys, const void *const *h_weights, const uint64_t *ks, size_t count,
+                        size_t batch, size_t k_special, size_t alpha, int flags);   /* staged host variant */
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

@@ -31,6 +31,9 @@ KEYSWITCH_CENTERED, KEYSWITCH_FLOOR, KEYSWITCH_COMPOSED, KEYSWITCH_FUSED, KEYSWI
 DOT_MULTI_MAX_OUTPUTS = 32
 ROTATE_MAX_OUTPUTS = 16
 ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_SEQUENCE, ROTATE_HOISTED = 0x100, 0x200, 0x1000, 0x2000
+MAC_MAX_TERMS, MAC_DOUBLE_BUFFER = 16, 0x1
+LINTRANS_MAX_TERMS = 16
+LINTRANS_CENTERED, LINTRANS_FLOOR, LINTRANS_SEQUENCE, LINTRANS_HOISTED = 0x100, 0x200, 0x1000, 0x2000
 
 
 class DotOperand(C.Structure):
@@ -83,6 +86,10 @@ SYMBOLS = [
     ("nflhip_keyswitch_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i]),
     ("nflhip_rotate_hoisted_ntt_dev", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i, _vp]),
     ("nflhip_rotate_hoisted_ntt", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i]),
+    ("nflhip_automorphism_mac_dev", _i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_automorphism_mac", _i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _i]),
+    ("nflhip_lintrans_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_lintrans_ntt", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i]),
     ("nflhip_gadget_mul_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),

@@ -388,7 +388,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch, nflhip::warm_dot_multi, nflhip::warm_rotate};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch, nflhip::warm_dot_multi, nflhip::warm_rotate, nflhip::warm_lintrans};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -499,7 +499,9 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   ctx->bconv.clear();
   if (ctx->ev_ks) (void)hipEventDestroy(ctx->ev_ks);
   if (ctx->ev_rot) (void)hipEventDestroy(ctx->ev_rot);
+  if (ctx->ev_lt) (void)hipEventDestroy(ctx->ev_lt);
   if (ctx->rot_scratch) (void)hipFree(ctx->rot_scratch);
+  if (ctx->lt_scratch) (void)hipFree(ctx->lt_scratch);
   if (ctx->ks_scratch) (void)hipFree(ctx->ks_scratch);
   for (auto &kv : ctx->ks_recs) (void)hipFree(kv.second);
   ctx->ks_recs.clear();
@@ -1367,6 +1369,212 @@ int nflhip_rotate_hoisted_ntt_dev(nflhip_ctx *ctx, void *const *d_out0s, void *c
   int rc = rotate_check(ctx, d_out0s, d_out1s, d_c0, d_c1, d_keys, ks, count, batch, k_special, alpha, flags);  // in full, before any device use
   if (rc || batch == 0) return rc;
   return rotate_run(ctx, d_out0s, d_out1s, d_c0, d_c1, d_keys, ks, count, batch, k_special, alpha, flags, (hipStream_t)stream);
+}
+
+// The weighted sum of NTT-form automorphisms (kernels_lintrans.hip; include/nflhip.h "weighted sums of automorphisms"): one launch,
+// the pointers in the kernel arguments, nothing allocated.
+int nflhip_automorphism_mac_dev(nflhip_ctx *ctx, void *d_out, const void *d_addend, const void *const *d_ins, const void *const *d_weights,
+                                const uint64_t *ks, size_t terms, size_t batch, size_t rows, int flags, void *stream) {
+  int rc = mac_check(ctx, d_out, d_addend, d_ins, d_weights, ks, terms, batch, rows, flags);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_permute_mac_ntt<T>(ctx->shape, ctx->tabs, (T *)d_out, (const T *)d_addend, (const T *const *)d_ins, (const T *const *)d_weights, ks,
+                                     (int)terms, batch, rows, 1, 0, 0, (flags & NFLHIP_MAC_DOUBLE_BUFFER) != 0, (hipStream_t)stream);
+  });
+  if (e != hipSuccess) return hipfail(ctx, e, "automorphism_mac");
+  return NFLHIP_OK;
+}
+
+// Slot linear transforms (kernels_lintrans.hip; include/nflhip.h "slot linear transforms"): the key-switch sums of one c1 against up to
+// 16 keys, each permuted, multiplied by its plaintext diagonal and added up WHILE STILL ON ALL nm ROWS, then ONE mod-down of the two
+// sums; the c0 terms and the unkeyed (k = 1, NULL key) terms are added on the L rows afterwards.  Two plans with the same words:
+//   sequence  X = c1 embedded in nm rows, per-digit nflhip_baseconv_ntt_dev into U = [dnum][batch][nm][n]; per keyed (m, c)
+//             nflhip_dot_dev into T, nflhip_automorphism_dev into P, nflhip_dot_dev (one term, the addend in place) of P against the
+//             weight into A = [2][batch][nm][n]; nflhip_moddown_ntt_dev; per term nflhip_automorphism_dev of c0 and nflhip_dot_dev
+//             with the addend in place on the child context over rows [0, L)
+//   hoisted   the mod-up by the two routes of rotate_run into U; k_dot_multi into S = [2 keyed][batch][nm][n]; k_permute_mac_ntt with
+//             blockIdx.y the component into A; one mod-down straight into out0 / out1; k_permute_mac_ntt on L rows, the addend in
+//             place, once for out0 (the c0 terms) and once for out1 (the unkeyed terms), where there are any
+// Default: hoisted, always.  The starting rule (hoisted from two keyed terms on) did not survive the measurement: with ONE keyed term
+// the hoisted plan measured x1.07 - x1.18 against the sequence, well beyond the blocks' spread, and with none it is the one-launch
+// primitive against a loop of automorphism + dot (profiles/r16_lintrans.txt).  The sequence is the cross-check.
+// Lock order: lt_mu, then ks_mu, then bcn_mu.
+static int lintrans_run(nflhip_ctx *ctx, void *out0, void *out1, const void *c0, const void *c1, const void *const *keys, const void *const *weights,
+                        const uint64_t *ks, size_t count, size_t batch, size_t K, size_t alpha, int flags, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->lt_mu);
+  const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha, row = ctx->shape.n * ctx->word, pb = nm * row, qb = L * row;
+  const bool centred = (flags & NFLHIP_LINTRANS_CENTERED) != 0, floor = (flags & NFLHIP_LINTRANS_FLOOR) != 0, cap = is_capturing(st);
+  const uint64_t *const *recs = nullptr;
+  int rc;
+  {  // the tables first: a repeated modulus is refused with the builder's message before anything is enqueued
+    std::lock_guard<std::mutex> l2(ctx->ks_mu);
+    try {
+      rc = keyswitch_records(ctx, K, alpha, st, &recs);
+    } catch (const std::bad_alloc &) {
+      return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+    }
+  }
+  if (rc) return rc;
+  // the keyed terms, in order; the rest are the unrotated diagonals
+  const void *kkeys[NFLHIP_LINTRANS_MAX_TERMS], *kw[NFLHIP_LINTRANS_MAX_TERMS], *uw[NFLHIP_LINTRANS_MAX_TERMS], *uin[NFLHIP_LINTRANS_MAX_TERMS],
+      *cin[NFLHIP_LINTRANS_MAX_TERMS];
+  uint64_t kks[NFLHIP_LINTRANS_MAX_TERMS], uks[NFLHIP_LINTRANS_MAX_TERMS];
+  size_t keyed = 0, unkeyed = 0;
+  for (size_t m = 0; m < count; ++m) {
+    cin[m] = c0;
+    if (keys[m]) {
+      kkeys[keyed] = keys[m];
+      kw[keyed] = weights[m];
+      kks[keyed++] = ks[m];
+    } else {
+      uw[unkeyed] = weights[m];
+      uin[unkeyed] = c1;
+      uks[unkeyed++] = 1;
+    }
+  }
+  int plan = flags & (NFLHIP_LINTRANS_SEQUENCE | NFLHIP_LINTRANS_HOISTED);
+  if (!plan) plan = NFLHIP_LINTRANS_HOISTED;
+  const int modes = flags & (NFLHIP_LINTRANS_CENTERED | NFLHIP_LINTRANS_FLOOR);
+  const bool adjacent = (char *)out1 == (char *)out0 + batch * qb;
+  const size_t down = keyed ? (adjacent ? 2 * batch : batch) : 0;  // the polynomials of one mod-down call
+  // what a call while capturing may do: repeat a (k_special, alpha, plan, modes) already served at this batch, keyed * batch and mod-down or larger
+  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes)};
+  auto wit = ctx->lt_warm.find(wkey);
+  if (cap && (wit == ctx->lt_warm.end() || wit->second[0] < batch || wit->second[1] < keyed * batch || wit->second[2] < down))
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "lintrans: the first call for a (k_special, alpha, plan), or for a larger batch, allocates, which a stream capture cannot do");
+  const bool seq = plan == NFLHIP_LINTRANS_SEQUENCE, perdigit = seq || (!ctx->shape.compiled_only && ctx->shape.n <= 2048);
+  // sequence: X, U, T, P, A and the permuted c0 on L rows; hoisted: X, U, S, A
+  const size_t xb = !keyed ? 0 : perdigit ? batch * pb : batch * qb, ub = keyed ? batch * dnum * pb : 0;
+  const size_t sb = !keyed ? 0 : seq ? 2 * batch * pb : 2 * keyed * batch * pb, ab = keyed ? 2 * batch * pb : 0, tb = seq && c0 ? batch * qb : 0;
+  const size_t need = xb + ub + sb + ab + tb;
+  if ((rc = set_device(ctx))) return rc;
+  nflhip_ctx *child = nullptr;
+  {
+    std::lock_guard<std::mutex> l2(ctx->bcn_mu);
+    if ((rc = bcn_child(ctx, 0, L, cap, &child))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+  }
+  if (ctx->lt_scratch_bytes < need) {
+    if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "lintrans: the scratch has to grow, which a stream capture cannot do");
+    if (ctx->lt_scratch) HIPCHK(ctx, hipFree(ctx->lt_scratch));  // (synchronises: nothing still reads it)
+    ctx->lt_scratch = nullptr;
+    ctx->lt_scratch_bytes = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->lt_scratch, need));
+    ctx->lt_scratch_bytes = need;
+  }
+  if (!ctx->ev_lt) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_lt, hipEventDisableTiming));
+  if (!cap && ctx->ev_lt_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_lt, 0));  // a previous call on another stream
+  char *X = (char *)ctx->lt_scratch, *U = X + xb, *S = U + ub, *A = S + sb, *T0 = A + ab;
+  const size_t pw = pb / ctx->word;  // words of a polynomial of nm rows
+  if (keyed) {
+    size_t a_gs, a_ts;  // U's layout: the strides of the digits operand, in polynomials
+    if (perdigit) {
+      HIPCHK(ctx, hipMemcpy2DAsync(X, pb, c1, qb, qb, batch, hipMemcpyDeviceToDevice, st));
+      for (size_t d = 0; d < dnum; ++d)
+        if ((rc = nflhip_baseconv_ntt_dev(ctx, U + d * batch * pb, X, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm,
+                                          centred ? NFLHIP_BASECONV_CENTERED : 0, st)))
+          return rc;
+      a_gs = 1, a_ts = batch;
+    } else {
+      HIPCHK(ctx, hipMemcpyAsync(X, c1, batch * qb, hipMemcpyDeviceToDevice, st));
+      if ((rc = nflhip_ntt_inv_dev(child, X, batch, st)) || (rc = set_device(ctx))) return rc;
+      hipError_t e = with_limb(ctx, [&](auto z) {
+        typedef decltype(z) T;
+        return launch_modup_digits<T>(ctx->shape, ctx->tabs, (T *)U, (const T *)X, recs, batch, L, alpha, centred, st);
+      });
+      if (e != hipSuccess) return hipfail(ctx, e, "lintrans: mod-up");
+      if ((rc = nflhip_ntt_fwd_dev(ctx, U, batch * dnum, st))) return rc;
+      a_gs = dnum, a_ts = 1;
+    }
+    if ((rc = set_device(ctx))) return rc;
+    if (seq) {
+      char *T = S, *P = S + batch * pb;
+      const nflhip_dot_operand a = {U, a_gs, a_ts}, pa = {P, 1, 0};
+      for (size_t m = 0; m < keyed; ++m)
+        for (size_t c = 0; c < 2; ++c) {
+          const nflhip_dot_operand b = {(const char *)kkeys[m] + c * pb, 0, 2}, w = {kw[m], 0, 0};
+          char *Ac = A + c * batch * pb;
+          if ((rc = nflhip_dot_dev(ctx, T, &a, &b, nullptr, batch, dnum, 0, st))) return rc;
+          if ((rc = nflhip_automorphism_dev(ctx, P, T, batch, kks[m], NFLHIP_FORM_NTT, st))) return rc;
+          if ((rc = nflhip_dot_dev(ctx, Ac, &pa, &w, m ? Ac : nullptr, batch, 1, 0, st))) return rc;
+        }
+    } else {
+      void *douts[2 * NFLHIP_LINTRANS_MAX_TERMS];
+      const void *dbs[2 * NFLHIP_LINTRANS_MAX_TERMS], *mins[NFLHIP_LINTRANS_MAX_TERMS];
+      for (size_t m = 0; m < keyed; ++m) {
+        for (size_t c = 0; c < 2; ++c) {
+          douts[2 * m + c] = S + (2 * m + c) * batch * pb;
+          dbs[2 * m + c] = (const char *)kkeys[m] + c * pb;
+        }
+        mins[m] = douts[2 * m];  // component c of term m lies c batch polynomials behind
+      }
+      hipError_t e = with_limb(ctx, [&](auto z) {
+        typedef decltype(z) T;
+        hipError_t r = launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, a_gs, a_ts, (const T *const *)dbs, 2, 2 * keyed,
+                                           batch, dnum, 1, st);
+        if (r != hipSuccess) return r;
+        return launch_permute_mac_ntt<T>(ctx->shape, ctx->tabs, (T *)A, nullptr, (const T *const *)mins, (const T *const *)kw, kks, (int)keyed, batch,
+                                         nm, 2, batch * pw, batch * pw, 0, st);
+      });
+      if (e != hipSuccess) return hipfail(ctx, e, "lintrans: inner products and weighted sum");
+    }
+    const int mdflags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
+    if (adjacent) {
+      rc = nflhip_moddown_ntt_dev(ctx, out0, A, 2 * batch, K, mdflags, st);
+    } else {
+      rc = nflhip_moddown_ntt_dev(ctx, out0, A, batch, K, mdflags, st);
+      if (!rc) rc = nflhip_moddown_ntt_dev(ctx, out1, A + batch * pb, batch, K, mdflags, st);
+    }
+    if (rc || (rc = set_device(ctx))) return rc;
+  }
+  // the terms on L rows: every diagonal against sigma(c0) into out0, the unrotated unkeyed ones against c1 into out1
+  if (!keyed && !c0) HIPCHK(ctx, hipMemsetAsync(out0, 0, batch * qb, st));  // (out1 has a term: with no keyed one, every term is unkeyed)
+  if (seq) {
+    for (size_t m = 0; m < count && c0; ++m) {
+      const nflhip_dot_operand a = {T0, 1, 0}, w = {weights[m], 0, 0};
+      if ((rc = nflhip_automorphism_dev(child, T0, c0, batch, ks[m], NFLHIP_FORM_NTT, st))) return rc;
+      if ((rc = nflhip_dot_dev(child, out0, &a, &w, keyed || m ? out0 : nullptr, batch, 1, 0, st))) return rc;
+    }
+    for (size_t m = 0; m < unkeyed; ++m) {
+      const nflhip_dot_operand a = {c1, 1, 0}, w = {uw[m], 0, 0};
+      if ((rc = nflhip_dot_dev(child, out1, &a, &w, keyed || m ? out1 : nullptr, batch, 1, 0, st))) return rc;
+    }
+    if ((rc = set_device(ctx))) return rc;
+  } else {
+    hipError_t e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      hipError_t r = hipSuccess;
+      if (c0)
+        r = launch_permute_mac_ntt<T>(ctx->shape, ctx->tabs, (T *)out0, keyed ? (const T *)out0 : nullptr, (const T *const *)cin, (const T *const *)weights,
+                                      ks, (int)count, batch, L, 1, 0, 0, 0, st);
+      if (r == hipSuccess && unkeyed)
+        r = launch_permute_mac_ntt<T>(ctx->shape, ctx->tabs, (T *)out1, keyed ? (const T *)out1 : nullptr, (const T *const *)uin, (const T *const *)uw, uks,
+                                      (int)unkeyed, batch, L, 1, 0, 0, 0, st);
+      return r;
+    });
+    if (e != hipSuccess) return hipfail(ctx, e, "lintrans: the terms on the kept rows");
+  }
+  if (!cap) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev_lt, st));
+    ctx->ev_lt_valid = true;
+    try {
+      std::array<size_t, 3> &w = ctx->lt_warm[wkey];
+      if (w[0] < batch) w[0] = batch;
+      if (w[1] < keyed * batch) w[1] = keyed * batch;
+      if (w[2] < down) w[2] = down;
+    } catch (const std::bad_alloc &) {
+    }
+  }
+  return NFLHIP_OK;
+}
+int nflhip_lintrans_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_c0, const void *d_c1, const void *const *d_keys,
+                            const void *const *d_weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags,
+                            void *stream) {
+  int rc = lintrans_check(ctx, d_out0, d_out1, d_c0, d_c1, d_keys, d_weights, ks, count, batch, k_special, alpha, flags);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  return lintrans_run(ctx, d_out0, d_out1, d_c0, d_c1, d_keys, d_weights, ks, count, batch, k_special, alpha, flags, (hipStream_t)stream);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

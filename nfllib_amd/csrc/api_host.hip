@@ -508,6 +508,70 @@ int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const
   return NFLHIP_OK;
 }
 
+// weighted sums of automorphisms: every input, every weight and the output (the addend copied into it) are staged whole
+int nflhip_automorphism_mac(nflhip_ctx *ctx, void *h_out, const void *h_addend, const void *const *h_ins, const void *const *h_weights,
+                            const uint64_t *ks, size_t terms, size_t batch, size_t rows, int flags) {
+  int rc = mac_check(ctx, h_out, h_addend, h_ins, h_weights, ks, terms, batch, rows, flags);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t wb = rows * ctx->shape.n * ctx->word, ob = batch * wb;
+  Staged s(ctx);
+  if ((rc = s.in(0, nullptr, terms * ob)) || (rc = s.in(1, nullptr, terms * wb)) || (rc = s.in(2, h_addend, ob))) return rc;
+  char *i = (char *)ctx->stage[0], *w = (char *)ctx->stage[1];
+  const void *ins[NFLHIP_MAC_MAX_TERMS], *ws[NFLHIP_MAC_MAX_TERMS];
+  for (size_t t = 0; t < terms; ++t) {
+    if (ctx->stage_host[0]) std::memcpy(i + t * ob, h_ins[t], ob);
+    else HIPCHK(ctx, hipMemcpyAsync(i + t * ob, h_ins[t], ob, hipMemcpyHostToDevice, ctx->hstream));
+    if (ctx->stage_host[1]) std::memcpy(w + t * wb, h_weights[t], wb);
+    else HIPCHK(ctx, hipMemcpyAsync(w + t * wb, h_weights[t], wb, hipMemcpyHostToDevice, ctx->hstream));
+    ins[t] = i + t * ob;
+    ws[t] = w + t * wb;
+  }
+  void *o = ctx->stage[2];
+  if ((rc = nflhip_automorphism_mac_dev(ctx, o, h_addend ? o : nullptr, ins, ws, ks, terms, batch, rows, flags, (void *)ctx->hstream))) return rc;
+  return s.out(h_out, 2, ob);
+}
+
+// slot linear transforms: c1 (and c0 behind it), every key, every weight and both outputs are staged whole (the outputs share one
+// slot, out1 behind out0, so that the mod-down runs as one batch)
+int nflhip_lintrans_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_c0, const void *h_c1, const void *const *h_keys,
+                        const void *const *h_weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
+  int rc = lintrans_check(ctx, h_out0, h_out1, h_c0, h_c1, h_keys, h_weights, ks, count, batch, k_special, alpha, flags);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * (nm - k_special) * row, wb = nm * row;
+  const size_t kb = 2 * keyswitch_digits(ctx, k_special, alpha) * wb;
+  Staged s(ctx);
+  if ((rc = s.in(0, nullptr, 2 * ob)) || (rc = s.in(1, nullptr, count * (kb + wb))) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
+  char *c = (char *)ctx->stage[0], *k = (char *)ctx->stage[1], *o = (char *)ctx->stage[2];
+  auto put = [&](int slot, void *d, const void *h, size_t bytes) {
+    if (ctx->stage_host[slot]) std::memcpy(d, h, bytes);
+    else HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->hstream));
+    return (int)NFLHIP_OK;
+  };
+  if ((rc = put(0, c, h_c1, ob)) || (h_c0 && (rc = put(0, c + ob, h_c0, ob)))) return rc;
+  const void *keys[NFLHIP_LINTRANS_MAX_TERMS], *ws[NFLHIP_LINTRANS_MAX_TERMS];
+  for (size_t m = 0; m < count; ++m) {
+    char *km = k + m * (kb + wb);
+    if ((h_keys[m] && (rc = put(1, km, h_keys[m], kb))) || (rc = put(1, km + kb, h_weights[m], wb))) return rc;
+    keys[m] = h_keys[m] ? km : nullptr;
+    ws[m] = km + kb;
+  }
+  if ((rc = nflhip_lintrans_ntt_dev(ctx, o, o + ob, h_c0 ? c + ob : nullptr, c, keys, ws, ks, count, batch, k_special, alpha, flags, (void *)ctx->hstream)))
+    return rc;
+  if (!ctx->stage_host[2]) {
+    HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out1, o + ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
+  s.pending = false;
+  if (ctx->stage_host[2]) {
+    std::memcpy(h_out0, o, ob);
+    std::memcpy(h_out1, o + ob, ob);
+  }
+  return NFLHIP_OK;
+}
+
 // sums of products across polynomials: the operands are `terms` times the size of the result, so the call is staged whole
 int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, size_t groups, size_t terms, int b_shared) {
   if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");

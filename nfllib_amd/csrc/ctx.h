@@ -104,6 +104,15 @@ struct nflhip_ctx {
   size_t rot_scratch_bytes = 0;
   hipEvent_t ev_rot = nullptr;
   bool ev_rot_valid = false;
+  // slot linear transforms (api.hip lintrans_run): per (k_special, alpha, plan | modes) the largest batch, the largest keyed * batch and
+  // the largest mod-down served so far (what a call while capturing may repeat); one scratch for the mod-up's input, the digits, the
+  // key-switch sums and the two accumulated sums, calls ordered on it by ev_lt.  All under lt_mu, which is taken BEFORE ks_mu and bcn_mu.
+  std::mutex lt_mu;
+  std::map<std::array<size_t, 3>, std::array<size_t, 3>> lt_warm;
+  void *lt_scratch = nullptr;
+  size_t lt_scratch_bytes = 0;
+  hipEvent_t ev_lt = nullptr;
+  bool ev_lt_valid = false;
 };
 
 void pipe_destroy(nflhip_ctx *ctx);  // api_host.hip: frees the context's host-pointer pipeline
@@ -359,6 +368,71 @@ inline int rotate_check(const nflhip_ctx *ctx, void *const *out0s, void *const *
       if (ranges_overlap(o, ob, keys[q], kb)) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: an output overlaps a key");
     for (size_t q = 0; q < m; ++q)
       if (ranges_overlap(o, ob, q < count ? out0s[q] : out1s[q - count], ob)) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: two outputs overlap");
+  }
+  return NFLHIP_OK;
+}
+// nflhip_automorphism_mac_dev / nflhip_automorphism_mac: every argument check, before any device use
+inline int mac_check(const nflhip_ctx *ctx, const void *out, const void *addend, const void *const *ins, const void *const *weights,
+                     const uint64_t *ks, size_t terms, size_t batch, size_t rows, int flags) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac: not on a cyclic row context");
+  if (flags & ~NFLHIP_MAC_DOUBLE_BUFFER) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac: unknown flag bits");
+  if (terms == 0 || terms > NFLHIP_MAC_MAX_TERMS) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac: the number of terms is out of range (1 to 16)");
+  if (rows == 0 || rows > ctx->shape.nm) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac: rows is out of range (1 to nmoduli)");
+  if (batch == 0) return NFLHIP_OK;
+  if (!ks) return fail(ctx, NFLHIP_ERR_INVALID, "NULL multiplier array");
+  for (size_t t = 0; t < terms; ++t)
+    if ((ks[t] & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac: the exponent k must be odd");
+  if (!out || !ins || !weights) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  for (size_t t = 0; t < terms; ++t)
+    if (!ins[t] || !weights[t]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t row = ctx->shape.n * ctx->word, wb = rows * row;
+  size_t ob;
+  if (__builtin_mul_overflow(batch, wb, &ob)) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac: the size overflows");
+  if (addend && addend != out && ranges_overlap(out, ob, addend, ob))
+    return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac: the addend overlaps the output without being the output");
+  for (size_t t = 0; t < terms; ++t)
+    if (ranges_overlap(out, ob, ins[t], ob) || ranges_overlap(out, ob, weights[t], wb))
+      return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac: the output overlaps an input or a weight");
+  return NFLHIP_OK;
+}
+// nflhip_lintrans_ntt_dev / nflhip_lintrans_ntt: every argument check short of the tables (a repeated modulus is found by their
+// builder, api.hip keyswitch_records), before any device use
+inline int lintrans_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *c0, const void *c1, const void *const *keys,
+                          const void *const *weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: a cyclic row context has no modulus chain");
+  const int plans = NFLHIP_LINTRANS_SEQUENCE | NFLHIP_LINTRANS_HOISTED, plan = flags & plans;
+  if (flags & ~(plans | NFLHIP_LINTRANS_CENTERED | NFLHIP_LINTRANS_FLOOR)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: unknown flag bits");
+  if (plan == plans) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: one plan flag at most");
+  if (count == 0 || count > NFLHIP_LINTRANS_MAX_TERMS) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: the number of terms is out of range (1 to 16)");
+  const size_t nm = ctx->shape.nm, dnum = keyswitch_digits(ctx, k_special, alpha);
+  if (k_special == 0 || k_special >= nm) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: k_special is out of range (1 to nmoduli - 1)");
+  if (dnum == 0) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: alpha is out of range (1 to nmoduli - k_special)");
+  if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: more than 65535 rows");
+  if (batch == 0) return NFLHIP_OK;
+  if (!ks) return fail(ctx, NFLHIP_ERR_INVALID, "NULL multiplier array");
+  for (size_t m = 0; m < count; ++m)
+    if ((ks[m] & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: the exponent k must be odd");
+  if (!out0 || !out1 || !c1 || !keys || !weights) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  for (size_t m = 0; m < count; ++m) {
+    if (!weights[m]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+    if (!keys[m] && (ks[m] & (2 * ctx->shape.n - 1)) != 1)
+      return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: a NULL key goes with k = 1 mod 2 degree only (the unrotated diagonal)");
+  }
+  const size_t row = ctx->shape.n * ctx->word, L = nm - k_special, wb = nm * row;
+  size_t ob, sb, kb, polys;
+  // (sb: the largest scratch of either plan -- [batch][dnum + 6 + 2 count][nm][n])
+  if (__builtin_mul_overflow(batch, L * row, &ob) || __builtin_mul_overflow(batch, dnum + 6 + 2 * count, &polys) ||
+      __builtin_mul_overflow(polys, wb, &sb) || __builtin_mul_overflow(2 * dnum, wb, &kb))
+    return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: the size overflows");
+  if (ranges_overlap(out0, ob, out1, ob)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: the two outputs overlap");
+  for (const void *o : {out0, out1}) {
+    if ((c0 && ranges_overlap(o, ob, c0, ob)) || ranges_overlap(o, ob, c1, ob)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: an output overlaps c0 or c1");
+    for (size_t m = 0; m < count; ++m) {
+      if (keys[m] && ranges_overlap(o, ob, keys[m], kb)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: an output overlaps a key");
+      if (ranges_overlap(o, ob, weights[m], wb)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: an output overlaps a weight");
+    }
   }
   return NFLHIP_OK;
 }

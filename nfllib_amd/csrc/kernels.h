@@ -124,6 +124,17 @@ constexpr int kRotateMaxPairs = 32;
 template <typename T>
 hipError_t launch_permute_add_ntt(const Shape &s, const DevTables &t, T *const *outs, const T *const *ins, const uint64_t *ks, unsigned add_mask,
                                   int pairs, const T *c0, size_t L, size_t batch, hipStream_t st);
+// the weighted sum of NTT-form automorphisms (kernels_lintrans.hip; include/nflhip.h "weighted sums of automorphisms"): for every
+// component c < comps, out + c out_cs = (addend + c out_cs) + sum_{t < terms} weights[t] (.) sigma^NTT_{ks[t]}(ins[t] + c in_cs), every
+// block [batch][R][n] in the dense layout over the first R moduli of the context, weights[t] = [>= R][n]; the strides in words;
+// addend nullptr or out itself or apart from it.  HOST arrays of device pointers, which travel in the kernel arguments.  out may
+// overlap no input and no weight (api.hip checks).  double_buffer: two staging buffers instead of one (the measured alternative).
+// hipErrorInvalidValue for an even k
+constexpr int kMacMaxTerms = 16;
+template <typename T>
+hipError_t launch_permute_mac_ntt(const Shape &s, const DevTables &t, T *out, const T *addend, const T *const *ins, const T *const *weights,
+                                  const uint64_t *ks, int terms, size_t batch, size_t R, size_t comps, size_t in_cs, size_t out_cs,
+                                  int double_buffer, hipStream_t st);
 // gadget decomposition (kernels_decompose.hip; include/nflhip.h "gadget decomposition"): in = [batch][nm][n] canonical words in
 // coefficient form, digit width 1 <= w <= limb_bits - 3, l = ceil((limb_bits - 2) / w), terms = nm l; sgn: balanced digits.
 // _words: out = [batch][terms][nm][n], the digit spread over every row (coefficient form).  _compact: out = [batch][terms][n] of
@@ -333,6 +344,7 @@ hipError_t warm_rescale(hipStream_t st);
 hipError_t warm_dot(hipStream_t st);
 hipError_t warm_dot_multi(hipStream_t st);
 hipError_t warm_rotate(hipStream_t st);
+hipError_t warm_lintrans(hipStream_t st);
 hipError_t warm_decompose(hipStream_t st);
 hipError_t warm_baseconv(hipStream_t st);
 hipError_t warm_baseconv_ntt(hipStream_t st);

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (DOT_MULTI_MAX_OUTPUTS, ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_HOISTED, ROTATE_MAX_OUTPUTS, ROTATE_SEQUENCE, KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
+from ._lib import (LINTRANS_CENTERED, LINTRANS_FLOOR, LINTRANS_HOISTED, LINTRANS_MAX_TERMS, LINTRANS_SEQUENCE, MAC_MAX_TERMS, MAC_DOUBLE_BUFFER, DOT_MULTI_MAX_OUTPUTS, ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_HOISTED, ROTATE_MAX_OUTPUTS, ROTATE_SEQUENCE, KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -485,6 +485,108 @@ class Engine:
         self._chk(self.lib.nflhip_rotate_hoisted_ntt(self.ctx, p0, p1, _vp(c0), _vp(c1), pk, kv, len(ks), batch, k_special, alpha,
                                                      self._rot_flags(centered, floor, plan)))
         return outs
+
+    # ---- weighted sums of automorphisms and slot linear transforms (include/nflhip.h "weighted sums of automorphisms", "slot
+    # linear transforms") ----
+    def automorphism_mac(self, ins, weights, ks, addend=None, out=None, rows=None, double_buffer=False, stream=None):
+        """addend + sum_t weights[t] * sigma_ks[t](ins[t]) on NTT-form data in ONE launch (at most 16 terms): every ins[t] a contiguous
+        [batch, rows, n] tensor over the first `rows` moduli (default: all), every weights[t] a [>= rows, n] tensor shared by the
+        batch.  ins may repeat; addend may be `out` itself; out must not overlap an input or a weight.  double_buffer=True stages
+        through two buffers instead of one (same words)."""
+        ins, weights, ks = list(ins), list(weights), [self._k(k) for k in ks]
+        rows = self.nmoduli if rows is None else int(rows)
+        if not (len(ins) == len(weights) == len(ks)) or not 1 <= len(ks) <= MAC_MAX_TERMS:
+            raise ValueError("one input and one weight per multiplier, 1 to 16 terms")
+        if not 1 <= rows <= self.nmoduli or any(x.numel() != ins[0].numel() or x.numel() % (rows * self.degree) or not x.is_contiguous() for x in ins):
+            raise ValueError("every input is a contiguous [batch, rows, n] tensor, 1 <= rows <= nm")
+        if any(w.numel() < rows * self.degree or not w.is_contiguous() for w in weights):
+            raise ValueError("every weight is a contiguous tensor of at least rows * n words")
+        batch = ins[0].numel() // (rows * self.degree)
+        if out is None:
+            out = _torch().empty((batch, rows, self.degree), dtype=self.torch_dtype, device=ins[0].device)
+        pi = (C.c_void_p * len(ks))(*[x.data_ptr() for x in ins])
+        pw = (C.c_void_p * len(ks))(*[w.data_ptr() for w in weights])
+        kv = (C.c_uint64 * len(ks))(*ks)
+        self._chk(self.lib.nflhip_automorphism_mac_dev(self.ctx, _vp(out), _vp(addend), pi, pw, kv, len(ks), batch, rows,
+                                                       MAC_DOUBLE_BUFFER if double_buffer else 0, self._stream(stream)))
+        return out
+
+    def h_automorphism_mac(self, ins, weights, ks, addend=None, rows=None):
+        """host-pointer variant: numpy ins[t] = [batch, rows, n], weights[t] = [>= rows, n] -> [batch, rows, n]"""
+        ins = [np.ascontiguousarray(x, dtype=self.np_dtype) for x in ins]
+        weights, ks = [np.ascontiguousarray(w, dtype=self.np_dtype) for w in weights], [self._k(k) for k in ks]
+        rows = self.nmoduli if rows is None else int(rows)
+        if not (len(ins) == len(weights) == len(ks)) or not 1 <= len(ks) <= MAC_MAX_TERMS:
+            raise ValueError("one input and one weight per multiplier, 1 to 16 terms")
+        if not 1 <= rows <= self.nmoduli or any(x.size != ins[0].size or x.size % (rows * self.degree) for x in ins) or \
+                any(w.size < rows * self.degree for w in weights):
+            raise ValueError("every input is [batch, rows, n], every weight [>= rows, n]")
+        batch = ins[0].size // (rows * self.degree)
+        addend = None if addend is None else np.ascontiguousarray(addend, dtype=self.np_dtype)
+        out = np.empty((batch, rows, self.degree), dtype=self.np_dtype)
+        pi = (C.c_void_p * len(ks))(*[x.ctypes.data for x in ins])
+        pw = (C.c_void_p * len(ks))(*[w.ctypes.data for w in weights])
+        kv = (C.c_uint64 * len(ks))(*ks)
+        self._chk(self.lib.nflhip_automorphism_mac(self.ctx, _vp(out), _vp(addend), pi, pw, kv, len(ks), batch, rows, 0))
+        return out
+
+    _LT_PLAN = {None: 0, "sequence": LINTRANS_SEQUENCE, "hoisted": LINTRANS_HOISTED}
+
+    def _lt_flags(self, centered, floor, plan):
+        return (LINTRANS_CENTERED if centered else 0) | (LINTRANS_FLOOR if floor else 0) | self._LT_PLAN[plan]
+
+    def linear_transform_ntt(self, c0, c1, keys, weights, ks, k_special, alpha, centered=False, floor=False, out=None, plan=None, stream=None):
+        """sum_m weights[m] * sigma_ks[m](ciphertext) in one call with ONE mod-down: (c0, c1) NTT-form [batch, L, n] batches with
+        L = nm - k_special (c0 may be None); keys[m] = [dnum, 2, nm, n] by the convention of rotate_hoisted_ntt, or None for the
+        unrotated diagonal (ks[m] = 1, no key switch); weights[m] = [nm, n], the diagonal in NTT form over all nm moduli (at most
+        16 terms).  The key-switch sums are weighted and added on all nm rows before the mod-down, so the words differ from a
+        weighted sum of rotate_hoisted_ntt results by that one rounding.  Returns (out0, out1), each [batch, L, n]; `out` = a
+        pair of such tensors, else both are views of one new [2, batch, L, n] tensor.  plan "sequence" / "hoisted" forces a
+        plan.  The first call for a (k_special, alpha), or a larger batch or count, allocates: make it before a graph capture."""
+        L = self.nmoduli - k_special
+        keys, weights, ks = list(keys), list(weights), [self._k(k) for k in ks]
+        if L <= 0 or c1.numel() % (L * self.degree) or not c1.is_contiguous() or (c0 is not None and (c0.shape != c1.shape or not c0.is_contiguous())):
+            raise ValueError("c0 and c1 are contiguous [batch, nm - k_special, n] tensors")
+        if not (len(keys) == len(weights) == len(ks)) or not 1 <= len(ks) <= LINTRANS_MAX_TERMS:
+            raise ValueError("one key (or None) and one weight per term, 1 to 16 terms")
+        batch = c1.numel() // (L * self.degree)
+        kwords = 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly
+        if any(k is not None and (k.numel() != kwords or not k.is_contiguous()) for k in keys):
+            raise ValueError("every key holds dnum * 2 polynomials of this context")
+        if any(w.numel() != self.words_per_poly or not w.is_contiguous() for w in weights):
+            raise ValueError("every weight is one polynomial of this context")
+        if out is None:
+            both = _torch().empty((2, batch, L, self.degree), dtype=self.torch_dtype, device=c1.device)
+            out = (both[0], both[1])
+        pk = (C.c_void_p * len(ks))(*[None if k is None else k.data_ptr() for k in keys])
+        pw = (C.c_void_p * len(ks))(*[w.data_ptr() for w in weights])
+        kv = (C.c_uint64 * len(ks))(*ks)
+        self._chk(self.lib.nflhip_lintrans_ntt_dev(self.ctx, _vp(out[0]), _vp(out[1]), _vp(c0), _vp(c1), pk, pw, kv, len(ks), batch, k_special,
+                                                   alpha, self._lt_flags(centered, floor, plan), self._stream(stream)))
+        return out
+
+    def h_linear_transform_ntt(self, c0, c1, keys, weights, ks, k_special, alpha, centered=False, floor=False, plan=None):
+        """host-pointer variant: numpy c0 (or None), c1 = [batch, L, n], keys[m] = [dnum, 2, nm, n] or None, weights[m] = [nm, n]
+        -> (out0, out1)"""
+        c1 = np.ascontiguousarray(c1, dtype=self.np_dtype)
+        c0 = None if c0 is None else np.ascontiguousarray(c0, dtype=self.np_dtype)
+        keys = [None if k is None else np.ascontiguousarray(k, dtype=self.np_dtype) for k in keys]
+        weights, ks = [np.ascontiguousarray(w, dtype=self.np_dtype) for w in weights], [self._k(k) for k in ks]
+        L = self.nmoduli - k_special
+        kwords = 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly
+        if L <= 0 or c1.size % (L * self.degree) or (c0 is not None and c0.shape != c1.shape) or \
+                any(k is not None and k.size != kwords for k in keys) or any(w.size != self.words_per_poly for w in weights):
+            raise ValueError("c0, c1 are [batch, nm - k_special, n], every key [dnum, 2, nm, n] or None, every weight [nm, n]")
+        if not (len(keys) == len(weights) == len(ks)) or not 1 <= len(ks) <= LINTRANS_MAX_TERMS:
+            raise ValueError("one key (or None) and one weight per term, 1 to 16 terms")
+        batch = c1.size // (L * self.degree)
+        out0, out1 = (np.empty((batch, L, self.degree), dtype=self.np_dtype) for _ in range(2))
+        pk = (C.c_void_p * len(ks))(*[None if k is None else k.ctypes.data for k in keys])
+        pw = (C.c_void_p * len(ks))(*[w.ctypes.data for w in weights])
+        kv = (C.c_uint64 * len(ks))(*ks)
+        self._chk(self.lib.nflhip_lintrans_ntt(self.ctx, _vp(out0), _vp(out1), _vp(c0), _vp(c1), pk, pw, kv, len(ks), batch, k_special, alpha,
+                                               self._lt_flags(centered, floor, plan)))
+        return out0, out1
 
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
         out = out if out is not None else _torch().empty_like(a)
