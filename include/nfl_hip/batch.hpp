@@ -267,6 +267,37 @@ template <class P> class device_batch {
                                                     Q::nmoduli - P::nmoduli, alpha, flags, w0.queue()), "linear_transform_ntt");
     w0.sync();
   }
+  // Ciphertext multiplication with relinearisation (include/nflhip.h "ciphertext multiplication"): a0, a1, b0, b1 are batches of this
+  // ring (L moduli) of one size -- b0 == b1 == NULL: the square --, key a batch of the ring with M > L moduli holding the 2 dnum
+  // polynomials of the key from s^2 to s in [term][component] order, shared by the whole batch.  out0, out1 are batches of this ring,
+  // or of the ring with L - 1 moduli: then the result is rescaled by the last kept modulus in the same rounding.  An output may be
+  // one of the inputs.  Streams as in assign_key_switch.
+  template <class O, class Q>
+  static void assign_mul_relin(device_batch<O> &out0, device_batch<O> &out1, const device_batch &a0, const device_batch &a1, const device_batch *b0,
+                               const device_batch *b1, const device_batch<Q> &key, size_t alpha, bool centered = false, bool floor = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && Q::nmoduli > P::nmoduli,
+                  "assign_mul_relin: the key's ring has the same limbs and degree and at least one modulus more");
+    static_assert(std::is_same<typename O::value_type, value_type>::value && O::degree == P::degree &&
+                      (O::nmoduli == P::nmoduli || O::nmoduli + 1 == P::nmoduli),
+                  "assign_mul_relin: the outputs live in the inputs' ring, or in the ring with one modulus less (the rescale)");
+    if (alpha == 0 || alpha > P::nmoduli) throw std::runtime_error("nfl(hip): mul_relin: alpha is out of range (1 to the inputs' moduli)");
+    if (!b0 != !b1) throw std::runtime_error("nfl(hip): mul_relin: b0 and b1 are both given, or both NULL for the square");
+    if (out0.size() != a0.size() || out1.size() != a0.size() || a1.size() != a0.size() || (b0 && (b0->size() != a0.size() || b1->size() != a0.size())))
+      throw std::runtime_error("nfl(hip): batch sizes differ");
+    if (key.size() != 2 * ((P::nmoduli + alpha - 1) / alpha)) throw std::runtime_error("nfl(hip): the key batch holds 2 * dnum polynomials");
+    if (out0.device() != key.device() || out1.device() != key.device() || a0.device() != key.device() || a1.device() != key.device() ||
+        (b0 && (b0->device() != key.device() || b1->device() != key.device())))
+      throw std::runtime_error("nfl(hip): mul_relin operands on different devices");
+    a0.sync();
+    out0.sync();
+    a0.strict("mul_relin"), a1.strict("mul_relin"), key.strict("mul_relin");
+    if (b0) b0->strict("mul_relin"), b1->strict("mul_relin");
+    const int flags = (centered ? NFLHIP_MULRELIN_CENTERED : 0) | (floor ? NFLHIP_MULRELIN_FLOOR : 0) |
+                      (O::nmoduli != P::nmoduli ? NFLHIP_MULRELIN_RESCALE : 0);
+    detail::check(key.ctx(), nflhip_mulrelin_ntt_dev(key.ctx(), out0.data(), out1.data(), a0.d_, a1.d_, b0 ? b0->d_ : nullptr, b1 ? b1->d_ : nullptr,
+                                                     key.data(), a0.n_, Q::nmoduli - P::nmoduli, alpha, flags, key.queue()), "mul_relin_ntt");
+    key.sync();
+  }
   // Sums of products across polynomials (include/nflhip.h): this batch holds `groups` polynomials, a and b groups * terms each,
   // term-minor: (*this)[g] = sum_j a[g * terms + j] * b[g * terms + j].  assign_matvec: v holds the `terms` polynomials every
   // group shares, (*this)[g] = sum_j m[g * terms + j] * v[j].  The operands must be other batches.

@@ -446,6 +446,67 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out1._p = d1;
   }
 
+  // Ciphertext multiplication with relinearisation (nfl::mul_relin_ntt / square_relin_ntt / mul_relin_rescale_ntt below).  This ring
+  // type is the KEY's (NbModuli moduli, the last NbModuli - LO special); a0, a1, b0, b1 live in the ring with LO moduli (b0 == b1 ==
+  // NULL: the square), out0 and out1 in the ring with OO moduli: OO == LO, or OO == LO - 1 for the rescale in the same rounding.  The
+  // 2 dnum key polynomials, [term][component], are gathered into one contiguous device buffer of this ring's context.  The ordering is
+  // that of key_switch_into, with the outputs' ring type awaited as well.  The results get payloads of their own: an output may be an
+  // input, and copy-on-write sharers of the outputs' old values keep them.  Never fused into a queue's rewrites.
+  template <size_t LO, size_t OO> static void mul_relin_into(poly_p<T, Degree, OO> &out0, poly_p<T, Degree, OO> &out1, poly_p<T, Degree, LO> const &a0,
+                                                             poly_p<T, Degree, LO> const &a1, poly_p<T, Degree, LO> const *b0,
+                                                             poly_p<T, Degree, LO> const *b1, poly_p const *key, size_t alpha, bool centered, bool floor) {
+    static_assert(LO >= 1 && LO < NbModuli, "nfl::mul_relin_ntt: the key's ring has at least one special modulus more than the ciphertexts'");
+    static_assert(OO == LO || OO + 1 == LO, "nfl::mul_relin_ntt: the outputs live in the inputs' ring, or in the ring with one modulus less");
+    typedef poly_p<T, Degree, LO> in_t;
+    typedef poly_p<T, Degree, OO> out_t;
+    if (alpha == 0 || alpha > LO) throw std::runtime_error("nfl(hip): mul_relin_ntt: alpha is out of range (1 to the ciphertexts' moduli)");
+    if (!b0 != !b1) throw std::runtime_error("nfl(hip): mul_relin_ntt: b0 and b1 are both given, or both NULL for the square");
+    const size_t dnum = (LO + alpha - 1) / alpha, pb = sizeof(T) * Degree * NbModuli;
+    lazy_t::inst().flush();
+    in_t::lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    typename in_t::ptr_type s0 = a0._p, s1 = a1._p, t0 = b0 ? b0->_p : typename in_t::ptr_type(), t1 = b1 ? b1->_p : typename in_t::ptr_type();
+    typename out_t::ptr_type d0 = out_t::fresh(), d1 = out_t::fresh();
+    std::vector<ptr_type> held;  // (the key's payloads)
+    for (size_t t = 0; t < 2 * dnum; ++t) held.push_back(key[t]._p);
+    const void *p_a0 = s0->dev_ro(), *p_a1 = s1->dev_ro(), *p_b0 = b0 ? t0->dev_ro() : nullptr, *p_b1 = b1 ? t1->dev_ro() : nullptr;
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo(), *kbuf = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &kbuf, 2 * dnum * pb), "mul_relin_ntt");
+    char *const kb = static_cast<char *>(kbuf);
+    int rc = NFLHIP_OK;
+    for (size_t t = 0; t < 2 * dnum && rc == NFLHIP_OK; ++t) rc = nflhip_memcpy_d2d(ctx_t::get(), kb + t * pb, held[t]->dev_ro(), pb, ctx_t::queue());
+    if (rc == NFLHIP_OK) rc = nflhip_stream_sync(in_t::ctx_t::get(), in_t::ctx_t::queue());
+    if (rc == NFLHIP_OK && OO != LO) rc = nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue());
+    const int flags = (centered ? NFLHIP_MULRELIN_CENTERED : 0) | (floor ? NFLHIP_MULRELIN_FLOOR : 0) | (OO != LO ? NFLHIP_MULRELIN_RESCALE : 0);
+    if (rc == NFLHIP_OK) rc = nflhip_mulrelin_ntt_dev(ctx_t::get(), o0, o1, p_a0, p_a1, p_b0, p_b1, kbuf, 1, NbModuli - LO, alpha, flags, ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered key goes)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), kbuf);
+      throw std::runtime_error("nfl(hip): mul_relin_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), kbuf);
+    detail::check(ctx_t::get(), rs, "mul_relin_ntt");
+    out0._p = d0;
+    out1._p = d1;
+  }
+
+  // The tensor product (nfl::tensor_ntt below): the deferred queue of this ring type runs first, then one launch on its stream.  The
+  // results get payloads of their own, so an output may be an input and copy-on-write sharers of the outputs' old values keep them.
+  static void tensor_into(poly_p &out0, poly_p &out1, poly_p &out2, poly_p const &a0, poly_p const &a1, poly_p const *b0, poly_p const *b1) {
+    if (!b0 != !b1) throw std::runtime_error("nfl(hip): tensor_ntt: b0 and b1 are both given, or both NULL for the square");
+    lazy_t::inst().flush();
+    ptr_type s0 = a0._p, s1 = a1._p, t0 = b0 ? b0->_p : ptr_type(), t1 = b1 ? b1->_p : ptr_type();
+    ptr_type d0 = fresh(), d1 = fresh(), d2 = fresh();
+    const void *p_a0 = s0->dev_ro(), *p_a1 = s1->dev_ro(), *p_b0 = b0 ? t0->dev_ro() : nullptr, *p_b1 = b1 ? t1->dev_ro() : nullptr;
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo(), *o2 = d2->dev_wo();
+    detail::check(ctx_t::get(), nflhip_tensor_ntt_dev(ctx_t::get(), o0, o1, o2, p_a0, p_a1, p_b0, p_b1, 1, NbModuli, 0, ctx_t::queue()), "tensor_ntt");
+    detail::check(ctx_t::get(), nflhip_stream_sync(ctx_t::get(), ctx_t::queue()), "tensor_ntt");
+    out0._p = d0;
+    out1._p = d1;
+    out2._p = d2;
+  }
+
   // Sum of products (nfl::dot / nfl::dot_add below): the deferred queue of this ring type runs first (on the caller), then the
   // pointer form of the entry on the queue's stream, 16 terms per launch, chained through the addend.  The result gets a
   // payload of its own, so `out` may be one of the inputs and copy-on-write sharers of out's old value keep it.
@@ -688,6 +749,89 @@ template <class T, size_t D, size_t L, size_t M>
 void key_switch_ntt(poly_p<T, D, L> &out0, poly_p<T, D, L> &out1, poly_p<T, D, L> const &in, poly_p<T, D, M> const *key, size_t alpha,
                     bool centered = false, bool floor = false) {
   poly_p<T, D, M>::template key_switch_into<L>(out0, out1, in, key, alpha, centered, floor);
+}
+
+/* Ciphertext multiplication (include/nflhip.h "ciphertext multiplication").  tensor_ntt: (out0, out1, out2) = (a0 b0, a0 b1 + a1 b0,
+ * a1 b1) in one pass; an output may be an input.  mul_relin_ntt: the ciphertexts (a0, a1) and (b0, b1) in the ring with L moduli, the
+ * key from s^2 to s in the ring with M > L moduli whose last K = M - L are the special ones -- an array of 2 dnum polynomials in
+ * [term][component] order, as key_switch_ntt takes it --; (out0, out1) = the tensor product with its third component relinearised,
+ * with ONE mod-down: the words of (d0, d1) + key_switch_ntt(d2).  square_relin_ntt: the same of (a0, a1) with itself.
+ * mul_relin_rescale_ntt: the outputs live in the ring with L - 1 moduli, divided by the last kept modulus in the same rounding.  An
+ * output may be an input.  On poly the staged host entries; on poly_p the key is gathered into one device buffer and the queues
+ * and streams of the ring types are ordered as nfl::key_switch_ntt orders them.  Never fused into a queue's rewrites. */
+namespace detail {
+template <class T, size_t D, size_t L, size_t O, size_t M>
+void mul_relin_host(poly<T, D, O> &out0, poly<T, D, O> &out1, poly<T, D, L> const &a0, poly<T, D, L> const &a1, poly<T, D, L> const *b0,
+                    poly<T, D, L> const *b1, poly<T, D, M> const *key, size_t alpha, bool centered, bool floor) {
+  static_assert(L >= 1 && L < M, "nfl::mul_relin_ntt: the key's ring has at least one special modulus more than the ciphertexts'");
+  static_assert(O == L || O + 1 == L, "nfl::mul_relin_ntt: the outputs live in the inputs' ring, or in the ring with one modulus less");
+  typedef poly<T, D, O> S;
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  S *t0 = S::make_temp(), *t1 = S::make_temp();  // (an output may be an input)
+  const int flags = (centered ? NFLHIP_MULRELIN_CENTERED : 0) | (floor ? NFLHIP_MULRELIN_FLOOR : 0) | (O != L ? NFLHIP_MULRELIN_RESCALE : 0);
+  const int rc = nflhip_mulrelin_ntt(P::ctx(), t0->data(), t1->data(), a0.cdata(), a1.cdata(), b0 ? b0->cdata() : nullptr, b1 ? b1->cdata() : nullptr,
+                                     key->cdata(), 1, M - L, alpha, flags);
+  if (rc == 0) {
+    std::memcpy(static_cast<void *>(out0.data()), t0->cdata(), sizeof(S));
+    std::memcpy(static_cast<void *>(out1.data()), t1->cdata(), sizeof(S));
+  }
+  S::drop_temp(t0);
+  S::drop_temp(t1);
+  check(P::ctx(), rc, "mul_relin_ntt");
+}
+}  // namespace detail
+template <class T, size_t D, size_t M>
+void tensor_ntt(poly<T, D, M> &out0, poly<T, D, M> &out1, poly<T, D, M> &out2, poly<T, D, M> const &a0, poly<T, D, M> const &a1,
+                poly<T, D, M> const *b0 = nullptr, poly<T, D, M> const *b1 = nullptr) {
+  typedef poly<T, D, M> P;
+  P *t[3] = {P::make_temp(), P::make_temp(), P::make_temp()};  // (an output may be an input)
+  const int rc = nflhip_tensor_ntt(P::ctx(), t[0]->data(), t[1]->data(), t[2]->data(), a0.cdata(), a1.cdata(), b0 ? b0->cdata() : nullptr,
+                                   b1 ? b1->cdata() : nullptr, 1, M, 0);
+  P *const outs[3] = {&out0, &out1, &out2};
+  for (int k = 0; k < 3; ++k) {
+    if (rc == 0) std::memcpy(static_cast<void *>(outs[k]->data()), t[k]->cdata(), sizeof(P));
+    P::drop_temp(t[k]);
+  }
+  detail::check(P::ctx(), rc, "tensor_ntt");
+}
+template <class T, size_t D, size_t M>
+void tensor_ntt(poly_p<T, D, M> &out0, poly_p<T, D, M> &out1, poly_p<T, D, M> &out2, poly_p<T, D, M> const &a0, poly_p<T, D, M> const &a1,
+                poly_p<T, D, M> const *b0 = nullptr, poly_p<T, D, M> const *b1 = nullptr) {
+  poly_p<T, D, M>::tensor_into(out0, out1, out2, a0, a1, b0, b1);
+}
+template <class T, size_t D, size_t L, size_t M>
+void mul_relin_ntt(poly<T, D, L> &out0, poly<T, D, L> &out1, poly<T, D, L> const &a0, poly<T, D, L> const &a1, poly<T, D, L> const &b0,
+                   poly<T, D, L> const &b1, poly<T, D, M> const *key, size_t alpha, bool centered = false, bool floor = false) {
+  detail::mul_relin_host<T, D, L, L, M>(out0, out1, a0, a1, &b0, &b1, key, alpha, centered, floor);
+}
+template <class T, size_t D, size_t L, size_t M>
+void mul_relin_ntt(poly_p<T, D, L> &out0, poly_p<T, D, L> &out1, poly_p<T, D, L> const &a0, poly_p<T, D, L> const &a1, poly_p<T, D, L> const &b0,
+                   poly_p<T, D, L> const &b1, poly_p<T, D, M> const *key, size_t alpha, bool centered = false, bool floor = false) {
+  poly_p<T, D, M>::template mul_relin_into<L, L>(out0, out1, a0, a1, &b0, &b1, key, alpha, centered, floor);
+}
+template <class T, size_t D, size_t L, size_t M>
+void square_relin_ntt(poly<T, D, L> &out0, poly<T, D, L> &out1, poly<T, D, L> const &a0, poly<T, D, L> const &a1, poly<T, D, M> const *key,
+                      size_t alpha, bool centered = false, bool floor = false) {
+  detail::mul_relin_host<T, D, L, L, M>(out0, out1, a0, a1, nullptr, nullptr, key, alpha, centered, floor);
+}
+template <class T, size_t D, size_t L, size_t M>
+void square_relin_ntt(poly_p<T, D, L> &out0, poly_p<T, D, L> &out1, poly_p<T, D, L> const &a0, poly_p<T, D, L> const &a1, poly_p<T, D, M> const *key,
+                      size_t alpha, bool centered = false, bool floor = false) {
+  poly_p<T, D, M>::template mul_relin_into<L, L>(out0, out1, a0, a1, nullptr, nullptr, key, alpha, centered, floor);
+}
+template <class T, size_t D, size_t L, size_t M>
+void mul_relin_rescale_ntt(poly<T, D, L - 1> &out0, poly<T, D, L - 1> &out1, poly<T, D, L> const &a0, poly<T, D, L> const &a1, poly<T, D, L> const &b0,
+                           poly<T, D, L> const &b1, poly<T, D, M> const *key, size_t alpha, bool centered = false, bool floor = false) {
+  static_assert(L >= 2, "nfl::mul_relin_rescale_ntt drops the last kept modulus: the ciphertexts need at least two");
+  detail::mul_relin_host<T, D, L, L - 1, M>(out0, out1, a0, a1, &b0, &b1, key, alpha, centered, floor);
+}
+template <class T, size_t D, size_t L, size_t M>
+void mul_relin_rescale_ntt(poly_p<T, D, L - 1> &out0, poly_p<T, D, L - 1> &out1, poly_p<T, D, L> const &a0, poly_p<T, D, L> const &a1,
+                           poly_p<T, D, L> const &b0, poly_p<T, D, L> const &b1, poly_p<T, D, M> const *key, size_t alpha, bool centered = false,
+                           bool floor = false) {
+  static_assert(L >= 2, "nfl::mul_relin_rescale_ntt drops the last kept modulus: the ciphertexts need at least two");
+  poly_p<T, D, M>::template mul_relin_into<L, L - 1>(out0, out1, a0, a1, &b0, &b1, key, alpha, centered, floor);
 }
 
 /* Hoisted rotations (include/nflhip.h "hoisted rotations"): the ciphertext (c0, c1) in the ring with L moduli rotated by ks[m], m <

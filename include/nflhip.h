@@ -542,6 +542,77 @@ int nflhip_lintrans_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void 
                         const void *const *h_keys, const void *const *h_weights, const uint64_t *ks, size_t count,
                         size_t batch, size_t k_special, size_t alpha, int flags);   /* staged host variant */
 
+/* ---- ciphertext multiplication: the tensor product, and the product with relinearisation --------
+ * THE TENSOR PRODUCT of two degree-1 ciphertexts (a0, a1), (b0, b1), row by row mod p_j on the `rows` leading moduli of the context,
+ * 1 <= rows <= nmoduli:
+ *     out0 = a0 (.) b0,     out1 = a0 (.) b1 + a1 (.) b0,     out2 = a1 (.) b1          every block [batch][rows][degree], canonical
+ * One streaming pass, nothing allocated, capturable.  out1 is accumulated unreduced in a double-width word and reduced once.  It
+ * does not look at the form (the product of NTT-form operands is the NTT form of the negacyclic product).  b0 == b1 == NULL: the
+ * SQUARE, a0^2, 2 a0 a1, a1^2, with two reads instead of four.  An output may be exactly an input (the same first byte); any
+ * other overlap of an output with an input or with another output is NFLHIP_ERR_INVALID.  Buffers off 16 bytes and rows shorter
+ * than 16 bytes take a word variant of the kernel.  flags: 0.
+ * NFLHIP_ERR_INVALID, nothing enqueued: a NULL context, a NULL pointer with batch != 0 (b0 and b1 both NULL is the square, one of
+ * them NULL is an error), rows out of range, flag bits, a size that overflows size_t, such an overlap, a cyclic row context.
+ * batch == 0 returns NFLHIP_OK and touches nothing.  The host variant stages the inputs and the three outputs.
+ *
+ * THE PRODUCT WITH RELINEARISATION.  The context, k_special, L = nmoduli - k_special, the digits of alpha rows and dnum are those
+ * of the key switch above.
+ *   a0, a1, b0, b1   [batch][L][degree], NTT form; b0 == b1 == NULL: the square of (a0, a1)
+ *   key              [dnum][2][nmoduli][degree] exactly as nflhip_keyswitch_ntt_dev takes it: the key from s^2 to s
+ *   out0, out1       [batch][L][degree], NTT form; with NFLHIP_MULRELIN_RESCALE [batch][L - 1][degree]
+ * Definition, word for word, with pi_j = P mod p_j, P the product of the special moduli:
+ *     d0, d1, d2 = the tensor product of (a0, a1) and (b0, b1) on L rows
+ *     U_d   as nflhip_keyswitch_ntt_dev forms it from d2                                        NFLHIP_MULRELIN_CENTERED as NFLHIP_KEYSWITCH_CENTERED
+ *     A_c   = E(pi (.) d_c) + sum_d U_d (.) key[d][c]       E: the L rows embedded in nmoduli rows, the special rows 0; nflhip_dot_dev with addend
+ *     out_c = nflhip_moddown_ntt_dev(A_c, k_special)                                            NFLHIP_MULRELIN_FLOOR as NFLHIP_MODDOWN_FLOOR
+ *             with NFLHIP_MULRELIN_RESCALE: nflhip_moddown_ntt_dev(A_c, k_special + 1);  needs L >= 2
+ * Without RESCALE these are the words of d_c + nflhip_keyswitch_ntt_dev(d2)_c: the mod-down computes (x_j - conv_j(special
+ * rows)) P^-1 mod p_j, the special rows of A_c are those of the key-switch sum, and pi_j d_c P^-1 = d_c mod p_j, in both rounding
+ * modes.  With RESCALE the sum is divided by P q_(L-1) in ONE rounding, (d_c + ks_c) / q_(L-1) rounded: the same
+ * function of the plaintext as the product followed by two nflhip_rescale_dev, with less noise and K + L row transforms per
+ * component instead of K + 2L -- not the words of the two-step way.  The result is a ciphertext over the first L - 1 moduli.
+ * Plans, same words; `flags` may carry at most one plan flag:
+ *   NFLHIP_MULRELIN_SEQUENCE  the definition through existing entries: the tensor product by nflhip_dot_dev on the context over the
+ *                             first L moduli, the scaling by pi as a one-term nflhip_dot_dev against a constant polynomial, per-digit
+ *                             nflhip_baseconv_ntt_dev, nflhip_dot_dev with the addend in place, the mod-down.  No kernel of its own:
+ *                             the cross-check.
+ *   NFLHIP_MULRELIN_MERGED    ONE launch of the tensor kernel that writes d2 straight into the mod-up's source buffer and pi d_c into
+ *                             the two sums; the mod-up by the two routes of the hoisted rotations; nflhip_dot_dev twice with the
+ *                             addend in place; ONE mod-down of 2 batch polynomials when out1 follows out0 in memory, else two.
+ *   NFLHIP_MULRELIN_FUSED     ONE launch from the four inputs up to the two sums: the key switch's one-launch kernel with the source
+ *                             rows formed as a1 (.) b1 at the load and pi d_c as the accumulators' carry-in; d0, d1, d2 never touch
+ *                             memory.  The LDS bound of NFLHIP_KEYSWITCH_FUSED, unchanged; beyond it the flag gives
+ *                             NFLHIP_ERR_UNSUPPORTED.
+ *   none                      the one-launch kernel where it fits (not for contexts created under NFLHIP_VARIANT=hipcc), else merged
+ *                             (DESIGN.md 5.19).
+ * Scratch, context-owned, in polynomials of nmoduli rows (p) and of L rows (q): merged batch (1 p | 1 q) + batch dnum p + 2 batch p;
+ * fused 2 batch p; the sequence batch (7 q + 3 p + dnum p + 2 p).
+ * The first call for a (k_special, alpha, plan, modes), or for a larger batch, builds tables and allocates (it synchronises): make
+ * it before capturing into a hipGraph; while capturing it is NFLHIP_ERR_UNSUPPORTED, nothing is enqueued and the stream stays
+ * usable.  Calls on different streams are ordered on the scratch by an event; a replaying graph must not run concurrently with
+ * other multiplications of the context.  An output may be exactly an input: every read of the inputs precedes the mod-down that
+ * writes the outputs.
+ * NFLHIP_ERR_INVALID, nothing enqueued: a NULL context, a NULL pointer with batch != 0 (b0 and b1 both NULL is the square, one of
+ * them NULL is an error), k_special or alpha out of range, RESCALE with L == 1, unknown flag bits or two plan flags, a size that
+ * overflows size_t, out0 overlapping out1, an output overlapping the key, an output overlapping an input without being it, a
+ * cyclic row context, a repeated modulus.  batch == 0 returns NFLHIP_OK and touches nothing.
+ * The host variant stages the inputs, the key and both outputs. */
+#define NFLHIP_MULRELIN_CENTERED 0x100
+#define NFLHIP_MULRELIN_FLOOR 0x200
+#define NFLHIP_MULRELIN_RESCALE 0x400
+#define NFLHIP_MULRELIN_FUSED 0x800
+#define NFLHIP_MULRELIN_SEQUENCE 0x1000
+#define NFLHIP_MULRELIN_MERGED 0x2000
+int nflhip_tensor_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, void *d_out2, const void *d_a0, const void *d_a1,
+                          const void *d_b0, const void *d_b1, size_t batch, size_t rows, int flags, void *stream);
+int nflhip_tensor_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, void *h_out2, const void *h_a0, const void *h_a1,
+                      const void *h_b0, const void *h_b1, size_t batch, size_t rows, int flags);   /* staged host variant */
+int nflhip_mulrelin_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_a0, const void *d_a1, const void *d_b0,
+                            const void *d_b1, const void *d_key, size_t batch, size_t k_special, size_t alpha, int flags,
+                            void *stream);
+int nflhip_mulrelin_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0,
+                        const void *h_b1, const void *h_key, size_t batch, size_t k_special, size_t alpha, int flags);   /* staged host variant */
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

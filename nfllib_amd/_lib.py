@@ -34,6 +34,7 @@ ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_SEQUENCE, ROTATE_HOISTED = 0x100, 0x200, 0
 MAC_MAX_TERMS, MAC_DOUBLE_BUFFER = 16, 0x1
 LINTRANS_MAX_TERMS = 16
 LINTRANS_CENTERED, LINTRANS_FLOOR, LINTRANS_SEQUENCE, LINTRANS_HOISTED = 0x100, 0x200, 0x1000, 0x2000
+MULRELIN_CENTERED, MULRELIN_FLOOR, MULRELIN_RESCALE, MULRELIN_FUSED, MULRELIN_SEQUENCE, MULRELIN_MERGED = 0x100, 0x200, 0x400, 0x800, 0x1000, 0x2000
 
 
 class DotOperand(C.Structure):
@@ -90,6 +91,10 @@ SYMBOLS = [
     ("nflhip_automorphism_mac", _i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _i]),
     ("nflhip_lintrans_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i, _vp]),
     ("nflhip_lintrans_ntt", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i]),
+    ("nflhip_tensor_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _vp]),
+    ("nflhip_tensor_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i]),
+    ("nflhip_mulrelin_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_mulrelin_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i]),
     ("nflhip_gadget_mul_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),

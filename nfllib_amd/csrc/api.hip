@@ -388,7 +388,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch, nflhip::warm_dot_multi, nflhip::warm_rotate, nflhip::warm_lintrans};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch, nflhip::warm_dot_multi, nflhip::warm_rotate, nflhip::warm_lintrans, nflhip::warm_mulrelin};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -502,6 +502,10 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   if (ctx->ev_lt) (void)hipEventDestroy(ctx->ev_lt);
   if (ctx->rot_scratch) (void)hipFree(ctx->rot_scratch);
   if (ctx->lt_scratch) (void)hipFree(ctx->lt_scratch);
+  if (ctx->ev_mr) (void)hipEventDestroy(ctx->ev_mr);
+  if (ctx->mr_scratch) (void)hipFree(ctx->mr_scratch);
+  for (auto &kv : ctx->mr_pi) (void)hipFree(kv.second);
+  ctx->mr_pi.clear();
   if (ctx->ks_scratch) (void)hipFree(ctx->ks_scratch);
   for (auto &kv : ctx->ks_recs) (void)hipFree(kv.second);
   ctx->ks_recs.clear();
@@ -1575,6 +1579,226 @@ int nflhip_lintrans_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const v
   int rc = lintrans_check(ctx, d_out0, d_out1, d_c0, d_c1, d_keys, d_weights, ks, count, batch, k_special, alpha, flags);  // in full, before any device use
   if (rc || batch == 0) return rc;
   return lintrans_run(ctx, d_out0, d_out1, d_c0, d_c1, d_keys, d_weights, ks, count, batch, k_special, alpha, flags, (hipStream_t)stream);
+}
+
+// The tensor product of two degree-1 ciphertexts (kernels_mulrelin.hip; include/nflhip.h "ciphertext multiplication"): one launch,
+// nothing allocated.
+int nflhip_tensor_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, void *d_out2, const void *d_a0, const void *d_a1, const void *d_b0,
+                          const void *d_b1, size_t batch, size_t rows, int flags, void *stream) {
+  int rc = tensor_check(ctx, d_out0, d_out1, d_out2, d_a0, d_a1, d_b0, d_b1, batch, rows, flags);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_tensor_ntt<T>(ctx->shape, ctx->tabs, (T *)d_out0, (T *)d_out1, (T *)d_out2, (const T *)d_a0, (const T *)d_a1, (const T *)d_b0,
+                                (const T *)d_b1, batch, rows, rows, rows * ctx->shape.n, rows * ctx->shape.n, nullptr, (hipStream_t)stream);
+  });
+  return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "tensor");
+}
+
+// Ciphertext multiplication with relinearisation (kernels_mulrelin.hip; include/nflhip.h "ciphertext multiplication"): the tensor
+// product d0, d1, d2 on the L kept rows, the key-switch sums of d2 with pi (.) d_c as their addend, one mod-down by the last K
+// (RESCALE: K + 1) moduli.  Three plans with the same words:
+//   sequence  existing entries only: a, b copied into S = [a0 a1 | b1 b0] = [4][batch][L][n]; nflhip_dot_dev on the child context over
+//             rows [0, L) into D = [3][batch][L][n] (one term for d0 and d2, two for d1); D embedded into X = [3][batch][nm][n] (zeroed
+//             first); A_c = X_c (.) C by a one-term nflhip_dot_dev, C the constant polynomial of pi; per-digit nflhip_baseconv_ntt_dev
+//             from X_2 into U = [dnum][batch][nm][n]; nflhip_dot_dev into A_c with A_c as the addend
+//   merged    k_tensor_ntt once: d2 into X (embedded in nm rows for the per-digit route, else L rows dense), pi d_c into A; the mod-up
+//             by the two routes of rotate_run; nflhip_dot_dev into A_c with A_c as the addend
+//   fused     k_tensor_modup_dot_fused straight from the inputs to A; bounded as the key switch's one-launch kernel
+// then nflhip_moddown_ntt_dev -- one call of 2 batch polynomials when out1 follows out0 in memory, else one per output.  Every read
+// of a and b is enqueued before the mod-down, so an output may be an input.
+// Default: see mulrelin_default_plan.  Lock order: mr_mu, then ks_mu, then bcn_mu.
+static int mulrelin_pi(nflhip_ctx *ctx, size_t K, hipStream_t st, const uint64_t **pi, const void **cpoly) {  // under mr_mu
+  const size_t nm = ctx->shape.nm, L = nm - K, n = ctx->shape.n, head = 2 * nm * sizeof(uint64_t);
+  auto it = ctx->mr_pi.find(K);
+  if (it == ctx->mr_pi.end()) {
+    if (is_capturing(st))
+      return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "mulrelin: the first call for a k_special uploads its tables, which a stream capture cannot do");
+    const int W = ctx->shape.limb_bits;
+    std::vector<uint64_t> h(2 * nm + (nm * n * ctx->word + 7) / 8, 0);
+    for (size_t j = 0; j < L; ++j) {
+      const uint64_t p = ctx->h_P[j];
+      unsigned __int128 v = 1;
+      for (size_t k = L; k < nm; ++k) v = v * (ctx->h_P[k] % p) % p;
+      h[2 * j] = (uint64_t)v;
+      h[2 * j + 1] = (uint64_t)((v << W) / p);  // floor(pi 2^W / p), pi < p < 2^(W-2)
+      with_limb(ctx, [&](auto z) {
+        typedef decltype(z) T;
+        T *row = reinterpret_cast<T *>(h.data() + 2 * nm) + j * n;
+        for (size_t i = 0; i < n; ++i) row[i] = (T)v;
+        return 0;
+      });
+    }
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    void *d = nullptr;
+    HIPCHK(ctx, hipMalloc(&d, h.size() * sizeof(uint64_t)));
+    hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      return hipfail(ctx, e, "mulrelin: table upload");
+    }
+    try {
+      it = ctx->mr_pi.emplace(K, d).first;
+    } catch (const std::bad_alloc &) {
+      (void)hipFree(d);
+      return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+    }
+  }
+  *pi = (const uint64_t *)it->second;
+  *cpoly = (const char *)it->second + head;
+  return NFLHIP_OK;
+}
+// Which plan serves by default.  The starting rule: the one-launch kernel where it fits (not for contexts created under
+// NFLHIP_VARIANT=hipcc), the merged plan otherwise.
+static int mulrelin_default_plan(const nflhip_ctx *ctx, size_t L, size_t dnum, bool centred) {
+  if (!ctx->shape.compiled_only && keyswitch_fused_fits(L, dnum, ctx->shape.n, ctx->word, centred)) return NFLHIP_MULRELIN_FUSED;
+  return NFLHIP_MULRELIN_MERGED;
+}
+static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0, const void *a1, const void *b0, const void *b1, const void *key,
+                        size_t batch, size_t K, size_t alpha, int flags, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->mr_mu);
+  const size_t nm = ctx->shape.nm, n = ctx->shape.n, L = nm - K, dnum = (L + alpha - 1) / alpha, row = n * ctx->word, pb = nm * row, qb = L * row;
+  const bool centred = (flags & NFLHIP_MULRELIN_CENTERED) != 0, floor = (flags & NFLHIP_MULRELIN_FLOOR) != 0;
+  const bool resc = (flags & NFLHIP_MULRELIN_RESCALE) != 0, cap = is_capturing(st);
+  const size_t down = K + (resc ? 1 : 0), kept = nm - down;
+  const uint64_t *const *recs = nullptr;
+  const uint64_t *pi = nullptr, *drec = nullptr;
+  const void *cpoly = nullptr;
+  int rc;
+  {  // the tables first: a repeated modulus is refused with the builder's message before anything is enqueued
+    std::lock_guard<std::mutex> l2(ctx->ks_mu);
+    try {
+      rc = keyswitch_records(ctx, K, alpha, st, &recs);
+    } catch (const std::bad_alloc &) {
+      return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+    }
+  }
+  // the mod-down by K + 1 rows: its record is built HERE only so that a repeated modulus is refused before anything is enqueued; the
+  // mod-down entry below looks it up again itself
+  if (!rc && resc) rc = baseconv_record(ctx, kept, down, 0, kept, true, st, &drec);
+  (void)drec;
+  if (rc) return rc;
+  try {
+    rc = mulrelin_pi(ctx, K, st, &pi, &cpoly);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+  }
+  if (rc) return rc;
+  int plan = flags & (NFLHIP_MULRELIN_SEQUENCE | NFLHIP_MULRELIN_MERGED | NFLHIP_MULRELIN_FUSED);
+  if (plan == NFLHIP_MULRELIN_FUSED && !keyswitch_fused_fits(L, dnum, n, ctx->word, centred))
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "mulrelin: the rows of this call do not fit the one-launch kernel's LDS");
+  if (!plan) plan = mulrelin_default_plan(ctx, L, dnum, centred);
+  const int modes = flags & (NFLHIP_MULRELIN_CENTERED | NFLHIP_MULRELIN_FLOOR | NFLHIP_MULRELIN_RESCALE);
+  // what a call while capturing may do: repeat a (k_special, alpha, plan, modes) already served at this batch or a larger one
+  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes)};
+  auto wit = ctx->mr_warm.find(wkey);
+  if (cap && (wit == ctx->mr_warm.end() || wit->second < batch))
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "mulrelin: the first call for a (k_special, alpha, plan), or for a larger batch, allocates, which a stream capture cannot do");
+  const bool seq = plan == NFLHIP_MULRELIN_SEQUENCE, fused = plan == NFLHIP_MULRELIN_FUSED;
+  const bool perdigit = seq || (!ctx->shape.compiled_only && n <= 2048);
+  // sequence: S, D, X, U, A; merged: X, U, A; fused: A
+  const size_t sb = seq ? 7 * batch * qb : 0, xb = fused ? 0 : seq ? 3 * batch * pb : perdigit ? batch * pb : batch * qb;
+  const size_t ub = fused ? 0 : batch * dnum * pb, ab = 2 * batch * pb, need = sb + xb + ub + ab;
+  if ((rc = set_device(ctx))) return rc;
+  nflhip_ctx *child = nullptr;
+  if (!fused) {  // the L-row context: the sequence's tensor product, the merged plan's inverse transform
+    std::lock_guard<std::mutex> l2(ctx->bcn_mu);
+    if ((rc = bcn_child(ctx, 0, L, cap, &child))) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+  }
+  if (ctx->mr_scratch_bytes < need) {
+    if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "mulrelin: the scratch has to grow, which a stream capture cannot do");
+    if (ctx->mr_scratch) HIPCHK(ctx, hipFree(ctx->mr_scratch));  // (synchronises: nothing still reads it)
+    ctx->mr_scratch = nullptr;
+    ctx->mr_scratch_bytes = 0;
+    HIPCHK(ctx, hipMalloc(&ctx->mr_scratch, need));
+    ctx->mr_scratch_bytes = need;
+  }
+  if (!ctx->ev_mr) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_mr, hipEventDisableTiming));
+  if (!cap && ctx->ev_mr_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_mr, 0));  // a previous call on another stream
+  char *S = (char *)ctx->mr_scratch, *X = S + sb, *U = X + xb, *A = U + ub;
+  const int bcflags = centred ? NFLHIP_BASECONV_CENTERED : 0;
+  nflhip_dot_operand u = {nullptr, 0, 0};
+  if (fused) {
+    hipError_t e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_tensor_modup_dot_fused<T>(ctx->shape, ctx->tabs, (T *)A, (const T *)a0, (const T *)a1, (const T *)b0, (const T *)b1, (const T *)key,
+                                              recs, pi, batch, L, alpha, centred, st);
+    });
+    if (e == hipErrorNotSupported) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "mulrelin: the rows of this call do not fit the one-launch kernel's LDS");
+    if (e != hipSuccess) return hipfail(ctx, e, "mulrelin (fused)");
+  } else if (seq) {
+    char *D = S + 4 * batch * qb, *X2 = X + 2 * batch * pb;
+    const void *const src[4] = {a0, a1, b1 ? b1 : a1, b0 ? b0 : a0};  // S = [a0 a1 | b1 b0]: d1 = a0 b1 + a1 b0 term by term
+    for (int k = 0; k < 4; ++k) HIPCHK(ctx, hipMemcpyAsync(S + k * batch * qb, src[k], batch * qb, hipMemcpyDefault, st));  // (a staged caller's inputs may be pinned host memory)
+    const nflhip_dot_operand sa0 = {S, 1, batch}, sa1 = {S + batch * qb, 1, batch}, sb1 = {S + 2 * batch * qb, 1, batch}, sb0 = {S + 3 * batch * qb, 1, batch};
+    if ((rc = nflhip_dot_dev(child, D, &sa0, &sb0, nullptr, batch, 1, 0, st))) return rc;
+    if ((rc = nflhip_dot_dev(child, D + batch * qb, &sa0, &sb1, nullptr, batch, 2, 0, st))) return rc;
+    if ((rc = nflhip_dot_dev(child, D + 2 * batch * qb, &sa1, &sb1, nullptr, batch, 1, 0, st))) return rc;
+    if ((rc = set_device(ctx))) return rc;
+    HIPCHK(ctx, hipMemsetAsync(X, 0, 3 * batch * pb, st));
+    HIPCHK(ctx, hipMemcpy2DAsync(X, pb, D, qb, qb, 3 * batch, hipMemcpyDeviceToDevice, st));
+    const nflhip_dot_operand c = {cpoly, 0, 0};
+    for (size_t k = 0; k < 2; ++k) {
+      const nflhip_dot_operand x = {X + k * batch * pb, 1, 0};
+      if ((rc = nflhip_dot_dev(ctx, A + k * batch * pb, &x, &c, nullptr, batch, 1, 0, st))) return rc;
+    }
+    for (size_t d = 0; d < dnum; ++d)
+      if ((rc = nflhip_baseconv_ntt_dev(ctx, U + d * batch * pb, X2, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm, bcflags, st))) return rc;
+    u = {U, 1, batch};
+  } else {
+    const size_t pw = pb / ctx->word, qw = qb / ctx->word;
+    hipError_t e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_tensor_ntt<T>(ctx->shape, ctx->tabs, (T *)A, (T *)(A + batch * pb), (T *)X, (const T *)a0, (const T *)a1, (const T *)b0, (const T *)b1,
+                                  batch, L, nm, pw, perdigit ? pw : qw, pi, st);
+    });
+    if (e != hipSuccess) return hipfail(ctx, e, "mulrelin: tensor");
+    if (perdigit) {
+      for (size_t d = 0; d < dnum; ++d)
+        if ((rc = nflhip_baseconv_ntt_dev(ctx, U + d * batch * pb, X, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm, bcflags, st))) return rc;
+      u = {U, 1, batch};
+    } else {
+      if ((rc = nflhip_ntt_inv_dev(child, X, batch, st)) || (rc = set_device(ctx))) return rc;
+      e = with_limb(ctx, [&](auto z) {
+        typedef decltype(z) T;
+        return launch_modup_digits<T>(ctx->shape, ctx->tabs, (T *)U, (const T *)X, recs, batch, L, alpha, centred, st);
+      });
+      if (e != hipSuccess) return hipfail(ctx, e, "mulrelin: mod-up");
+      if ((rc = nflhip_ntt_fwd_dev(ctx, U, batch * dnum, st))) return rc;
+      u = {U, dnum, 1};
+    }
+  }
+  for (size_t c = 0; c < 2 && !fused; ++c) {
+    const nflhip_dot_operand b = {(const char *)key + c * pb, 0, 2};
+    if ((rc = nflhip_dot_dev(ctx, A + c * batch * pb, &u, &b, A + c * batch * pb, batch, dnum, 0, st))) return rc;
+  }
+  const int mdflags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
+  if ((char *)out1 == (char *)out0 + batch * kept * row) {
+    rc = nflhip_moddown_ntt_dev(ctx, out0, A, 2 * batch, down, mdflags, st);
+  } else {
+    rc = nflhip_moddown_ntt_dev(ctx, out0, A, batch, down, mdflags, st);
+    if (!rc) rc = nflhip_moddown_ntt_dev(ctx, out1, A + batch * pb, batch, down, mdflags, st);
+  }
+  if (rc || (rc = set_device(ctx))) return rc;
+  if (!cap) {
+    HIPCHK(ctx, hipEventRecord(ctx->ev_mr, st));
+    ctx->ev_mr_valid = true;
+    try {
+      size_t &w = ctx->mr_warm[wkey];
+      if (w < batch) w = batch;
+    } catch (const std::bad_alloc &) {
+    }
+  }
+  return NFLHIP_OK;
+}
+int nflhip_mulrelin_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_a0, const void *d_a1, const void *d_b0, const void *d_b1,
+                            const void *d_key, size_t batch, size_t k_special, size_t alpha, int flags, void *stream) {
+  int rc = mulrelin_check(ctx, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, alpha, flags);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  return mulrelin_run(ctx, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, alpha, flags, (hipStream_t)stream);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

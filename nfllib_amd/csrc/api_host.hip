@@ -572,6 +572,68 @@ int nflhip_lintrans_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void 
   return NFLHIP_OK;
 }
 
+// the tensor product: the inputs share one slot (a0, a1, then b0, b1 unless it is the square), the three outputs another
+int nflhip_tensor_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, void *h_out2, const void *h_a0, const void *h_a1, const void *h_b0,
+                      const void *h_b1, size_t batch, size_t rows, int flags) {
+  int rc = tensor_check(ctx, h_out0, h_out1, h_out2, h_a0, h_a1, h_b0, h_b1, batch, rows, flags);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t ob = batch * rows * ctx->shape.n * ctx->word, nin = h_b0 ? 4 : 2;
+  Staged s(ctx);
+  if ((rc = s.in(0, nullptr, nin * ob)) || (rc = s.in(2, nullptr, 3 * ob))) return rc;
+  char *i = (char *)ctx->stage[0], *o = (char *)ctx->stage[2];
+  const void *const hin[4] = {h_a0, h_a1, h_b0, h_b1};
+  for (size_t k = 0; k < nin; ++k) {
+    if (ctx->stage_host[0]) std::memcpy(i + k * ob, hin[k], ob);
+    else HIPCHK(ctx, hipMemcpyAsync(i + k * ob, hin[k], ob, hipMemcpyHostToDevice, ctx->hstream));
+  }
+  if ((rc = nflhip_tensor_ntt_dev(ctx, o, o + ob, o + 2 * ob, i, i + ob, h_b0 ? i + 2 * ob : nullptr, h_b0 ? i + 3 * ob : nullptr, batch, rows, flags,
+                                  (void *)ctx->hstream)))
+    return rc;
+  void *const hout[3] = {h_out0, h_out1, h_out2};
+  if (!ctx->stage_host[2])
+    for (size_t k = 0; k < 3; ++k) HIPCHK(ctx, hipMemcpyAsync(hout[k], o + k * ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
+  s.pending = false;
+  if (ctx->stage_host[2])
+    for (size_t k = 0; k < 3; ++k) std::memcpy(hout[k], o + k * ob, ob);
+  return NFLHIP_OK;
+}
+
+// ciphertext multiplication: the inputs (one slot), the key and both outputs are staged whole (the outputs share one slot, out1
+// behind out0, so that the mod-down runs as one batch)
+int nflhip_mulrelin_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0, const void *h_b1,
+                        const void *h_key, size_t batch, size_t k_special, size_t alpha, int flags) {
+  int rc = mulrelin_check(ctx, h_out0, h_out1, h_a0, h_a1, h_b0, h_b1, h_key, batch, k_special, alpha, flags);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ib = batch * (nm - k_special) * row;
+  const size_t ob = (flags & NFLHIP_MULRELIN_RESCALE) ? ib - batch * row : ib, nin = h_b0 ? 4 : 2;
+  const size_t kb = 2 * keyswitch_digits(ctx, k_special, alpha) * nm * row;
+  Staged s(ctx);
+  if ((rc = s.in(0, nullptr, nin * ib)) || (rc = s.in(1, h_key, kb)) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
+  char *i = (char *)ctx->stage[0], *o = (char *)ctx->stage[2];
+  const void *const hin[4] = {h_a0, h_a1, h_b0, h_b1};
+  for (size_t k = 0; k < nin; ++k) {
+    if (ctx->stage_host[0]) std::memcpy(i + k * ib, hin[k], ib);
+    else HIPCHK(ctx, hipMemcpyAsync(i + k * ib, hin[k], ib, hipMemcpyHostToDevice, ctx->hstream));
+  }
+  if ((rc = nflhip_mulrelin_ntt_dev(ctx, o, o + ob, i, i + ib, h_b0 ? i + 2 * ib : nullptr, h_b0 ? i + 3 * ib : nullptr, ctx->stage[1], batch, k_special,
+                                    alpha, flags, (void *)ctx->hstream)))
+    return rc;
+  if (!ctx->stage_host[2]) {
+    HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out1, o + ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
+  s.pending = false;
+  if (ctx->stage_host[2]) {
+    std::memcpy(h_out0, o, ob);
+    std::memcpy(h_out1, o + ob, ob);
+  }
+  return NFLHIP_OK;
+}
+
 // sums of products across polynomials: the operands are `terms` times the size of the result, so the call is staged whole
 int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, size_t groups, size_t terms, int b_shared) {
   if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");

@@ -113,6 +113,18 @@ struct nflhip_ctx {
   size_t lt_scratch_bytes = 0;
   hipEvent_t ev_lt = nullptr;
   bool ev_lt_valid = false;
+  // ciphertext multiplication (api.hip mulrelin_run): per k_special one device block -- nm pairs (pi_j = P mod p_j, its Shoup
+  // companion; zeros on the special rows), then the constant polynomial [nm][n] that holds pi_j in every word of row j (the
+  // sequence's one-term dot) -- built on the host at the first call for that k_special; per (k_special, alpha, plan | modes) the
+  // largest batch served so far (what a call while capturing may repeat); one scratch for the tensor's components, the mod-up's
+  // input, the digits and the two sums, calls ordered on it by ev_mr.  All under mr_mu, which is taken BEFORE ks_mu and bcn_mu.
+  std::mutex mr_mu;
+  std::map<size_t, void *> mr_pi;
+  std::map<std::array<size_t, 3>, size_t> mr_warm;
+  void *mr_scratch = nullptr;
+  size_t mr_scratch_bytes = 0;
+  hipEvent_t ev_mr = nullptr;
+  bool ev_mr_valid = false;
 };
 
 void pipe_destroy(nflhip_ctx *ctx);  // api_host.hip: frees the context's host-pointer pipeline
@@ -433,6 +445,66 @@ inline int lintrans_check(const nflhip_ctx *ctx, const void *out0, const void *o
       if (keys[m] && ranges_overlap(o, ob, keys[m], kb)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: an output overlaps a key");
       if (ranges_overlap(o, ob, weights[m], wb)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: an output overlaps a weight");
     }
+  }
+  return NFLHIP_OK;
+}
+// nflhip_tensor_ntt_dev / nflhip_tensor_ntt: every argument check, before any device use.  An output may be exactly an input (the
+// same first byte); every other overlap of an output with an input or another output is refused.
+inline int tensor_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *out2, const void *a0, const void *a1,
+                        const void *b0, const void *b1, size_t batch, size_t rows, int flags) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "tensor: not on a cyclic row context");
+  if (flags) return fail(ctx, NFLHIP_ERR_INVALID, "tensor: unknown flag bits");
+  if (rows == 0 || rows > ctx->shape.nm) return fail(ctx, NFLHIP_ERR_INVALID, "tensor: rows is out of range (1 to nmoduli)");
+  if (ctx->shape.nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "tensor: more than 65535 rows");
+  if (batch == 0) return NFLHIP_OK;
+  if (!out0 || !out1 || !out2 || !a0 || !a1) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  if (!b0 != !b1) return fail(ctx, NFLHIP_ERR_INVALID, "tensor: b0 and b1 are both given, or both NULL for the square");
+  size_t ob;
+  if (__builtin_mul_overflow(batch, rows * ctx->shape.n * ctx->word, &ob)) return fail(ctx, NFLHIP_ERR_INVALID, "tensor: the size overflows");
+  const void *const outs[3] = {out0, out1, out2}, *const ins[4] = {a0, a1, b0, b1};
+  for (int o = 0; o < 3; ++o) {
+    for (int q = 0; q < o; ++q)
+      if (ranges_overlap(outs[o], ob, outs[q], ob)) return fail(ctx, NFLHIP_ERR_INVALID, "tensor: two outputs overlap");
+    for (int i = 0; i < 4; ++i)
+      if (ins[i] && ins[i] != outs[o] && ranges_overlap(outs[o], ob, ins[i], ob))
+        return fail(ctx, NFLHIP_ERR_INVALID, "tensor: an output overlaps an input without being that input");
+  }
+  return NFLHIP_OK;
+}
+// nflhip_mulrelin_ntt_dev / nflhip_mulrelin_ntt: every argument check short of the tables (a repeated modulus is found by their
+// builder, api.hip keyswitch_records), before any device use
+inline int mulrelin_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *a0, const void *a1, const void *b0,
+                          const void *b1, const void *key, size_t batch, size_t k_special, size_t alpha, int flags) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: a cyclic row context has no modulus chain");
+  const int plans = NFLHIP_MULRELIN_SEQUENCE | NFLHIP_MULRELIN_MERGED | NFLHIP_MULRELIN_FUSED, plan = flags & plans;
+  if (flags & ~(plans | NFLHIP_MULRELIN_CENTERED | NFLHIP_MULRELIN_FLOOR | NFLHIP_MULRELIN_RESCALE))
+    return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: unknown flag bits");
+  if (plan & (plan - 1)) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: one plan flag at most");
+  const size_t nm = ctx->shape.nm, dnum = keyswitch_digits(ctx, k_special, alpha);
+  if (k_special == 0 || k_special >= nm) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: k_special is out of range (1 to nmoduli - 1)");
+  if (dnum == 0) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: alpha is out of range (1 to nmoduli - k_special)");
+  if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: more than 65535 rows");
+  const size_t row = ctx->shape.n * ctx->word, L = nm - k_special;
+  if ((flags & NFLHIP_MULRELIN_RESCALE) && L < 2)
+    return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: the rescale needs two kept moduli at least (nmoduli - k_special >= 2)");
+  if (batch == 0) return NFLHIP_OK;
+  if (!out0 || !out1 || !a0 || !a1 || !key) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  if (!b0 != !b1) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: b0 and b1 are both given, or both NULL for the square");
+  size_t ib, ob, sb, kb, polys;
+  // (sb: the largest scratch of either plan -- [batch][dnum + 12][nm][n] and a polynomial)
+  if (__builtin_mul_overflow(batch, L * row, &ib) || __builtin_mul_overflow(batch, dnum + 13, &polys) || __builtin_mul_overflow(polys, nm * row, &sb) ||
+      __builtin_mul_overflow(2 * dnum, nm * row, &kb))
+    return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: the size overflows");
+  ob = (flags & NFLHIP_MULRELIN_RESCALE) ? ib - batch * row : ib;
+  if (ranges_overlap(out0, ob, out1, ob)) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: the two outputs overlap");
+  const void *const ins[4] = {a0, a1, b0, b1};
+  for (const void *o : {out0, out1}) {
+    if (ranges_overlap(o, ob, key, kb)) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: an output overlaps the key");
+    for (int i = 0; i < 4; ++i)
+      if (ins[i] && ins[i] != o && ranges_overlap(o, ob, ins[i], ib))
+        return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: an output overlaps an input without being that input");
   }
   return NFLHIP_OK;
 }

@@ -194,6 +194,21 @@ inline bool keyswitch_fused_fits(size_t L, size_t dnum, size_t n, size_t word, i
 template <typename T>
 hipError_t launch_modup_dot_fused(const Shape &s, const DevTables &t, T *acc, const T *in, const T *key, const uint64_t *const *recs, size_t batch,
                                   size_t L, size_t alpha, int centred, hipStream_t st);
+// the tensor product of two degree-1 ciphertexts (kernels_mulrelin.hip; include/nflhip.h "ciphertext multiplication"): out0 = a0 b0,
+// out1 = a0 b1 + a1 b0, out2 = a1 b1 on the first `rows` moduli, inputs dense [batch][rows][n]; b0 == b1 == nullptr: the square.
+// An output may be exactly an input.  pi == nullptr (the public entry): orows == rows, pitch01 == pitch2 == rows n.  pi = a device
+// array of nm pairs (pi_m, Shoup companion): out0 / out1 are written as pi_m d_c over orows rows with the polynomial pitch pitch01,
+// rows [rows, orows) as zeros, out2 with the pitch pitch2 (words).
+template <typename T>
+hipError_t launch_tensor_ntt(const Shape &s, const DevTables &t, T *out0, T *out1, T *out2, const T *a0, const T *a1, const T *b0, const T *b1,
+                             size_t batch, size_t rows, size_t orows, size_t pitch01, size_t pitch2, const uint64_t *pi, hipStream_t st);
+// the multiplication's one-launch plan up to the two sums: a*, b* = [batch][L][n] NTT form (b0 == b1 == nullptr: the square), key =
+// [dnum][2][nm][n], acc = [2][batch][nm][n] canonical, acc[c][b] = E(pi d_c) + sum_d U_d key[d][c] with U_d the mod-up of a1 (.) b1.
+// The LDS and the bounds of launch_modup_dot_fused (keyswitch_fused_lds / keyswitch_fused_fits): hipErrorNotSupported beyond them.
+template <typename T>
+hipError_t launch_tensor_modup_dot_fused(const Shape &s, const DevTables &t, T *acc, const T *a0, const T *a1, const T *b0, const T *b1, const T *key,
+                                         const uint64_t *const *recs, const uint64_t *pi, size_t batch, size_t L, size_t alpha, int centred,
+                                         hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);
@@ -345,6 +360,7 @@ hipError_t warm_dot(hipStream_t st);
 hipError_t warm_dot_multi(hipStream_t st);
 hipError_t warm_rotate(hipStream_t st);
 hipError_t warm_lintrans(hipStream_t st);
+hipError_t warm_mulrelin(hipStream_t st);
 hipError_t warm_decompose(hipStream_t st);
 hipError_t warm_baseconv(hipStream_t st);
 hipError_t warm_baseconv_ntt(hipStream_t st);

@@ -35,6 +35,7 @@
 #include "dot_reduce.h"
 #include "baseconv_pos.h"
 #include "ntt_lds.h"
+#include "keyswitch_fused.h"  // kFusedPos and the steps k_modup_dot_fused shares with kernels_mulrelin.hip
 
 namespace nflhip {
 
@@ -162,8 +163,6 @@ hipError_t launch_modup_digits(const Shape &s, const DevTables &t, T *out, const
   return hipGetLastError();
 }
 
-static constexpr int kFusedPos = 4;  // positions per thread of k_modup_dot_fused: n <= 2048, n / 4 threads clamped to 64 .. 1024
-
 template <typename T>
 __global__ void __launch_bounds__(1024) k_modup_dot_fused(T *__restrict__ accout, const T *__restrict__ in, const T *__restrict__ key,
                                                           const Tw<T> *__restrict__ psi, const ModConst<T> *__restrict__ mc,
@@ -189,17 +188,7 @@ __global__ void __launch_bounds__(1024) k_modup_dot_fused(T *__restrict__ accout
     // from here to the end of the polynomial a thread touches Y, Vr and B only at its own positions outside the transforms
     for (unsigned d = 0; d < dnum; ++d) {
       const unsigned s0 = d * alpha, ks = L - s0 < alpha ? L - s0 : alpha;
-      const uint64_t *__restrict__ src = recs[d];
-      for (unsigned j = threadIdx.x; j < n; j += blockDim.x) {
-        uint64_t flo = 0, fhi = 0;
-        for (unsigned i = 0; i < ks; ++i) {
-          const T w = (T)src[4 * i], wp = (T)src[4 * i + 1], p = (T)src[4 * i + 2];
-          const T y = bc_y<T>(Y[((size_t)(s0 + i) << logn) + j], w, wp, p);
-          Y[((size_t)(s0 + i) << logn) + j] = y;
-          if (centred) bc_fsum_add(flo, fhi, bc_frac<T>(y, src[4 * i + 3]));
-        }
-        if (centred) Vr[(size_t)d * n + j] = (uint16_t)bc_fsum_round(flo, fhi);  // v <= ks <= 1024
-      }
+      ks_fused_y_pass<T>(Y, Vr, recs[d], d, s0, ks, logn, n, centred);
     }
     for (unsigned r = 0; r < nm; ++r) {
       const ModConst<T> cr = mc[r];
@@ -213,19 +202,7 @@ __global__ void __launch_bounds__(1024) k_modup_dot_fused(T *__restrict__ accout
         const T *k0 = key + (((size_t)(2 * d) * nm + r) << logn), *k1 = k0 + ((size_t)nm << logn);
         const bool own = r - s0 < ks;  // (unsigned: s0 <= r < s0 + ks) a row of the digit: the NTT-form input word
         if (!own) {
-          const uint64_t *__restrict__ src = recs[d];
-          const uint64_t *__restrict__ dst = src + 4 * (size_t)ks, *__restrict__ c = dst + 8 * (size_t)nm + (size_t)r * ks;
-          const T qj = (T)dst[8 * r + 1], qj_sh = (T)dst[8 * r + 2];
-          for (unsigned j = threadIdx.x; j < n; j += blockDim.x) {
-            acc_t acc = 0;
-            for (unsigned i = 0; i < ks; ++i) {
-              acc += (acc_t)Y[((size_t)(s0 + i) << logn) + j] * (acc_t)(T)c[i];
-              if ((i + 1) % kDotChunk == 0 && i + 1 < ks) acc = (acc_t)red.reduce(acc);  // a full chunk behind, more to come
-            }
-            B[j] = bc_finish<T>(red.reduce(acc), centred != 0, centred ? (T)Vr[(size_t)d * n + j] : (T)0, qj, qj_sh, false, (T)0, (T)0, (T)0, p);
-          }
-          resc_fwd_lds<T>(B, psi + ((size_t)r << logn), logn, p, (T)(2 * p));
-          __syncthreads();
+          ks_fused_conv_row<T>(B, Y, Vr, recs[d], red, psi + ((size_t)r << logn), d, s0, ks, r, nm, logn, n, centred, p);
         }
 #pragma unroll
         for (int k = 0; k < kFusedPos; ++k) {

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (LINTRANS_CENTERED, LINTRANS_FLOOR, LINTRANS_HOISTED, LINTRANS_MAX_TERMS, LINTRANS_SEQUENCE, MAC_MAX_TERMS, MAC_DOUBLE_BUFFER, DOT_MULTI_MAX_OUTPUTS, ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_HOISTED, ROTATE_MAX_OUTPUTS, ROTATE_SEQUENCE, KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
+from ._lib import (MULRELIN_CENTERED, MULRELIN_FLOOR, MULRELIN_FUSED, MULRELIN_MERGED, MULRELIN_RESCALE, MULRELIN_SEQUENCE, LINTRANS_CENTERED, LINTRANS_FLOOR, LINTRANS_HOISTED, LINTRANS_MAX_TERMS, LINTRANS_SEQUENCE, MAC_MAX_TERMS, MAC_DOUBLE_BUFFER, DOT_MULTI_MAX_OUTPUTS, ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_HOISTED, ROTATE_MAX_OUTPUTS, ROTATE_SEQUENCE, KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -586,6 +586,79 @@ class Engine:
         kv = (C.c_uint64 * len(ks))(*ks)
         self._chk(self.lib.nflhip_lintrans_ntt(self.ctx, _vp(out0), _vp(out1), _vp(c0), _vp(c1), pk, pw, kv, len(ks), batch, k_special, alpha,
                                                self._lt_flags(centered, floor, plan)))
+        return out0, out1
+
+    # ---- ciphertext multiplication (include/nflhip.h "ciphertext multiplication") ----
+    _MR_PLAN = {None: 0, "sequence": MULRELIN_SEQUENCE, "merged": MULRELIN_MERGED, "fused": MULRELIN_FUSED}
+
+    def _mr_flags(self, rescale, centered, floor, plan):
+        return (MULRELIN_RESCALE if rescale else 0) | (MULRELIN_CENTERED if centered else 0) | (MULRELIN_FLOOR if floor else 0) | self._MR_PLAN[plan]
+
+    def _tensor_rows(self, a0, a1, b0, b1, rows, size, contiguous):
+        rows = self.nmoduli if rows is None else rows
+        if (b0 is None) != (b1 is None):
+            raise ValueError("b0 and b1 are both given, or both None for the square")
+        ops = [x for x in (a0, a1, b0, b1) if x is not None]
+        if not 1 <= rows <= self.nmoduli or size(a0) % (rows * self.degree) or any(size(x) != size(a0) or not contiguous(x) for x in ops):
+            raise ValueError("a0, a1, b0, b1 are contiguous [batch, rows, n] blocks of one size")
+        return rows, size(a0) // (rows * self.degree)
+
+    def tensor_ntt(self, a0, a1, b0=None, b1=None, rows=None, outs=None, stream=None):
+        """the tensor product of the ciphertexts (a0, a1) and (b0, b1), each component a [batch, rows, n] block over the first `rows`
+        moduli (default: all): (a0 b0, a0 b1 + a1 b0, a1 b1) row by row, one launch.  b0 = b1 = None: the square, (a0^2, 2 a0 a1,
+        a1^2).  `outs` = three such tensors (any may be one of the inputs), else views of one new [3, batch, rows, n] tensor."""
+        rows, batch = self._tensor_rows(a0, a1, b0, b1, rows, lambda x: x.numel(), lambda x: x.is_contiguous())
+        if outs is None:
+            o = _torch().empty((3, batch, rows, self.degree), dtype=self.torch_dtype, device=a0.device)
+            outs = (o[0], o[1], o[2])
+        elif len(outs) != 3 or any(o.numel() != a0.numel() or not o.is_contiguous() for o in outs):
+            raise ValueError("outs are three contiguous [batch, rows, n] tensors")
+        self._chk(self.lib.nflhip_tensor_ntt_dev(self.ctx, _vp(outs[0]), _vp(outs[1]), _vp(outs[2]), _vp(a0), _vp(a1), _vp(b0), _vp(b1), batch, rows,
+                                                 0, self._stream(stream)))
+        return outs
+
+    def h_tensor_ntt(self, a0, a1, b0=None, b1=None, rows=None):
+        """host-pointer variant: numpy blocks [batch, rows, n] -> (out0, out1, out2)"""
+        a0, a1, b0, b1 = (None if x is None else np.ascontiguousarray(x, dtype=self.np_dtype) for x in (a0, a1, b0, b1))
+        rows, batch = self._tensor_rows(a0, a1, b0, b1, rows, lambda x: x.size, lambda x: True)
+        outs = tuple(np.empty((batch, rows, self.degree), dtype=self.np_dtype) for _ in range(3))
+        self._chk(self.lib.nflhip_tensor_ntt(self.ctx, _vp(outs[0]), _vp(outs[1]), _vp(outs[2]), _vp(a0), _vp(a1), _vp(b0), _vp(b1), batch, rows, 0))
+        return outs
+
+    def mul_relin_ntt(self, a0, a1, b0, b1, key, k_special, alpha, rescale=False, centered=False, floor=False, out=None, plan=None, stream=None):
+        """the product of the ciphertexts (a0, a1) and (b0, b1) with relinearisation, one call: NTT-form [batch, L, n] batches with
+        L = nm - k_special (b0 = b1 = None: the square), key = [dnum, 2, nm, n] as key_switch_ntt takes it, from s^2 to s.  The tensor
+        product's first two components go into the key-switch sums of the third before the ONE mod-down.  rescale=True divides by
+        the last kept modulus in the same rounding: the results are [batch, L - 1, n].  Returns (out0, out1); `out` = a pair of
+        such tensors (each may be one of the inputs), else both are views of one new [2, batch, L or L - 1, n] tensor.  plan
+        "sequence" / "merged" / "fused" forces a plan.  The first call for a (k_special, alpha), or a larger batch, allocates: make it before
+        a graph capture."""
+        L = self.nmoduli - k_special
+        if L <= 0:
+            raise ValueError("k_special is 1 to nm - 1")
+        _, batch = self._tensor_rows(a0, a1, b0, b1, L, lambda x: x.numel(), lambda x: x.is_contiguous())
+        if key.numel() != 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly or not key.is_contiguous():
+            raise ValueError("key holds dnum * 2 polynomials of this context")
+        if out is None:
+            both = _torch().empty((2, batch, L - 1 if rescale else L, self.degree), dtype=self.torch_dtype, device=a0.device)
+            out = (both[0], both[1])
+        elif len(out) != 2 or any(o.numel() != batch * (L - 1 if rescale else L) * self.degree or not o.is_contiguous() for o in out):
+            raise ValueError("out is a pair of contiguous [batch, L, n] tensors ([batch, L - 1, n] with rescale)")
+        self._chk(self.lib.nflhip_mulrelin_ntt_dev(self.ctx, _vp(out[0]), _vp(out[1]), _vp(a0), _vp(a1), _vp(b0), _vp(b1), _vp(key), batch, k_special,
+                                                   alpha, self._mr_flags(rescale, centered, floor, plan), self._stream(stream)))
+        return out
+
+    def h_mul_relin_ntt(self, a0, a1, b0, b1, key, k_special, alpha, rescale=False, centered=False, floor=False, plan=None):
+        """host-pointer variant: numpy a0, a1, b0, b1 = [batch, L, n] (b0 = b1 = None: the square), key = [dnum, 2, nm, n] -> (out0, out1)"""
+        a0, a1, b0, b1 = (None if x is None else np.ascontiguousarray(x, dtype=self.np_dtype) for x in (a0, a1, b0, b1))
+        key = np.ascontiguousarray(key, dtype=self.np_dtype)
+        L = self.nmoduli - k_special
+        if L <= 0 or key.size != 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly:
+            raise ValueError("k_special is 1 to nm - 1, key [dnum, 2, nm, n]")
+        _, batch = self._tensor_rows(a0, a1, b0, b1, L, lambda x: x.size, lambda x: True)
+        out0, out1 = (np.empty((batch, L - 1 if rescale else L, self.degree), dtype=self.np_dtype) for _ in range(2))
+        self._chk(self.lib.nflhip_mulrelin_ntt(self.ctx, _vp(out0), _vp(out1), _vp(a0), _vp(a1), _vp(b0), _vp(b1), _vp(key), batch, k_special, alpha,
+                                               self._mr_flags(rescale, centered, floor, plan)))
         return out0, out1
 
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
