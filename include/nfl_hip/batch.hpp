@@ -298,6 +298,59 @@ template <class P> class device_batch {
                                                      key.data(), a0.n_, Q::nmoduli - P::nmoduli, alpha, flags, key.queue()), "mul_relin_ntt");
     key.sync();
   }
+  // The two at a level (include/nflhip.h "leveled key switching"): this ring's moduli count is the level Lv, and `key` is a batch of the
+  // ring with M moduli holding the 2 dnum_L polynomials of the ONE top-level key, of which the first 2 ceil(Lv / alpha) are read.  The
+  // last K moduli of the key's ring are the special ones: K cannot be deduced from the types any more, so it is explicit, and
+  // Lv <= M - K is checked at compile time.  Streams as in assign_key_switch.
+  template <size_t K, class Q>
+  static void assign_key_switch_level(device_batch &out0, device_batch &out1, const device_batch &src, const device_batch<Q> &key, size_t alpha,
+                                      bool centered = false, bool floor = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && K >= 1 && K < Q::nmoduli &&
+                      P::nmoduli <= Q::nmoduli - K,
+                  "assign_key_switch_level: the key's ring has the same limbs and degree, K special moduli and at least Lv others");
+    if (alpha == 0 || alpha > Q::nmoduli - K) throw std::runtime_error("nfl(hip): key_switch_level: alpha is out of range (1 to the key's ordinary moduli)");
+    if (out0.size() != src.size() || out1.size() != src.size()) throw std::runtime_error("nfl(hip): batch sizes differ");
+    if (key.size() != 2 * ((Q::nmoduli - K + alpha - 1) / alpha)) throw std::runtime_error("nfl(hip): the key batch holds the 2 * dnum polynomials of the top level");
+    if (out0.device() != key.device() || out1.device() != key.device() || src.device() != key.device())
+      throw std::runtime_error("nfl(hip): key_switch_level operands on different devices");
+    src.sync();
+    src.strict("key_switch_level");
+    key.strict("key_switch_level");
+    int flags = centered ? NFLHIP_KEYSWITCH_CENTERED : 0;
+    if (floor) flags |= NFLHIP_KEYSWITCH_FLOOR;
+    detail::check(key.ctx(), nflhip_keyswitch_level_ntt_dev(key.ctx(), out0.d_, out1.d_, src.d_, key.data(), src.n_, K, alpha, P::nmoduli, flags,
+                                                            key.queue()), "key_switch_level_ntt");
+    key.sync();
+  }
+  template <size_t K, class O, class Q>
+  static void assign_mul_relin_level(device_batch<O> &out0, device_batch<O> &out1, const device_batch &a0, const device_batch &a1,
+                                     const device_batch *b0, const device_batch *b1, const device_batch<Q> &key, size_t alpha, bool centered = false,
+                                     bool floor = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && K >= 1 && K < Q::nmoduli &&
+                      P::nmoduli <= Q::nmoduli - K,
+                  "assign_mul_relin_level: the key's ring has the same limbs and degree, K special moduli and at least Lv others");
+    static_assert(std::is_same<typename O::value_type, value_type>::value && O::degree == P::degree &&
+                      (O::nmoduli == P::nmoduli || O::nmoduli + 1 == P::nmoduli),
+                  "assign_mul_relin_level: the outputs live in the inputs' ring, or in the ring with one modulus less (the rescale)");
+    if (alpha == 0 || alpha > Q::nmoduli - K) throw std::runtime_error("nfl(hip): mul_relin_level: alpha is out of range (1 to the key's ordinary moduli)");
+    if (!b0 != !b1) throw std::runtime_error("nfl(hip): mul_relin_level: b0 and b1 are both given, or both NULL for the square");
+    if (out0.size() != a0.size() || out1.size() != a0.size() || a1.size() != a0.size() || (b0 && (b0->size() != a0.size() || b1->size() != a0.size())))
+      throw std::runtime_error("nfl(hip): batch sizes differ");
+    if (key.size() != 2 * ((Q::nmoduli - K + alpha - 1) / alpha)) throw std::runtime_error("nfl(hip): the key batch holds the 2 * dnum polynomials of the top level");
+    if (out0.device() != key.device() || out1.device() != key.device() || a0.device() != key.device() || a1.device() != key.device() ||
+        (b0 && (b0->device() != key.device() || b1->device() != key.device())))
+      throw std::runtime_error("nfl(hip): mul_relin_level operands on different devices");
+    a0.sync();
+    out0.sync();
+    a0.strict("mul_relin_level"), a1.strict("mul_relin_level"), key.strict("mul_relin_level");
+    if (b0) b0->strict("mul_relin_level"), b1->strict("mul_relin_level");
+    int flags = (centered ? NFLHIP_MULRELIN_CENTERED : 0) | (floor ? NFLHIP_MULRELIN_FLOOR : 0);
+    if (O::nmoduli != P::nmoduli) flags |= NFLHIP_MULRELIN_RESCALE;
+    const void *const x0 = b0 ? b0->d_ : nullptr, *const x1 = b1 ? b1->d_ : nullptr;
+    detail::check(key.ctx(), nflhip_mulrelin_level_ntt_dev(key.ctx(), out0.data(), out1.data(), a0.d_, a1.d_, x0, x1, key.data(), a0.n_, K, alpha,
+                                                           P::nmoduli, flags, key.queue()), "mul_relin_level_ntt");
+    key.sync();
+  }
   // Sums of products across polynomials (include/nflhip.h): this batch holds `groups` polynomials, a and b groups * terms each,
   // term-minor: (*this)[g] = sum_j a[g * terms + j] * b[g * terms + j].  assign_matvec: v holds the `terms` polynomials every
   // group shares, (*this)[g] = sum_j m[g * terms + j] * v[j].  The operands must be other batches.

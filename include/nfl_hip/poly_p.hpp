@@ -491,6 +491,94 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out1._p = d1;
   }
 
+  // The two at a level (nfl::key_switch_level_ntt<K> / mul_relin_level_ntt<K> below; include/nflhip.h "leveled key switching").  This
+  // ring type is the KEY's: NbModuli moduli, the last K special -- explicit, the types no longer tell.  The operands live in the ring
+  // with LO <= NbModuli - K moduli, the level; the outputs of the multiplication in the ring with OO == LO or LO - 1 moduli.  `key` is
+  // the ONE top-level key, 2 dnum_L polynomials [term][component]; only the 2 dnum_l LIVE ones, dnum_l = ceil(LO / alpha), are touched
+  // and gathered into the device buffer -- whole polynomials of this ring, so that the entry finds phys(r) itself; a live polynomial
+  // that is empty (moved from) is refused, a dead one is never looked at.  Ordering, payloads and errors as
+  // key_switch_into / mul_relin_into.  Never fused into a queue's rewrites.
+  template <size_t K, size_t LO> static void key_switch_level_into(poly_p<T, Degree, LO> &out0, poly_p<T, Degree, LO> &out1,
+                                                                   poly_p<T, Degree, LO> const &in, poly_p const *key, size_t alpha, bool centered,
+                                                                   bool floor) {
+    static_assert(K >= 1 && K < NbModuli && LO >= 1 && LO <= NbModuli - K, "nfl::key_switch_level_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+    typedef poly_p<T, Degree, LO> out_t;
+    if (alpha == 0 || alpha > NbModuli - K) throw std::runtime_error("nfl(hip): key_switch_level_ntt: alpha is out of range (1 to the key ring's ordinary moduli)");
+    const size_t live = 2 * ((LO + alpha - 1) / alpha), pb = sizeof(T) * Degree * NbModuli;
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    typename out_t::ptr_type src = in._p;
+    typename out_t::ptr_type d0 = out_t::fresh(), d1 = out_t::fresh();
+    std::vector<ptr_type> kept;
+    for (size_t t = 0; t < live; ++t) {  // (the live polynomials only: the rest of the key may be anything, even moved from)
+      if (!key[t]._p) throw std::runtime_error("nfl(hip): a live key polynomial is empty (moved from)");
+      kept.push_back(key[t]._p);
+    }
+    const void *s = src->dev_ro();
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo(), *kgat = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &kgat, live * pb), "key_switch_level_ntt");
+    int rc = NFLHIP_OK;
+    for (size_t t = 0; t < live && rc == NFLHIP_OK; ++t)
+      rc = nflhip_memcpy_d2d(ctx_t::get(), static_cast<char *>(kgat) + t * pb, kept[t]->dev_ro(), pb, ctx_t::queue());
+    if (rc == NFLHIP_OK) rc = nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue());
+    int flags = centered ? NFLHIP_KEYSWITCH_CENTERED : 0;
+    if (floor) flags |= NFLHIP_KEYSWITCH_FLOOR;
+    if (rc == NFLHIP_OK) rc = nflhip_keyswitch_level_ntt_dev(ctx_t::get(), o0, o1, s, kgat, 1, K, alpha, LO, flags, ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered key goes)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), kgat);
+      throw std::runtime_error("nfl(hip): key_switch_level_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), kgat);
+    detail::check(ctx_t::get(), rs, "key_switch_level_ntt");
+    out0._p = d0;
+    out1._p = d1;
+  }
+  template <size_t K, size_t LO, size_t OO> static void mul_relin_level_into(poly_p<T, Degree, OO> &out0, poly_p<T, Degree, OO> &out1,
+                                                                             poly_p<T, Degree, LO> const &a0, poly_p<T, Degree, LO> const &a1,
+                                                                             poly_p<T, Degree, LO> const *b0, poly_p<T, Degree, LO> const *b1,
+                                                                             poly_p const *key, size_t alpha, bool centered, bool floor) {
+    static_assert(K >= 1 && K < NbModuli && LO >= 1 && LO <= NbModuli - K, "nfl::mul_relin_level_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+    static_assert(OO == LO || OO + 1 == LO, "nfl::mul_relin_level_ntt<K>: the outputs live in the inputs' ring, or in the ring with one modulus less");
+    typedef poly_p<T, Degree, LO> in_t;
+    typedef poly_p<T, Degree, OO> out_t;
+    if (alpha == 0 || alpha > NbModuli - K) throw std::runtime_error("nfl(hip): mul_relin_level_ntt: alpha is out of range (1 to the key ring's ordinary moduli)");
+    if (!b0 != !b1) throw std::runtime_error("nfl(hip): mul_relin_level_ntt: b0 and b1 are both given, or both NULL for the square");
+    const size_t live = 2 * ((LO + alpha - 1) / alpha), pb = sizeof(T) * Degree * NbModuli;
+    lazy_t::inst().flush();
+    in_t::lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    typename in_t::ptr_type s0 = a0._p, s1 = a1._p, t0 = b0 ? b0->_p : typename in_t::ptr_type(), t1 = b1 ? b1->_p : typename in_t::ptr_type();
+    typename out_t::ptr_type d0 = out_t::fresh(), d1 = out_t::fresh();
+    std::vector<ptr_type> kept;
+    for (size_t t = 0; t < live; ++t) {  // (the live polynomials only: the rest of the key may be anything, even moved from)
+      if (!key[t]._p) throw std::runtime_error("nfl(hip): a live key polynomial is empty (moved from)");
+      kept.push_back(key[t]._p);
+    }
+    const void *p_a0 = s0->dev_ro(), *p_a1 = s1->dev_ro(), *p_b0 = b0 ? t0->dev_ro() : nullptr, *p_b1 = b1 ? t1->dev_ro() : nullptr;
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo(), *kgat = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &kgat, live * pb), "mul_relin_level_ntt");
+    int rc = NFLHIP_OK;
+    for (size_t t = 0; t < live && rc == NFLHIP_OK; ++t)
+      rc = nflhip_memcpy_d2d(ctx_t::get(), static_cast<char *>(kgat) + t * pb, kept[t]->dev_ro(), pb, ctx_t::queue());
+    if (rc == NFLHIP_OK) rc = nflhip_stream_sync(in_t::ctx_t::get(), in_t::ctx_t::queue());
+    if (rc == NFLHIP_OK && OO != LO) rc = nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue());
+    int flags = (centered ? NFLHIP_MULRELIN_CENTERED : 0) | (floor ? NFLHIP_MULRELIN_FLOOR : 0);
+    if (OO != LO) flags |= NFLHIP_MULRELIN_RESCALE;
+    if (rc == NFLHIP_OK) rc = nflhip_mulrelin_level_ntt_dev(ctx_t::get(), o0, o1, p_a0, p_a1, p_b0, p_b1, kgat, 1, K, alpha, LO, flags, ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered key goes)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), kgat);
+      throw std::runtime_error("nfl(hip): mul_relin_level_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), kgat);
+    detail::check(ctx_t::get(), rs, "mul_relin_level_ntt");
+    out0._p = d0;
+    out1._p = d1;
+  }
+
   // The tensor product (nfl::tensor_ntt below): the deferred queue of this ring type runs first, then one launch on its stream.  The
   // results get payloads of their own, so an output may be an input and copy-on-write sharers of the outputs' old values keep them.
   static void tensor_into(poly_p &out0, poly_p &out1, poly_p &out2, poly_p const &a0, poly_p const &a1, poly_p const *b0, poly_p const *b1) {
@@ -832,6 +920,95 @@ void mul_relin_rescale_ntt(poly_p<T, D, L - 1> &out0, poly_p<T, D, L - 1> &out1,
                            bool floor = false) {
   static_assert(L >= 2, "nfl::mul_relin_rescale_ntt drops the last kept modulus: the ciphertexts need at least two");
   poly_p<T, D, M>::template mul_relin_into<L, L - 1>(out0, out1, a0, a1, &b0, &b1, key, alpha, centered, floor);
+}
+
+/* The same BELOW the top level (include/nflhip.h "leveled key switching"): x, y0, y1, a*, b* in the ring with Lv moduli, the level; the
+ * key is the ONE top-level key in the ring with M moduli whose last K are the special ones, 2 dnum_L polynomials in [term][component]
+ * order, dnum_L = ceil((M - K) / alpha).  Lv comes from the types; K cannot be deduced any more, so it is explicit:
+ * nfl::key_switch_level_ntt<K>(y0, y1, x, key, alpha).  Lv <= M - K is checked at compile time.  Only the rows [0, Lv) and the K special
+ * rows of the first ceil(Lv / alpha) digits of the key are read; on poly_p only those 2 ceil(Lv / alpha) polynomials are gathered.
+ * mul_relin_rescale_level_ntt<K>: the outputs live in the ring with Lv - 1 moduli.  Never fused into a queue's rewrites. */
+namespace detail {
+template <size_t K, class T, size_t D, size_t Lv, size_t O, size_t M>
+void mul_relin_level_host(poly<T, D, O> &out0, poly<T, D, O> &out1, poly<T, D, Lv> const &a0, poly<T, D, Lv> const &a1, poly<T, D, Lv> const *b0,
+                          poly<T, D, Lv> const *b1, poly<T, D, M> const *key, size_t alpha, bool centered, bool floor) {
+  static_assert(K >= 1 && K < M && Lv >= 1 && Lv <= M - K, "nfl::mul_relin_level_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+  static_assert(O == Lv || O + 1 == Lv, "nfl::mul_relin_level_ntt<K>: the outputs live in the inputs' ring, or in the ring with one modulus less");
+  typedef poly<T, D, O> S;
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  S *t0 = S::make_temp(), *t1 = S::make_temp();  // (an output may be an input)
+  int flags = (centered ? NFLHIP_MULRELIN_CENTERED : 0) | (floor ? NFLHIP_MULRELIN_FLOOR : 0);
+  if (O != Lv) flags |= NFLHIP_MULRELIN_RESCALE;
+  const int rc = nflhip_mulrelin_level_ntt(P::ctx(), t0->data(), t1->data(), a0.cdata(), a1.cdata(), b0 ? b0->cdata() : nullptr,
+                                           b1 ? b1->cdata() : nullptr, key->cdata(), 1, K, alpha, Lv, flags);
+  if (rc == 0) {
+    std::memcpy(static_cast<void *>(out0.data()), t0->cdata(), sizeof(S));
+    std::memcpy(static_cast<void *>(out1.data()), t1->cdata(), sizeof(S));
+  }
+  S::drop_temp(t0);
+  S::drop_temp(t1);
+  check(P::ctx(), rc, "mul_relin_level_ntt");
+}
+}  // namespace detail
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void key_switch_level_ntt(poly<T, D, Lv> &y0, poly<T, D, Lv> &y1, poly<T, D, Lv> const &x, poly<T, D, M> const *key, size_t alpha, bool centered = false,
+                          bool floor = false) {
+  static_assert(K >= 1 && K < M && Lv >= 1 && Lv <= M - K, "nfl::key_switch_level_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+  typedef poly<T, D, Lv> S;
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  S *t0 = S::make_temp(), *t1 = S::make_temp();  // (an output may be `x`)
+  int flags = centered ? NFLHIP_KEYSWITCH_CENTERED : 0;
+  if (floor) flags |= NFLHIP_KEYSWITCH_FLOOR;
+  const int rc = nflhip_keyswitch_level_ntt(P::ctx(), t0->data(), t1->data(), x.cdata(), key->cdata(), 1, K, alpha, Lv, flags);
+  if (rc == 0) {
+    std::memcpy(static_cast<void *>(y0.data()), t0->cdata(), sizeof(S));
+    std::memcpy(static_cast<void *>(y1.data()), t1->cdata(), sizeof(S));
+  }
+  S::drop_temp(t0);
+  S::drop_temp(t1);
+  detail::check(P::ctx(), rc, "key_switch_level_ntt");
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void key_switch_level_ntt(poly_p<T, D, Lv> &y0, poly_p<T, D, Lv> &y1, poly_p<T, D, Lv> const &x, poly_p<T, D, M> const *key, size_t alpha,
+                          bool centered = false, bool floor = false) {
+  poly_p<T, D, M>::template key_switch_level_into<K, Lv>(y0, y1, x, key, alpha, centered, floor);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void mul_relin_level_ntt(poly<T, D, Lv> &out0, poly<T, D, Lv> &out1, poly<T, D, Lv> const &a0, poly<T, D, Lv> const &a1, poly<T, D, Lv> const &b0,
+                         poly<T, D, Lv> const &b1, poly<T, D, M> const *key, size_t alpha, bool centered = false, bool floor = false) {
+  detail::mul_relin_level_host<K, T, D, Lv, Lv, M>(out0, out1, a0, a1, &b0, &b1, key, alpha, centered, floor);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void mul_relin_level_ntt(poly_p<T, D, Lv> &out0, poly_p<T, D, Lv> &out1, poly_p<T, D, Lv> const &a0, poly_p<T, D, Lv> const &a1,
+                         poly_p<T, D, Lv> const &b0, poly_p<T, D, Lv> const &b1, poly_p<T, D, M> const *key, size_t alpha, bool centered = false,
+                         bool floor = false) {
+  poly_p<T, D, M>::template mul_relin_level_into<K, Lv, Lv>(out0, out1, a0, a1, &b0, &b1, key, alpha, centered, floor);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void square_relin_level_ntt(poly<T, D, Lv> &out0, poly<T, D, Lv> &out1, poly<T, D, Lv> const &a0, poly<T, D, Lv> const &a1, poly<T, D, M> const *key,
+                            size_t alpha, bool centered = false, bool floor = false) {
+  detail::mul_relin_level_host<K, T, D, Lv, Lv, M>(out0, out1, a0, a1, nullptr, nullptr, key, alpha, centered, floor);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void square_relin_level_ntt(poly_p<T, D, Lv> &out0, poly_p<T, D, Lv> &out1, poly_p<T, D, Lv> const &a0, poly_p<T, D, Lv> const &a1,
+                            poly_p<T, D, M> const *key, size_t alpha, bool centered = false, bool floor = false) {
+  poly_p<T, D, M>::template mul_relin_level_into<K, Lv, Lv>(out0, out1, a0, a1, nullptr, nullptr, key, alpha, centered, floor);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void mul_relin_rescale_level_ntt(poly<T, D, Lv - 1> &out0, poly<T, D, Lv - 1> &out1, poly<T, D, Lv> const &a0, poly<T, D, Lv> const &a1,
+                                 poly<T, D, Lv> const &b0, poly<T, D, Lv> const &b1, poly<T, D, M> const *key, size_t alpha, bool centered = false,
+                                 bool floor = false) {
+  static_assert(Lv >= 2, "nfl::mul_relin_rescale_level_ntt drops the last live modulus: the level is at least two");
+  detail::mul_relin_level_host<K, T, D, Lv, Lv - 1, M>(out0, out1, a0, a1, &b0, &b1, key, alpha, centered, floor);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void mul_relin_rescale_level_ntt(poly_p<T, D, Lv - 1> &out0, poly_p<T, D, Lv - 1> &out1, poly_p<T, D, Lv> const &a0, poly_p<T, D, Lv> const &a1,
+                                 poly_p<T, D, Lv> const &b0, poly_p<T, D, Lv> const &b1, poly_p<T, D, M> const *key, size_t alpha,
+                                 bool centered = false, bool floor = false) {
+  static_assert(Lv >= 2, "nfl::mul_relin_rescale_level_ntt drops the last live modulus: the level is at least two");
+  poly_p<T, D, M>::template mul_relin_level_into<K, Lv, Lv - 1>(out0, out1, a0, a1, &b0, &b1, key, alpha, centered, floor);
 }
 
 /* Hoisted rotations (include/nflhip.h "hoisted rotations"): the ciphertext (c0, c1) in the ring with L moduli rotated by ks[m], m <

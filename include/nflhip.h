@@ -613,6 +613,43 @@ int nflhip_mulrelin_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const v
 int nflhip_mulrelin_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0,
                         const void *h_b1, const void *h_key, size_t batch, size_t k_special, size_t alpha, int flags);   /* staged host variant */
 
+/* ---- leveled key switching and multiplication: one key for every level --------------------------
+ * The two entries above on a ciphertext BELOW the context's top level -- what nflhip_mulrelin_ntt_dev with NFLHIP_MULRELIN_RESCALE
+ * returns -- with the ONE top-level key: no context and no copy of the keys per level.  The context has nm = nmoduli moduli, the
+ * last k_special of them special, L = nm - k_special, as above.  A level is l with 1 <= l <= L.
+ *   live rows    A_l = [0, l) and [L, nm): l + k_special rows;  phys(r) = r for r < l, r + (L - l) from there on
+ *   digits       S_d = [d alpha, min((d + 1) alpha, l)), dnum_l = ceil(l / alpha) (nflhip_keyswitch_level_digits); the last live digit
+ *                may be shorter than it is at the top level, and alpha may exceed l (one short digit)
+ *   key          unchanged: [dnum_L][2][nmoduli][degree], NTT form over the full context.  Only key[d][c][phys(r)] is read, for
+ *                d < dnum_l and r < l + k_special: rows [l, L) of the key and digits >= dnum_l are never read
+ *   in, a*, b*   [batch][l][degree], NTT form, the dense layout over the first l moduli
+ *   out0, out1   [batch][l][degree]; nflhip_mulrelin_level_* with NFLHIP_MULRELIN_RESCALE [batch][l - 1][degree]
+ * Definition, word for word: let C_l be the context over the moduli (p_j : j in A_l), in that order, and key_l[d][c][r] =
+ * key[d][c][phys(r)].  A level-l call returns the words of nflhip_keyswitch_ntt_dev / nflhip_mulrelin_ntt_dev on C_l with key_l,
+ * k_special and min(alpha, l).  For l = L it is that entry on this context itself.  The mod-down drops the k_special special rows
+ * onto rows [0, l); with RESCALE the multiplication drops rows {l - 1} and [L, nm), the last k_special + 1 rows of C_l (it needs
+ * l >= 2); the tensor product runs on l rows; pi_j = P mod p_j is unchanged.  No new rounding rule.
+ * Flags, plans, modes and the overlap rules are those of the two entries above with L read as l throughout -- the one-launch
+ * kernels need (l + 1) * degree * (limb_bits / 8) [+ 2 * dnum_l * degree, centred] <= 65536 bytes, so a top level that does not
+ * fit may fit lower down.  The level context C_l is created at the first call for a (k_special, l) and lives with this context;
+ * tables and scratch are per (k_special, alpha, l, plan, modes) and sized by l + k_special rows.  The first-call, larger-batch and
+ * while-capturing rules are those of the key switch: the first call for a level while capturing is NFLHIP_ERR_UNSUPPORTED, nothing
+ * is enqueued and the stream stays usable.  The key is read where it lies: the kernels that read it (the inner products and the two
+ * one-launch kernels) have instances that know the parent's pitch and the hole of L - l rows.
+ * NFLHIP_ERR_INVALID, nothing enqueued: what the two entries above refuse, and level == 0, level > L, RESCALE with level == 1.
+ * The host variants stage the operands and the 2 dnum_l key polynomials that are read. */
+size_t nflhip_keyswitch_level_digits(const nflhip_ctx *ctx, size_t k_special, size_t alpha, size_t level);   /* dnum at that level; 0 for invalid arguments */
+int nflhip_keyswitch_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_in, const void *d_key, size_t batch,
+                                   size_t k_special, size_t alpha, size_t level, int flags, void *stream);
+int nflhip_keyswitch_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_in, const void *h_key, size_t batch,
+                               size_t k_special, size_t alpha, size_t level, int flags);   /* staged host variant */
+int nflhip_mulrelin_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_a0, const void *d_a1, const void *d_b0,
+                                  const void *d_b1, const void *d_key, size_t batch, size_t k_special, size_t alpha, size_t level,
+                                  int flags, void *stream);
+int nflhip_mulrelin_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0,
+                              const void *h_b1, const void *h_key, size_t batch, size_t k_special, size_t alpha, size_t level,
+                              int flags);   /* staged host variant */
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

@@ -95,6 +95,11 @@ SYMBOLS = [
     ("nflhip_tensor_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i]),
     ("nflhip_mulrelin_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _vp]),
     ("nflhip_mulrelin_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i]),
+    ("nflhip_keyswitch_level_digits", _sz, [_vp, _sz, _sz, _sz]),
+    ("nflhip_keyswitch_level_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_keyswitch_level_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _i]),
+    ("nflhip_mulrelin_level_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_mulrelin_level_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _i]),
     ("nflhip_gadget_mul_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),

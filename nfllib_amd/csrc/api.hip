@@ -491,6 +491,8 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   if (ctx->resc_scratch) (void)hipFree(ctx->resc_scratch);
   for (auto &kv : ctx->bcn_child) nflhip_ctx_destroy(kv.second);
   ctx->bcn_child.clear();
+  for (auto &kv : ctx->lvl_child) nflhip_ctx_destroy(kv.second);
+  ctx->lvl_child.clear();
   (void)hipSetDevice(ctx->device);
   if (ctx->ev_bcn) (void)hipEventDestroy(ctx->ev_bcn);
   for (int k = 0; k < 2; ++k)
@@ -1076,6 +1078,63 @@ int nflhip_moddown_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_
   return baseconv_ntt_run(ctx, d_out, d_in, batch, kept, k, 0, kept, flags, !(flags & NFLHIP_MODDOWN_FLOOR), true, (hipStream_t)stream);
 }
 
+// Calls below the top level (kernels_level.hip; include/nflhip.h "leveled key switching").  The level context C_l over the rows
+// [0, level) and [nm - K, nm) of this one -- a subsequence of the moduli, in their order: created on first use, never while
+// capturing, destroyed with this context.  keyswitch_run and mulrelin_run then run on it as they are, with its own records, scratch,
+// events and warm maps; the key alone stays in this context's layout, described by a KeyLevel that travels to the three launchers
+// which read it (dot_key and the two one-launch kernels).
+static int level_child(nflhip_ctx *ctx, size_t K, size_t level, bool cap, nflhip_ctx **out) {
+  std::lock_guard<std::mutex> lk(ctx->bcn_mu);
+  const std::array<size_t, 2> key = {K, level};
+  auto it = ctx->lvl_child.find(key);
+  if (it != ctx->lvl_child.end()) {
+    *out = it->second;
+    return NFLHIP_OK;
+  }
+  if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "level: the first call at a (k_special, level) creates its context, which a stream capture cannot do");
+  const size_t nm = ctx->shape.nm, count = level + K;
+  nflhip_ctx *child = nullptr;
+  int rc = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    std::vector<T> P(count), roots(count), invk(count);
+    for (size_t i = 0; i < count; ++i) {
+      const size_t j = i < level ? i : nm - count + i;  // phys(i)
+      P[i] = (T)ctx->h_P[j];
+      roots[i] = (T)ctx->h_roots[j];
+      invk[i] = (T)ctx->h_invk[j];
+    }
+    return ctx_create_mode(&child, ctx->device, ctx->shape.limb_bits, ctx->shape.n, count, P.data(), roots.data(), invk.data(), ctx->kmax_log2, 0, ctx);
+  });
+  if (rc) return rc;
+  try {
+    ctx->lvl_child[key] = child;
+  } catch (const std::bad_alloc &) {
+    nflhip_ctx_destroy(child);
+    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+  }
+  *out = child;
+  return NFLHIP_OK;
+}
+// acc = [addend +] sum_d a(., d) (.) key[d][c]: nflhip_dot_dev with the key as the shared second operand, a term every two polynomials;
+// kl: the key lies in the parent's layout (ctx is a level context)
+static int dot_key(nflhip_ctx *ctx, void *out, const nflhip_dot_operand *a, const void *key, size_t c, const void *addend, size_t groups,
+                   size_t terms, const KeyLevel *kl, hipStream_t st) {
+  if (!kl) {
+    const nflhip_dot_operand b = {(const char *)key + c * poly_bytes(ctx, 1), 0, 2};
+    return nflhip_dot_dev(ctx, out, a, &b, addend, groups, terms, 0, st);
+  }
+  if (terms == 0 || terms > nflhip::kDotMaxTerms) return fail(ctx, NFLHIP_ERR_INVALID, "dot: the number of terms is out of range (1 to 2^31)");  // (as dot_check)
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  const char *kc = (const char *)key + c * kl->knm * ctx->shape.n * ctx->word;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_dot_key_level<T>(ctx->shape, ctx->tabs, (T *)out, (const T *)a->ptr, a->group_stride, a->term_stride, (const T *)kc,
+                                   (const T *)addend, groups, terms, groups > 1, *kl, st);
+  });
+  return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "dot (level key)");
+}
+
 // Hybrid key switching in NTT form (kernels_keyswitch.hip; include/nflhip.h "hybrid key switching"): the mod-up of every digit, the
 // two inner products against the key and the mod-down of both sums, defined as the composition of nflhip_baseconv_ntt_dev,
 // nflhip_dot_dev and nflhip_moddown_ntt_dev.  Three plans with the same words:
@@ -1124,7 +1183,7 @@ static int keyswitch_default_plan(const nflhip_ctx *ctx, size_t L, size_t dnum, 
   return ctx->shape.n > 2048 ? NFLHIP_KEYSWITCH_COMPOSED : NFLHIP_KEYSWITCH_SEQUENCE;
 }
 static int keyswitch_run(nflhip_ctx *ctx, void *out0, void *out1, const void *in, const void *key, size_t batch, size_t K, size_t alpha, int flags,
-                         hipStream_t st) {
+                         hipStream_t st, const KeyLevel *kl = nullptr) {
   std::lock_guard<std::mutex> lk(ctx->ks_mu);
   const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha, row = ctx->shape.n * ctx->word, pb = nm * row;
   const bool centred = (flags & NFLHIP_KEYSWITCH_CENTERED) != 0, floor = (flags & NFLHIP_KEYSWITCH_FLOOR) != 0, cap = is_capturing(st);
@@ -1170,6 +1229,7 @@ static int keyswitch_run(nflhip_ctx *ctx, void *out0, void *out1, const void *in
   if (plan == NFLHIP_KEYSWITCH_FUSED) {
     e = with_limb(ctx, [&](auto z) {
       typedef decltype(z) T;
+      if (kl) return launch_modup_dot_fused_level<T>(ctx->shape, ctx->tabs, (T *)acc, (const T *)in, (const T *)key, recs, batch, L, alpha, centred, *kl, st);
       return launch_modup_dot_fused<T>(ctx->shape, ctx->tabs, (T *)acc, (const T *)in, (const T *)key, recs, batch, L, alpha, centred, st);
     });
     if (e == hipErrorNotSupported) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "keyswitch: the rows of this call do not fit the one-launch kernel's LDS");
@@ -1192,10 +1252,8 @@ static int keyswitch_run(nflhip_ctx *ctx, void *out0, void *out1, const void *in
       if ((rc = nflhip_ntt_fwd_dev(ctx, U, batch * dnum, st))) return rc;
       a = {U, dnum, 1};
     }
-    for (size_t c = 0; c < 2; ++c) {
-      const nflhip_dot_operand b = {(const char *)key + c * pb, 0, 2};
-      if ((rc = nflhip_dot_dev(ctx, acc + c * batch * pb, &a, &b, nullptr, batch, dnum, 0, st))) return rc;
-    }
+    for (size_t c = 0; c < 2; ++c)
+      if ((rc = dot_key(ctx, acc + c * batch * pb, &a, key, c, nullptr, batch, dnum, kl, st))) return rc;
   }
   const int mdflags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
   if ((char *)out1 == (char *)out0 + batch * L * row) {
@@ -1657,7 +1715,7 @@ static int mulrelin_default_plan(const nflhip_ctx *ctx, size_t L, size_t dnum, b
   return NFLHIP_MULRELIN_MERGED;
 }
 static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0, const void *a1, const void *b0, const void *b1, const void *key,
-                        size_t batch, size_t K, size_t alpha, int flags, hipStream_t st) {
+                        size_t batch, size_t K, size_t alpha, int flags, hipStream_t st, const KeyLevel *kl = nullptr) {
   std::lock_guard<std::mutex> lk(ctx->mr_mu);
   const size_t nm = ctx->shape.nm, n = ctx->shape.n, L = nm - K, dnum = (L + alpha - 1) / alpha, row = n * ctx->word, pb = nm * row, qb = L * row;
   const bool centred = (flags & NFLHIP_MULRELIN_CENTERED) != 0, floor = (flags & NFLHIP_MULRELIN_FLOOR) != 0;
@@ -1724,6 +1782,8 @@ static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0,
   if (fused) {
     hipError_t e = with_limb(ctx, [&](auto z) {
       typedef decltype(z) T;
+      if (kl) return launch_tensor_modup_dot_fused_level<T>(ctx->shape, ctx->tabs, (T *)A, (const T *)a0, (const T *)a1, (const T *)b0, (const T *)b1,
+                                                            (const T *)key, recs, pi, batch, L, alpha, centred, *kl, st);
       return launch_tensor_modup_dot_fused<T>(ctx->shape, ctx->tabs, (T *)A, (const T *)a0, (const T *)a1, (const T *)b0, (const T *)b1, (const T *)key,
                                               recs, pi, batch, L, alpha, centred, st);
     });
@@ -1771,10 +1831,8 @@ static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0,
       u = {U, dnum, 1};
     }
   }
-  for (size_t c = 0; c < 2 && !fused; ++c) {
-    const nflhip_dot_operand b = {(const char *)key + c * pb, 0, 2};
-    if ((rc = nflhip_dot_dev(ctx, A + c * batch * pb, &u, &b, A + c * batch * pb, batch, dnum, 0, st))) return rc;
-  }
+  for (size_t c = 0; c < 2 && !fused; ++c)
+    if ((rc = dot_key(ctx, A + c * batch * pb, &u, key, c, A + c * batch * pb, batch, dnum, kl, st))) return rc;
   const int mdflags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
   if ((char *)out1 == (char *)out0 + batch * kept * row) {
     rc = nflhip_moddown_ntt_dev(ctx, out0, A, 2 * batch, down, mdflags, st);
@@ -1799,6 +1857,40 @@ int nflhip_mulrelin_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const v
   int rc = mulrelin_check(ctx, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, alpha, flags);  // in full, before any device use
   if (rc || batch == 0) return rc;
   return mulrelin_run(ctx, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, alpha, flags, (hipStream_t)stream);
+}
+
+
+// The two at a level (include/nflhip.h "leveled key switching"): by definition the entries above on the level context with the live
+// rows and digits of the key.  level == L forwards.  Below it the digits are those of min(alpha, level): one short digit when alpha
+// exceeds the level.
+size_t nflhip_keyswitch_level_digits(const nflhip_ctx *ctx, size_t k_special, size_t alpha, size_t level) {
+  return keyswitch_level_digits(ctx, k_special, alpha, level);
+}
+int nflhip_keyswitch_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_in, const void *d_key, size_t batch, size_t k_special,
+                                   size_t alpha, size_t level, int flags, void *stream) {
+  int rc = level_check(ctx, k_special, level, "keyswitch");  // in full, before any device use
+  if (!rc) rc = keyswitch_check(ctx, d_out0, d_out1, d_in, d_key, batch, k_special, alpha, flags, level);
+  if (rc || batch == 0) return rc;
+  const size_t nm = ctx->shape.nm, L = nm - k_special;
+  hipStream_t st = (hipStream_t)stream;
+  if (level == L) return keyswitch_run(ctx, d_out0, d_out1, d_in, d_key, batch, k_special, alpha, flags, st);
+  nflhip_ctx *child = nullptr;
+  if ((rc = set_device(ctx)) || (rc = level_child(ctx, k_special, level, is_capturing(st), &child))) return rc;
+  const KeyLevel kl = {nm, level, L - level};
+  return keyswitch_run(child, d_out0, d_out1, d_in, d_key, batch, k_special, std::min(alpha, level), flags, st, &kl);
+}
+int nflhip_mulrelin_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_a0, const void *d_a1, const void *d_b0, const void *d_b1,
+                                  const void *d_key, size_t batch, size_t k_special, size_t alpha, size_t level, int flags, void *stream) {
+  int rc = level_check(ctx, k_special, level, "mulrelin");  // in full, before any device use
+  if (!rc) rc = mulrelin_check(ctx, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, alpha, flags, level);
+  if (rc || batch == 0) return rc;
+  const size_t nm = ctx->shape.nm, L = nm - k_special;
+  hipStream_t st = (hipStream_t)stream;
+  if (level == L) return mulrelin_run(ctx, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, alpha, flags, st);
+  nflhip_ctx *child = nullptr;
+  if ((rc = set_device(ctx)) || (rc = level_child(ctx, k_special, level, is_capturing(st), &child))) return rc;
+  const KeyLevel kl = {nm, level, L - level};
+  return mulrelin_run(child, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, std::min(alpha, level), flags, st, &kl);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

@@ -466,6 +466,33 @@ int nflhip_keyswitch_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void
   return NFLHIP_OK;
 }
 
+// the same at a level: the operands have `level` rows, and of the key the digits that are read are staged (the outputs share one
+// slot, out1 behind out0, so that the mod-down runs as one batch)
+int nflhip_keyswitch_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_in, const void *h_key, size_t batch, size_t k_special,
+                               size_t alpha, size_t level, int flags) {
+  int rc = level_check(ctx, k_special, level, "keyswitch");
+  if (!rc) rc = keyswitch_check(ctx, h_out0, h_out1, h_in, h_key, batch, k_special, alpha, flags, level);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * level * row;
+  const size_t kb = 2 * keyswitch_level_digits(ctx, k_special, alpha, level) * nm * row;
+  Staged s(ctx);
+  if ((rc = s.in(0, h_in, ob)) || (rc = s.in(1, h_key, kb)) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
+  char *o = (char *)ctx->stage[2];
+  if ((rc = nflhip_keyswitch_level_ntt_dev(ctx, o, o + ob, ctx->stage[0], ctx->stage[1], batch, k_special, alpha, level, flags, (void *)ctx->hstream))) return rc;
+  if (!ctx->stage_host[2]) {
+    HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out1, o + ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
+  s.pending = false;
+  if (ctx->stage_host[2]) {
+    std::memcpy(h_out0, o, ob);
+    std::memcpy(h_out1, o + ob, ob);
+  }
+  return NFLHIP_OK;
+}
+
 // hoisted rotations: c1 (and c0 behind it), every key and every output are staged whole (the outputs share one slot, out0s then out1s)
 int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const *h_out1s, const void *h_c0, const void *h_c1,
                               const void *const *h_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
@@ -620,6 +647,41 @@ int nflhip_mulrelin_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void 
   }
   if ((rc = nflhip_mulrelin_ntt_dev(ctx, o, o + ob, i, i + ib, h_b0 ? i + 2 * ib : nullptr, h_b0 ? i + 3 * ib : nullptr, ctx->stage[1], batch, k_special,
                                     alpha, flags, (void *)ctx->hstream)))
+    return rc;
+  if (!ctx->stage_host[2]) {
+    HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));
+    HIPCHK(ctx, hipMemcpyAsync(h_out1, o + ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
+  s.pending = false;
+  if (ctx->stage_host[2]) {
+    std::memcpy(h_out0, o, ob);
+    std::memcpy(h_out1, o + ob, ob);
+  }
+  return NFLHIP_OK;
+}
+
+// the same at a level: the operands have `level` rows, and of the key the digits that are read are staged (the outputs share one
+// slot, out1 behind out0, so that the mod-down runs as one batch)
+int nflhip_mulrelin_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0, const void *h_b1,
+                              const void *h_key, size_t batch, size_t k_special, size_t alpha, size_t level, int flags) {
+  int rc = level_check(ctx, k_special, level, "mulrelin");
+  if (!rc) rc = mulrelin_check(ctx, h_out0, h_out1, h_a0, h_a1, h_b0, h_b1, h_key, batch, k_special, alpha, flags, level);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ib = batch * level * row;
+  const size_t ob = (flags & NFLHIP_MULRELIN_RESCALE) ? ib - batch * row : ib, nin = h_b0 ? 4 : 2;
+  const size_t kb = 2 * keyswitch_level_digits(ctx, k_special, alpha, level) * nm * row;
+  Staged s(ctx);
+  if ((rc = s.in(0, nullptr, nin * ib)) || (rc = s.in(1, h_key, kb)) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
+  char *i = (char *)ctx->stage[0], *o = (char *)ctx->stage[2];
+  const void *const hin[4] = {h_a0, h_a1, h_b0, h_b1};
+  for (size_t k = 0; k < nin; ++k) {
+    if (ctx->stage_host[0]) std::memcpy(i + k * ib, hin[k], ib);
+    else HIPCHK(ctx, hipMemcpyAsync(i + k * ib, hin[k], ib, hipMemcpyHostToDevice, ctx->hstream));
+  }
+  if ((rc = nflhip_mulrelin_level_ntt_dev(ctx, o, o + ob, i, i + ib, h_b0 ? i + 2 * ib : nullptr, h_b0 ? i + 3 * ib : nullptr, ctx->stage[1], batch, k_special,
+                                          alpha, level, flags, (void *)ctx->hstream)))
     return rc;
   if (!ctx->stage_host[2]) {
     HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));

@@ -80,6 +80,10 @@ struct nflhip_ctx {
   // converted rows of a destination range that is not the whole context; calls are ordered on both by ev_bcn.  All under bcn_mu.
   std::mutex bcn_mu;
   std::map<std::array<size_t, 2>, nflhip_ctx *> bcn_child;
+  // leveled key switching / multiplication (api.hip level_child): the context over the rows [0, level) and [nm - k_special, nm) of
+  // this one, keyed by (k_special, level), created on first use, never while capturing, destroyed with this context; its records,
+  // scratch, events and warm maps are its own.  Under bcn_mu.
+  std::map<std::array<size_t, 2>, nflhip_ctx *> lvl_child;
   void *bcn_scratch[2] = {nullptr, nullptr};
   size_t bcn_scratch_bytes[2] = {0, 0};
   hipEvent_t ev_bcn = nullptr;
@@ -290,8 +294,21 @@ inline size_t keyswitch_digits(const nflhip_ctx *ctx, size_t k_special, size_t a
   if (k_special == 0 || k_special >= nm || alpha == 0 || alpha > nm - k_special) return 0;
   return (nm - k_special + alpha - 1) / alpha;
 }
+// the level entries: the level against the context, ahead of the checks of the top-level entries (which then take the level)
+inline size_t keyswitch_level_digits(const nflhip_ctx *ctx, size_t k_special, size_t alpha, size_t level) {
+  if (keyswitch_digits(ctx, k_special, alpha) == 0 || level == 0 || level > ctx->shape.nm - k_special) return 0;
+  return (level + alpha - 1) / alpha;
+}
+inline int level_check(const nflhip_ctx *ctx, size_t k_special, size_t level, const char *what) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": a cyclic row context has no modulus chain");
+  if (k_special == 0 || k_special >= ctx->shape.nm) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": k_special is out of range (1 to nmoduli - 1)");
+  if (level == 0 || level > ctx->shape.nm - k_special) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": the level is out of range (1 to nmoduli - k_special)");
+  return NFLHIP_OK;
+}
+// (level: the operands' rows and the digits of a call below the top level, 1 <= level <= L checked by level_check; 0: the top level)
 inline int keyswitch_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *in, const void *key, size_t batch,
-                           size_t k_special, size_t alpha, int flags) {
+                           size_t k_special, size_t alpha, int flags, size_t level = 0) {
   if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
   if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: a cyclic row context has no modulus chain");
   const int plans = NFLHIP_KEYSWITCH_COMPOSED | NFLHIP_KEYSWITCH_FUSED | NFLHIP_KEYSWITCH_SEQUENCE, plan = flags & plans;
@@ -303,11 +320,11 @@ inline int keyswitch_check(const nflhip_ctx *ctx, const void *out0, const void *
   if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: more than 65535 rows");
   if (batch == 0) return NFLHIP_OK;
   if (!out0 || !out1 || !in || !key) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
-  const size_t row = ctx->shape.n * ctx->word, L = nm - k_special;
+  const size_t row = ctx->shape.n * ctx->word, L = level ? level : nm - k_special, kd = level ? (level + alpha - 1) / alpha : dnum;
   size_t ob, sb, kb, polys;
   // (sb: the largest scratch of any plan -- the embedded input, the digits and the two sums, [batch][1 + dnum + 2][nm][n])
   if (__builtin_mul_overflow(batch, L * row, &ob) || __builtin_mul_overflow(batch, dnum + 3, &polys) || __builtin_mul_overflow(polys, nm * row, &sb) ||
-      __builtin_mul_overflow(2 * dnum, nm * row, &kb))
+      __builtin_mul_overflow(2 * kd, nm * row, &kb))  // (kb: the digits that are read)
     return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: the size overflows");
   const void *const ptr[4] = {out0, out1, in, key};
   const size_t len[4] = {ob, ob, ob, kb};
@@ -475,7 +492,7 @@ inline int tensor_check(const nflhip_ctx *ctx, const void *out0, const void *out
 // nflhip_mulrelin_ntt_dev / nflhip_mulrelin_ntt: every argument check short of the tables (a repeated modulus is found by their
 // builder, api.hip keyswitch_records), before any device use
 inline int mulrelin_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *a0, const void *a1, const void *b0,
-                          const void *b1, const void *key, size_t batch, size_t k_special, size_t alpha, int flags) {
+                          const void *b1, const void *key, size_t batch, size_t k_special, size_t alpha, int flags, size_t level = 0) {
   if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
   if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: a cyclic row context has no modulus chain");
   const int plans = NFLHIP_MULRELIN_SEQUENCE | NFLHIP_MULRELIN_MERGED | NFLHIP_MULRELIN_FUSED, plan = flags & plans;
@@ -486,16 +503,18 @@ inline int mulrelin_check(const nflhip_ctx *ctx, const void *out0, const void *o
   if (k_special == 0 || k_special >= nm) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: k_special is out of range (1 to nmoduli - 1)");
   if (dnum == 0) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: alpha is out of range (1 to nmoduli - k_special)");
   if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: more than 65535 rows");
-  const size_t row = ctx->shape.n * ctx->word, L = nm - k_special;
+  // (level: as keyswitch_check)
+  const size_t row = ctx->shape.n * ctx->word, L = level ? level : nm - k_special, kd = level ? (level + alpha - 1) / alpha : dnum;
   if ((flags & NFLHIP_MULRELIN_RESCALE) && L < 2)
-    return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: the rescale needs two kept moduli at least (nmoduli - k_special >= 2)");
+    return fail(ctx, NFLHIP_ERR_INVALID, level ? "mulrelin: the rescale needs two kept moduli at least (level >= 2)"
+                                               : "mulrelin: the rescale needs two kept moduli at least (nmoduli - k_special >= 2)");
   if (batch == 0) return NFLHIP_OK;
   if (!out0 || !out1 || !a0 || !a1 || !key) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
   if (!b0 != !b1) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: b0 and b1 are both given, or both NULL for the square");
   size_t ib, ob, sb, kb, polys;
   // (sb: the largest scratch of either plan -- [batch][dnum + 12][nm][n] and a polynomial)
   if (__builtin_mul_overflow(batch, L * row, &ib) || __builtin_mul_overflow(batch, dnum + 13, &polys) || __builtin_mul_overflow(polys, nm * row, &sb) ||
-      __builtin_mul_overflow(2 * dnum, nm * row, &kb))
+      __builtin_mul_overflow(2 * kd, nm * row, &kb))  // (kb: the digits that are read)
     return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: the size overflows");
   ob = (flags & NFLHIP_MULRELIN_RESCALE) ? ib - batch * row : ib;
   if (ranges_overlap(out0, ob, out1, ob)) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: the two outputs overlap");

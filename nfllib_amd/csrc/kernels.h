@@ -209,6 +209,21 @@ template <typename T>
 hipError_t launch_tensor_modup_dot_fused(const Shape &s, const DevTables &t, T *acc, const T *a0, const T *a1, const T *b0, const T *b1, const T *key,
                                          const uint64_t *const *recs, const uint64_t *pi, size_t batch, size_t L, size_t alpha, int centred,
                                          hipStream_t st);
+// the key reads of a call below the top level (kernels_level.hip; include/nflhip.h "leveled key switching"): s, t are those of the
+// level context C_l (split + K rows), the key stays in its PARENT's layout [dnum][2][knm][n] -- child row r of a key polynomial is the
+// parent's row r for r < split and r + hole from there on, knm = s.nm + hole.  _dot_key_level: launch_dot with b = key + c knm n as the
+// shared second operand, a term every two parent polynomials (key[d][c]).  The other two: the one-launch kernels above, L = split.
+struct KeyLevel { size_t knm, split, hole; };
+template <typename T>
+hipError_t launch_dot_key_level(const Shape &s, const DevTables &t, T *out, const T *a, size_t a_gs, size_t a_ts, const T *key, const T *addend,
+                                size_t groups, size_t terms, int tiled, const KeyLevel &kl, hipStream_t st);
+template <typename T>
+hipError_t launch_modup_dot_fused_level(const Shape &s, const DevTables &t, T *acc, const T *in, const T *key, const uint64_t *const *recs,
+                                        size_t batch, size_t L, size_t alpha, int centred, const KeyLevel &kl, hipStream_t st);
+template <typename T>
+hipError_t launch_tensor_modup_dot_fused_level(const Shape &s, const DevTables &t, T *acc, const T *a0, const T *a1, const T *b0, const T *b1,
+                                               const T *key, const uint64_t *const *recs, const uint64_t *pi, size_t batch, size_t L, size_t alpha,
+                                               int centred, const KeyLevel &kl, hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);

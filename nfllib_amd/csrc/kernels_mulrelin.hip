@@ -20,6 +20,7 @@
 #include "baseconv_pos.h"
 #include "ntt_lds.h"
 #include "keyswitch_fused.h"  // kFusedPos and the steps the one-launch kernel shares with k_modup_dot_fused
+#include "mulrelin_fused.h"  // MrFusedArgs and k_tensor_modup_dot_fused<T, Args>
 
 namespace nflhip {
 
@@ -111,133 +112,8 @@ hipError_t launch_tensor_ntt(const Shape &s, const DevTables &t, T *out0, T *out
   return hipGetLastError();
 }
 
-// k_tensor_modup_dot_fused<T> -- ONE launch from the four NTT-form inputs to the two sums A_c = E(pi d_c) + sum_d U_d key[d][c], U_d the
-// mod-up of d2 = a1 (.) b1: k_modup_dot_fused (kernels_keyswitch.hip, which see for the LDS layout, the thread ownership and the
-// barrier argument -- all unchanged) with three differences.  The source rows enter LDS as the products a1 b1, formed at the load.  A
-// digit's own rows re-form that product from global memory where the key switch re-reads its input.  And on a kept row r < L the two
-// accumulators of a position start from pi_r d_0 and pi_r d_1, formed from the four input words of the position and reduced to
-// canonical words: the carry-in of nflhip_dot_dev's addend, so that the bound of dot_reduce.h (16 products and a canonical carry-in)
-// holds as it stands and the words are those of the merged plan.  d0, d1, d2 never touch memory.  b0 == b1 == nullptr: the square.
-//
-// Scalar registers.  Ten pointers and seven sizes in the kernel arguments, the row's constants, a digit's record pointers and the
-// loop state are more uniform values than the 100-odd scalar registers hold, and the compiler does not reload a kernel argument: it
-// parks what does not fit in vector lanes.  So the arguments travel as ONE struct, the kernel's only argument, and every POINTER is
-// read from the kernel-argument segment where it is used (MR_ARG: a scalar load from constant memory through a pointer the compiler
-// cannot see through, so the value lives from that load to its last use nearby and not across the loops).  The seven sizes are read
-// once.  No scalar register is spilled (tests/test_mulrelin_cpu.py).
-template <typename T> struct MrFusedArgs {
-  T *accout;
-  const T *a0, *a1, *b0, *b1, *key;
-  const Tw<T> *psi;
-  const ModConst<T> *mc;
-  const uint64_t *const *recs;
-  const uint64_t *pi;
-  size_t batch;
-  unsigned logn, nm, L, alpha, dnum, centred;
-};
-template <typename T> __device__ __forceinline__ const __attribute__((address_space(4))) MrFusedArgs<T> *mr_fused_args() {
-  const __attribute__((address_space(4))) MrFusedArgs<T> *p =
-      (const __attribute__((address_space(4))) MrFusedArgs<T> *)__builtin_amdgcn_kernarg_segment_ptr();  // the struct is argument 0: offset 0
-  asm volatile("" : "+s"(p));
-  return p;
-}
-#define MR_ARG(field) (mr_fused_args<T>()->field)
-
-template <typename T>
-__global__ void __launch_bounds__(1024) k_tensor_modup_dot_fused(const MrFusedArgs<T> args_in_the_kernarg_segment) {
-  typedef typename DotRed<T>::acc_t acc_t;
-  (void)args_in_the_kernarg_segment;
-  const unsigned logn = MR_ARG(logn), nm = MR_ARG(nm), L = MR_ARG(L), alpha = MR_ARG(alpha), dnum = MR_ARG(dnum), centred = MR_ARG(centred);
-  const size_t batch = MR_ARG(batch);
-  extern __shared__ uint4 mr_lds_raw[];
-  const unsigned n = 1u << logn;
-  T *Y = reinterpret_cast<T *>(mr_lds_raw), *B = Y + ((size_t)L << logn);
-  uint16_t *Vr = reinterpret_cast<uint16_t *>(B + n);  // [dnum][n], centred mode only
-  for (size_t b = blockIdx.x; b < batch; b += gridDim.x) {
-    // the polynomial's offsets, too, are formed where they are used, from values the compiler cannot hoist
-    const size_t in = (b * L) << logn;
-    for (unsigned i = 0; i < L; ++i) {
-      T *Yi = Y + ((size_t)i << logn);
-      const ModConst<T> ci = MR_ARG(mc)[i];
-      const DotRed<T> ri(ci);
-      size_t at = in + ((size_t)i << logn);
-      asm volatile("" : "+s"(at));
-      {
-        const T *a1 = MR_ARG(a1), *b1 = MR_ARG(b1);
-        for (unsigned j = threadIdx.x; j < n; j += blockDim.x) Yi[j] = ri.reduce((acc_t)a1[at + j] * (acc_t)b1[at + j]);
-      }
-      resc_inv_lds<T>(Yi, MR_ARG(psi) + ((size_t)i << logn), logn, ci);
-    }
-    __syncthreads();
-    for (unsigned d = 0; d < dnum; ++d) {
-      const unsigned s0 = d * alpha, ks = L - s0 < alpha ? L - s0 : alpha;
-      ks_fused_y_pass<T>(Y, Vr, MR_ARG(recs)[d], d, s0, ks, logn, n, centred);
-    }
-    for (unsigned r = 0; r < nm; ++r) {
-      const ModConst<T> cr = MR_ARG(mc)[r];
-      const DotRed<T> red(cr);
-      const T p = (T)cr.p;
-      acc_t s0a[kFusedPos], s1a[kFusedPos];
-#pragma unroll
-      for (int k = 0; k < kFusedPos; ++k) s0a[k] = s1a[k] = 0;
-      size_t at = in + ((size_t)r << logn);  // (read on the kept rows r < L only)
-      asm volatile("" : "+s"(at));
-      if (r < L) {  // the addend pi_r d_c as the canonical carry-in
-        const T w = (T)MR_ARG(pi)[2 * r], wp = (T)MR_ARG(pi)[2 * r + 1];
-        const T *a0 = MR_ARG(a0), *a1 = MR_ARG(a1), *b0 = MR_ARG(b0), *b1 = MR_ARG(b1);
-#pragma unroll
-        for (int k = 0; k < kFusedPos; ++k) {
-          const unsigned j = threadIdx.x + (unsigned)k * blockDim.x;
-          if (j < n) {
-            const T u0 = a0[at + j], u1 = a1[at + j], v0 = b0[at + j], v1 = b1[at + j];
-            s0a[k] = (acc_t)mul_shoup<T>(red.reduce((acc_t)u0 * (acc_t)v0), w, wp, p);
-            s1a[k] = (acc_t)mul_shoup<T>(red.reduce((acc_t)u0 * (acc_t)v1 + (acc_t)u1 * (acc_t)v0), w, wp, p);
-          }
-          asm volatile("" ::: "memory");  // one position at a time: four positions' loads and double-width products at once do not fit 128 registers
-        }
-      }
-      for (unsigned d = 0; d < dnum; ++d) {
-        const unsigned s0 = d * alpha, ks = L - s0 < alpha ? L - s0 : alpha;
-        const T *k0 = MR_ARG(key) + (((size_t)(2 * d) * nm + r) << logn), *k1 = k0 + ((size_t)nm << logn);
-        const bool own = r - s0 < ks;  // (unsigned: s0 <= r < s0 + ks) a row of the digit: the NTT-form product itself
-        if (!own) {
-          ks_fused_conv_row<T>(B, Y, Vr, MR_ARG(recs)[d], red, MR_ARG(psi) + ((size_t)r << logn), d, s0, ks, r, nm, logn, n, centred, p);
-        }
-        const T *a1 = MR_ARG(a1), *b1 = MR_ARG(b1);
-#pragma unroll
-        for (int k = 0; k < kFusedPos; ++k) {
-          const unsigned j = threadIdx.x + (unsigned)k * blockDim.x;
-          if (j < n) {
-            const T u = own ? red.reduce((acc_t)a1[at + j] * (acc_t)b1[at + j]) : reduce4<T>(B[j], p);
-            s0a[k] += (acc_t)u * (acc_t)k0[j];
-            s1a[k] += (acc_t)u * (acc_t)k1[j];
-          }
-        }
-        if ((d + 1) % kDotChunk == 0 && d + 1 < dnum) {  // a full chunk behind, more to come: back to a canonical carry-in
-#pragma unroll
-          for (int k = 0; k < kFusedPos; ++k) {
-            s0a[k] = (acc_t)red.reduce(s0a[k]);
-            s1a[k] = (acc_t)red.reduce(s1a[k]);
-          }
-        }
-        // (B[j] is rewritten next by the thread that just read it; the transform's first barrier orders the rest)
-      }
-      size_t o = (b * nm + r) << logn, ostep = (batch * nm) << logn;
-      asm volatile("" : "+s"(o), "+s"(ostep));
-      T *accout = MR_ARG(accout);
-#pragma unroll
-      for (int k = 0; k < kFusedPos; ++k) {
-        const unsigned j = threadIdx.x + (unsigned)k * blockDim.x;
-        if (j < n) {
-          accout[o + j] = red.reduce(s0a[k]);
-          accout[o + ostep + j] = red.reduce(s1a[k]);
-        }
-      }
-    }
-    __syncthreads();  // the next polynomial's loads overwrite Y
-  }
-}
-
+// k_tensor_modup_dot_fused<T, Args>, its arguments and the account of its scalar registers are in mulrelin_fused.h; here its instances
+// on the context's own key layout (Args = MrFusedArgs<T>)
 template <typename T>
 hipError_t launch_tensor_modup_dot_fused(const Shape &s, const DevTables &t, T *acc, const T *a0, const T *a1, const T *b0, const T *b1, const T *key,
                                          const uint64_t *const *recs, const uint64_t *pi, size_t batch, size_t L, size_t alpha, int centred,
@@ -252,7 +128,7 @@ hipError_t launch_tensor_modup_dot_fused(const Shape &s, const DevTables &t, T *
   const size_t cap = (size_t)1 << 20;
   const MrFusedArgs<T> args = {acc, a0, a1, b0 ? b0 : a0, b1 ? b1 : a1, key, (const Tw<T> *)t.psi, (const ModConst<T> *)t.mc, recs, pi, batch,
                                (unsigned)s.logn, (unsigned)s.nm, (unsigned)L, (unsigned)alpha, (unsigned)dnum, centred ? 1u : 0u};
-  hipLaunchKernelGGL((k_tensor_modup_dot_fused<T>), dim3((unsigned)(batch < cap ? batch : cap)), dim3(threads), lds < 16 ? 16 : lds, st, args);
+  hipLaunchKernelGGL((k_tensor_modup_dot_fused<T, MrFusedArgs<T>>), dim3((unsigned)(batch < cap ? batch : cap)), dim3(threads), lds < 16 ? 16 : lds, st, args);
   return hipGetLastError();
 }
 
@@ -266,7 +142,6 @@ NFLHIP_MULRELIN_INSTANCES(uint16_t)
 NFLHIP_MULRELIN_INSTANCES(uint32_t)
 NFLHIP_MULRELIN_INSTANCES(uint64_t)
 #undef NFLHIP_MULRELIN_INSTANCES
-#undef MR_ARG
 
 __global__ void k_warm_mulrelin() {}
 hipError_t warm_mulrelin(hipStream_t st) {

@@ -43,14 +43,20 @@ class Engine:
     """One (T, Degree, NbModuli) context on one GPU -- the device-side
     counterpart of poly<T,Degree,NbModuli>::base / ::gmp (poly.hpp:247, 275)."""
 
-    def __init__(self, limb_bits, degree, nmoduli, device=0):
+    def __init__(self, limb_bits, degree, nmoduli, device=0, rows=None):
+        """the context over the first nmoduli moduli of the limb width; rows = a list of nmoduli distinct modulus indices: over
+        those moduli instead, in that order (level_engine)"""
         self.lib = _lib.lib
         self.limb_bits, self.degree, self.nmoduli, self.device = limb_bits, degree, nmoduli, device
         self.np_dtype = np.dtype(_NP[limb_bits])
         pr = self.params = limb_params(limb_bits)
+        rows = list(range(nmoduli)) if rows is None else [int(r) for r in rows]
         if nmoduli > pr.max_moduli:
             raise ValueError("only %d moduli are mirrored for %d-bit limbs" % (pr.max_moduli, limb_bits))
-        self._keep = [np.ascontiguousarray(x[:nmoduli]) for x in (pr.P, pr.primitive_roots, pr.invkmax)]
+        if len(rows) != nmoduli or len(set(rows)) != nmoduli or not all(0 <= r < pr.max_moduli for r in rows):
+            raise ValueError("rows are nmoduli = %d distinct modulus indices below %d" % (nmoduli, pr.max_moduli))
+        self.rows = rows
+        self._keep = [np.ascontiguousarray(x[rows]) for x in (pr.P, pr.primitive_roots, pr.invkmax)]
         h = C.c_void_p()
         rc = self.lib.nflhip_ctx_create(C.byref(h), device, limb_bits, degree, nmoduli,
                                         *[_vp(x) for x in self._keep], pr.kmax_log2)
@@ -388,23 +394,54 @@ class Engine:
     # ---- hybrid key switching, NTT form (include/nflhip.h "hybrid key switching") ----
     _KS_PLAN = {None: 0, "sequence": KEYSWITCH_SEQUENCE, "composed": KEYSWITCH_COMPOSED, "fused": KEYSWITCH_FUSED}
 
-    def keyswitch_digits(self, k_special, alpha):
-        """dnum = ceil((nm - k_special) / alpha), the number of digits (and of key terms) of a key switch"""
+    def keyswitch_digits(self, k_special, alpha, level=None):
+        """dnum = ceil((nm - k_special) / alpha), the number of digits (and of key terms) of a key switch; with a level,
+        ceil(level / alpha): the digits a call at that level reads"""
+        if level is not None:
+            dnum = self.lib.nflhip_keyswitch_level_digits(self.ctx, k_special, alpha, level)
+            if dnum == 0:
+                raise ValueError("k_special %r (1 to nm - 1), alpha %r (1 to nm - k_special) or level %r (1 to nm - k_special) is out of range"
+                                 % (k_special, alpha, level))
+            return dnum
         dnum = self.lib.nflhip_keyswitch_digits(self.ctx, k_special, alpha)
         if dnum == 0:
             raise ValueError("k_special %r (1 to nm - 1) or alpha %r (1 to nm - k_special) is out of range" % (k_special, alpha))
         return dnum
 
+    def level_rows(self, level, k_special):
+        """A_l: the rows of this context that are alive at a level, [0, level) and the k_special special rows"""
+        L = self.nmoduli - k_special
+        if k_special < 1 or L < 1 or not 1 <= level <= L:
+            raise ValueError("k_special is 1 to nm - 1, level 1 to nm - k_special")
+        return list(range(level)) + list(range(L, self.nmoduli))
+
+    def level_engine(self, level, k_special):
+        """an Engine over C_l, the moduli of level_rows(level, k_special) in that order, on the same device: a call with level=l on
+        this engine returns the words of the same call on that engine with key[:dnum_l, :, level_rows] -- the definition of a level
+        call, and how test vectors for one are prepared"""
+        rows = [self.rows[r] for r in self.level_rows(level, k_special)]
+        return Engine(self.limb_bits, self.degree, len(rows), device=self.device, rows=rows)
+
+    def _level_key(self, size, k_special, alpha, level):
+        """a key for a call at a level: the whole [dnum_L, 2, nm, n], or as many leading digits as the level reads, at least"""
+        lo, hi = self.keyswitch_digits(k_special, alpha, level), self.keyswitch_digits(k_special, alpha)
+        if size % (2 * self.words_per_poly) or not lo <= size // (2 * self.words_per_poly) <= hi:
+            raise ValueError("key holds dnum * 2 polynomials of this context (the digits of the level, at least)")
+
     def _ks_flags(self, centered, floor, plan):
         return (KEYSWITCH_CENTERED if centered else 0) | (KEYSWITCH_FLOOR if floor else 0) | self._KS_PLAN[plan]
 
-    def key_switch_ntt(self, a, key, k_special, alpha, centered=False, floor=False, out=None, plan=None, stream=None):
+    def key_switch_ntt(self, a, key, k_special, alpha, centered=False, floor=False, out=None, plan=None, stream=None, level=None):
         """the hybrid key switch of the NTT-form batch a = [batch, L, n], L = nm - k_special (the layout of Engine(limb_bits, degree, L)),
         against key = [dnum, 2, nm, n] (NTT form over this context, shared by the batch): mod-up of every digit of alpha rows (fast,
         or centered=True), the two sums of products, mod-down by the last k_special moduli (rounding, or floor=True).  Returns
         (out0, out1), each [batch, L, n]; `out` = a pair of such tensors, else both are views of one new [2, batch, L, n] tensor.
         plan "sequence" / "composed" / "fused" forces a plan.  The first call for a (k_special, alpha), or a larger batch,
-        allocates: make it before a graph capture."""
+        allocates: make it before a graph capture.
+        level=l (1 to L): a and the results are [batch, l, n], a ciphertext below the top level, and the key is still the ONE
+        top-level key, of which only the live rows [0, l), [L, nm) and the first ceil(l / alpha) digits are read."""
+        if level is not None:
+            return self._key_switch_level(a, key, k_special, alpha, level, self._ks_flags(centered, floor, plan), out, stream)
         L = self.nmoduli - k_special
         if L <= 0 or a.numel() % (L * self.degree) or not a.is_contiguous() or not key.is_contiguous():
             raise ValueError("a is a contiguous [batch, nm - k_special, n] tensor")
@@ -418,9 +455,32 @@ class Engine:
                                                     self._ks_flags(centered, floor, plan), self._stream(stream)))
         return out
 
-    def h_key_switch_ntt(self, a, key, k_special, alpha, centered=False, floor=False, plan=None):
-        """host-pointer variant: numpy a = [batch, L, n] and key = [dnum, 2, nm, n] -> (out0, out1)"""
+    def _key_switch_level(self, a, key, k_special, alpha, level, flags, out, stream):
+        self.level_rows(level, k_special)
+        if a.numel() % (level * self.degree) or not a.is_contiguous() or not key.is_contiguous():
+            raise ValueError("a is a contiguous [batch, level, n] tensor")
+        batch = a.numel() // (level * self.degree)
+        self._level_key(key.numel(), k_special, alpha, level)
+        if out is None:
+            both = _torch().empty((2, batch, level, self.degree), dtype=self.torch_dtype, device=a.device)
+            out = (both[0], both[1])
+        self._chk(self.lib.nflhip_keyswitch_level_ntt_dev(self.ctx, _vp(out[0]), _vp(out[1]), _vp(a), _vp(key), batch, k_special, alpha, level,
+                                                          flags, self._stream(stream)))
+        return out
+
+    def h_key_switch_ntt(self, a, key, k_special, alpha, centered=False, floor=False, plan=None, level=None):
+        """host-pointer variant: numpy a = [batch, L, n] and key = [dnum, 2, nm, n] -> (out0, out1); level as key_switch_ntt"""
         a, key = np.ascontiguousarray(a, dtype=self.np_dtype), np.ascontiguousarray(key, dtype=self.np_dtype)
+        if level is not None:
+            self.level_rows(level, k_special)
+            if a.size % (level * self.degree):
+                raise ValueError("a is [batch, level, n]")
+            self._level_key(key.size, k_special, alpha, level)
+            batch = a.size // (level * self.degree)
+            out0, out1 = (np.empty((batch, level, self.degree), dtype=self.np_dtype) for _ in range(2))
+            self._chk(self.lib.nflhip_keyswitch_level_ntt(self.ctx, _vp(out0), _vp(out1), _vp(a), _vp(key), batch, k_special, alpha, level,
+                                                          self._ks_flags(centered, floor, plan)))
+            return out0, out1
         L = self.nmoduli - k_special
         if L <= 0 or a.size % (L * self.degree) or key.size != 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly:
             raise ValueError("a is [batch, nm - k_special, n], key [dnum, 2, nm, n]")
@@ -625,33 +685,62 @@ class Engine:
         self._chk(self.lib.nflhip_tensor_ntt(self.ctx, _vp(outs[0]), _vp(outs[1]), _vp(outs[2]), _vp(a0), _vp(a1), _vp(b0), _vp(b1), batch, rows, 0))
         return outs
 
-    def mul_relin_ntt(self, a0, a1, b0, b1, key, k_special, alpha, rescale=False, centered=False, floor=False, out=None, plan=None, stream=None):
+    def mul_relin_ntt(self, a0, a1, b0, b1, key, k_special, alpha, rescale=False, centered=False, floor=False, out=None, plan=None, stream=None,
+                      level=None):
         """the product of the ciphertexts (a0, a1) and (b0, b1) with relinearisation, one call: NTT-form [batch, L, n] batches with
         L = nm - k_special (b0 = b1 = None: the square), key = [dnum, 2, nm, n] as key_switch_ntt takes it, from s^2 to s.  The tensor
         product's first two components go into the key-switch sums of the third before the ONE mod-down.  rescale=True divides by
         the last kept modulus in the same rounding: the results are [batch, L - 1, n].  Returns (out0, out1); `out` = a pair of
         such tensors (each may be one of the inputs), else both are views of one new [2, batch, L or L - 1, n] tensor.  plan
         "sequence" / "merged" / "fused" forces a plan.  The first call for a (k_special, alpha), or a larger batch, allocates: make it before
-        a graph capture."""
+        a graph capture.
+        level=l (1 to L; 2 at least with rescale): the operands are [batch, l, n], the results [batch, l or l - 1, n], and the key is
+        still the ONE top-level key, read as key_switch_ntt reads it at a level -- so the result of a rescaling product can be
+        multiplied again."""
         L = self.nmoduli - k_special
         if L <= 0:
             raise ValueError("k_special is 1 to nm - 1")
+        if level is not None:
+            self.level_rows(level, k_special)
+            if rescale and level < 2:
+                raise ValueError("the rescale needs level >= 2")
+            L = level
         _, batch = self._tensor_rows(a0, a1, b0, b1, L, lambda x: x.numel(), lambda x: x.is_contiguous())
-        if key.numel() != 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly or not key.is_contiguous():
+        if not key.is_contiguous():
+            raise ValueError("key holds dnum * 2 polynomials of this context")
+        if level is not None:
+            self._level_key(key.numel(), k_special, alpha, level)
+        elif key.numel() != 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly:
             raise ValueError("key holds dnum * 2 polynomials of this context")
         if out is None:
             both = _torch().empty((2, batch, L - 1 if rescale else L, self.degree), dtype=self.torch_dtype, device=a0.device)
             out = (both[0], both[1])
         elif len(out) != 2 or any(o.numel() != batch * (L - 1 if rescale else L) * self.degree or not o.is_contiguous() for o in out):
             raise ValueError("out is a pair of contiguous [batch, L, n] tensors ([batch, L - 1, n] with rescale)")
+        if level is not None:
+            self._chk(self.lib.nflhip_mulrelin_level_ntt_dev(self.ctx, _vp(out[0]), _vp(out[1]), _vp(a0), _vp(a1), _vp(b0), _vp(b1), _vp(key), batch,
+                                                             k_special, alpha, level, self._mr_flags(rescale, centered, floor, plan),
+                                                             self._stream(stream)))
+            return out
         self._chk(self.lib.nflhip_mulrelin_ntt_dev(self.ctx, _vp(out[0]), _vp(out[1]), _vp(a0), _vp(a1), _vp(b0), _vp(b1), _vp(key), batch, k_special,
                                                    alpha, self._mr_flags(rescale, centered, floor, plan), self._stream(stream)))
         return out
 
-    def h_mul_relin_ntt(self, a0, a1, b0, b1, key, k_special, alpha, rescale=False, centered=False, floor=False, plan=None):
-        """host-pointer variant: numpy a0, a1, b0, b1 = [batch, L, n] (b0 = b1 = None: the square), key = [dnum, 2, nm, n] -> (out0, out1)"""
+    def h_mul_relin_ntt(self, a0, a1, b0, b1, key, k_special, alpha, rescale=False, centered=False, floor=False, plan=None, level=None):
+        """host-pointer variant: numpy a0, a1, b0, b1 = [batch, L, n] (b0 = b1 = None: the square), key = [dnum, 2, nm, n] -> (out0, out1);
+        level as mul_relin_ntt"""
         a0, a1, b0, b1 = (None if x is None else np.ascontiguousarray(x, dtype=self.np_dtype) for x in (a0, a1, b0, b1))
         key = np.ascontiguousarray(key, dtype=self.np_dtype)
+        if level is not None:
+            self.level_rows(level, k_special)
+            if rescale and level < 2:
+                raise ValueError("the rescale needs level >= 2")
+            self._level_key(key.size, k_special, alpha, level)
+            _, batch = self._tensor_rows(a0, a1, b0, b1, level, lambda x: x.size, lambda x: True)
+            out0, out1 = (np.empty((batch, level - 1 if rescale else level, self.degree), dtype=self.np_dtype) for _ in range(2))
+            self._chk(self.lib.nflhip_mulrelin_level_ntt(self.ctx, _vp(out0), _vp(out1), _vp(a0), _vp(a1), _vp(b0), _vp(b1), _vp(key), batch, k_special,
+                                                         alpha, level, self._mr_flags(rescale, centered, floor, plan)))
+            return out0, out1
         L = self.nmoduli - k_special
         if L <= 0 or key.size != 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly:
             raise ValueError("k_special is 1 to nm - 1, key [dnum, 2, nm, n]")
