@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <array>
 #include <cstdio>
 #include <cstring>
@@ -150,6 +151,53 @@ static bool is_capturing(hipStream_t st) {
     return false;
   }
   return cs == hipStreamCaptureStatusActive;
+}
+
+// A context's workspaces (ctx.h Workspace), each under its owner's mutex.  ws_grow: the buffer holds `need` bytes afterwards, or the
+// call is refused while capturing -- `what`: the caller and its article, "keyswitch: the".  ws_begin: that, and the stream waits for
+// the call that used the workspace last; ws_end: the next call waits for this one.  A capturing call neither waits nor records.
+static int ws_grow(nflhip_ctx *ctx, Workspace &w, size_t need, bool cap, const char *what) {
+  if (w.bytes >= need) return NFLHIP_OK;
+  if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, std::string(what) + " scratch has to grow, which a stream capture cannot do");
+  if (w.buf) HIPCHK(ctx, hipFree(w.buf));  // (synchronises: nothing still reads it)
+  w.buf = nullptr;
+  w.bytes = 0;
+  HIPCHK(ctx, hipMalloc(&w.buf, need));
+  w.bytes = need;
+  return NFLHIP_OK;
+}
+static int ws_begin(nflhip_ctx *ctx, Workspace &w, size_t need, bool cap, hipStream_t st, const char *what) {
+  int rc = ws_grow(ctx, w, need, cap, what);
+  if (rc) return rc;
+  if (!w.ev) HIPCHK(ctx, hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+  if (!cap && w.ev_valid) HIPCHK(ctx, hipStreamWaitEvent(st, w.ev, 0));  // a previous call on another stream
+  return NFLHIP_OK;
+}
+static int ws_end(nflhip_ctx *ctx, Workspace &w, bool cap, hipStream_t st) {
+  if (cap) return NFLHIP_OK;
+  HIPCHK(ctx, hipEventRecord(w.ev, st));
+  w.ev_valid = true;
+  return NFLHIP_OK;
+}
+static void ws_free(Workspace &w) {
+  if (w.ev) (void)hipEventDestroy(w.ev);
+  if (w.buf) (void)hipFree(w.buf);
+  w = Workspace();
+}
+
+// The warm maps (ctx.h WarmMap), each under its owner's mutex: a call while capturing may repeat what warm_covers finds -- an entry
+// for its key with every size at least the call's -- and a call outside a capture raises the entry to its sizes afterwards (an
+// entry that cannot be stored only costs a later capture its refusal).
+static bool warm_covers(const WarmMap &m, const std::array<size_t, 3> &key, const std::array<size_t, 3> &sizes) {
+  const auto it = m.find(key);
+  return it != m.end() && it->second[0] >= sizes[0] && it->second[1] >= sizes[1] && it->second[2] >= sizes[2];
+}
+static void warm_note(WarmMap &m, const std::array<size_t, 3> &key, const std::array<size_t, 3> &sizes) {
+  try {
+    std::array<size_t, 3> &w = m[key];  // (a new entry is zeros)
+    for (int i = 0; i < 3; ++i) w[i] = std::max(w[i], sizes[i]);
+  } catch (const std::bad_alloc &) {
+  }
 }
 
 // composed path: NTT(a)->c, NTT(b)->scratch, inverse with the product fused into its load
@@ -486,29 +534,20 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   nflhip_ctx_destroy(ctx->resc_last);
   nflhip_ctx_destroy(ctx->resc_kept);
   ctx->resc_last = ctx->resc_kept = nullptr;
-  (void)hipSetDevice(ctx->device);
-  if (ctx->ev_resc) (void)hipEventDestroy(ctx->ev_resc);
-  if (ctx->resc_scratch) (void)hipFree(ctx->resc_scratch);
   for (auto &kv : ctx->bcn_child) nflhip_ctx_destroy(kv.second);
   ctx->bcn_child.clear();
   for (auto &kv : ctx->lvl_child) nflhip_ctx_destroy(kv.second);
   ctx->lvl_child.clear();
   (void)hipSetDevice(ctx->device);
-  if (ctx->ev_bcn) (void)hipEventDestroy(ctx->ev_bcn);
-  for (int k = 0; k < 2; ++k)
-    if (ctx->bcn_scratch[k]) (void)hipFree(ctx->bcn_scratch[k]);
+  // (the buffers go in the order they always went: where a LATER context's scratch lands follows the order of these frees, and a
+  // table measured with another order moved by up to 2 % at its largest scratch -- profiles/r19_keyswitch_host.txt)
+  for (Workspace *w : {&ctx->resc_ws, &ctx->bcn_ws[0], &ctx->bcn_ws[1]}) ws_free(*w);
   for (auto &kv : ctx->bconv) (void)hipFree(kv.second);
   ctx->bconv.clear();
-  if (ctx->ev_ks) (void)hipEventDestroy(ctx->ev_ks);
-  if (ctx->ev_rot) (void)hipEventDestroy(ctx->ev_rot);
-  if (ctx->ev_lt) (void)hipEventDestroy(ctx->ev_lt);
-  if (ctx->rot_scratch) (void)hipFree(ctx->rot_scratch);
-  if (ctx->lt_scratch) (void)hipFree(ctx->lt_scratch);
-  if (ctx->ev_mr) (void)hipEventDestroy(ctx->ev_mr);
-  if (ctx->mr_scratch) (void)hipFree(ctx->mr_scratch);
+  for (Workspace *w : {&ctx->rot_ws, &ctx->lt_ws, &ctx->mr_ws}) ws_free(*w);
   for (auto &kv : ctx->mr_pi) (void)hipFree(kv.second);
   ctx->mr_pi.clear();
-  if (ctx->ks_scratch) (void)hipFree(ctx->ks_scratch);
+  ws_free(ctx->ks_ws);
   for (auto &kv : ctx->ks_recs) (void)hipFree(kv.second);
   ctx->ks_recs.clear();
   if (ctx->hstream) (void)hipStreamDestroy(ctx->hstream);
@@ -526,6 +565,53 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   delete ctx;
   return NFLHIP_OK;
 }
+
+// A child context over `count` rows of this one -- row i of the child is row phys(i) here, in order -- with the tables mode
+// `cyclic`; never while capturing (`refusal`: the caller's message).  The child takes this context's configuration; a cyclic row
+// child reads the environment itself.  bcn_child, level_child, rescale_children and row_child keep what this creates.
+extern "C++" {
+template <typename Phys>
+static int child_create(nflhip_ctx *ctx, size_t count, Phys phys, int cyclic, bool cap, const char *refusal, nflhip_ctx **out) {
+  if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, refusal);
+  try {
+    return with_limb(ctx, [&](auto z) {  // the parameter tables in the limb type's own width
+      typedef decltype(z) T;
+      std::vector<T> P(count), roots(count), invk(count);
+      for (size_t i = 0; i < count; ++i) {
+        const size_t j = phys(i);
+        P[i] = (T)ctx->h_P[j];
+        roots[i] = (T)ctx->h_roots[j];
+        invk[i] = (T)ctx->h_invk[j];
+      }
+      return ctx_create_mode(out, ctx->device, ctx->shape.limb_bits, ctx->shape.n, count, P.data(), roots.data(), invk.data(), ctx->kmax_log2,
+                             cyclic, cyclic ? nullptr : ctx);
+    });
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+  }
+}
+// ... kept in a map under `key`: looked up, or created and entered
+template <typename Phys>
+static int child_in_map(nflhip_ctx *ctx, ChildMap &m, const std::array<size_t, 2> &key, size_t count, Phys phys, bool cap, const char *refusal,
+                        nflhip_ctx **out) {
+  const auto it = m.find(key);
+  if (it != m.end()) {
+    *out = it->second;
+    return NFLHIP_OK;
+  }
+  nflhip_ctx *child = nullptr;
+  int rc = child_create(ctx, count, phys, 0, cap, refusal, &child);
+  if (rc) return rc;
+  try {
+    m[key] = child;
+  } catch (const std::bad_alloc &) {
+    nflhip_ctx_destroy(child);
+    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+  }
+  *out = child;
+  return NFLHIP_OK;
+}
+}  // extern "C++"
 
 int nflhip_ctx_device(const nflhip_ctx *ctx) { return ctx ? ctx->device : -1; }
 size_t nflhip_degree(const nflhip_ctx *ctx) { return ctx ? ctx->shape.n : 0; }
@@ -672,56 +758,32 @@ int nflhip_automorphism_multi_dev(nflhip_ctx *ctx, void *const *d_outs, const ui
 // and through the inverse transform of a one-modulus child context (the last modulus); d_i = (h - r) mod p_i is expanded into the
 // output, which the child context over the first nm - 1 moduli forward-transforms in place; one pass combines it with the kept
 // input rows.  Every transform launcher of the project therefore serves it, the compiled ones under NFLHIP_VARIANT=hipcc.
-static int rescale_children(nflhip_ctx *ctx) {  // under resc_mu
-  if (ctx->resc_last && ctx->resc_kept) return NFLHIP_OK;
+static int rescale_children(nflhip_ctx *ctx, bool cap) {  // under resc_mu
   const size_t nm = ctx->shape.nm;
-  return with_limb(ctx, [&](auto z) {
-    typedef decltype(z) T;
-    std::vector<T> P(nm), roots(nm), invk(nm);
-    for (size_t cm = 0; cm < nm; ++cm) {
-      P[cm] = (T)ctx->h_P[cm];
-      roots[cm] = (T)ctx->h_roots[cm];
-      invk[cm] = (T)ctx->h_invk[cm];
-    }
-    int rc = NFLHIP_OK;
-    if (!ctx->resc_last)
-      rc = ctx_create_mode(&ctx->resc_last, ctx->device, ctx->shape.limb_bits, ctx->shape.n, 1, &P[nm - 1], &roots[nm - 1], &invk[nm - 1],
-                           ctx->kmax_log2, 0, ctx);
-    if (!rc && !ctx->resc_kept)
-      rc = ctx_create_mode(&ctx->resc_kept, ctx->device, ctx->shape.limb_bits, ctx->shape.n, nm - 1, P.data(), roots.data(), invk.data(),
-                           ctx->kmax_log2, 0, ctx);
-    return rc;
-  });
+  const char *refusal = "rescale: the composed plan's child contexts have to be created, which a stream capture cannot do";
+  int rc = NFLHIP_OK;
+  if (!ctx->resc_last) rc = child_create(ctx, 1, [nm](size_t) { return nm - 1; }, 0, cap, refusal, &ctx->resc_last);
+  if (!rc && !ctx->resc_kept) rc = child_create(ctx, nm - 1, [](size_t i) { return i; }, 0, cap, refusal, &ctx->resc_kept);
+  return rc;
 }
 static int rescale_composed(nflhip_ctx *ctx, void *out, const void *in, size_t batch, hipStream_t st) {
   std::lock_guard<std::mutex> lk(ctx->resc_mu);
-  int rc = rescale_children(ctx);
+  const size_t row = ctx->shape.n * ctx->word, nm = ctx->shape.nm;
+  const bool cap = is_capturing(st);
+  int rc = rescale_children(ctx, cap);
   if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t row = ctx->shape.n * ctx->word, nm = ctx->shape.nm, need = batch * row;
-  const bool cap = is_capturing(st);
-  if (ctx->resc_scratch_bytes < need) {
-    if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "rescale: the composed plan's scratch has to grow, which a stream capture cannot do");
-    if (ctx->resc_scratch) HIPCHK(ctx, hipFree(ctx->resc_scratch));  // (synchronises: nothing still reads it)
-    ctx->resc_scratch = nullptr;
-    ctx->resc_scratch_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->resc_scratch, need));
-    ctx->resc_scratch_bytes = need;
-  }
-  if (!ctx->ev_resc) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_resc, hipEventDisableTiming));
-  if (!cap && ctx->ev_resc_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_resc, 0));  // a previous call on another stream
-  HIPCHK(ctx, hipMemcpy2DAsync(ctx->resc_scratch, row, (const char *)in + (nm - 1) * row, nm * row, row, batch, hipMemcpyDeviceToDevice, st));
-  rc = nflhip_ntt_inv_dev(ctx->resc_last, ctx->resc_scratch, batch, st);
+  Workspace &ws = ctx->resc_ws;
+  if ((rc = ws_begin(ctx, ws, batch * row, cap, st, "rescale: the composed plan's"))) return rc;
+  HIPCHK(ctx, hipMemcpy2DAsync(ws.buf, row, (const char *)in + (nm - 1) * row, nm * row, row, batch, hipMemcpyDeviceToDevice, st));
+  rc = nflhip_ntt_inv_dev(ctx->resc_last, ws.buf, batch, st);
   if (rc) return rc;
   hipError_t e = with_limb(ctx, [&](auto z) {
     typedef decltype(z) T;
-    return launch_rescale_expand<T>(ctx->shape, ctx->tabs, (T *)out, (const T *)ctx->resc_scratch, batch, st);
+    return launch_rescale_expand<T>(ctx->shape, ctx->tabs, (T *)out, (const T *)ws.buf, batch, st);
   });
   if (e != hipSuccess) return hipfail(ctx, e, "rescale: expand");
-  if (!cap) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_resc, st));
-    ctx->ev_resc_valid = true;
-  }
+  if ((rc = ws_end(ctx, ws, cap, st))) return rc;  // (here: the expand was the workspace's last reader)
   rc = nflhip_ntt_fwd_dev(ctx->resc_kept, out, batch, st);
   if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -952,43 +1014,14 @@ static int bcn_child(nflhip_ctx *ctx, size_t first, size_t count, bool cap, nflh
     *out = ctx;
     return NFLHIP_OK;
   }
-  const std::array<size_t, 2> key = {first, count};
-  auto it = ctx->bcn_child.find(key);
-  if (it != ctx->bcn_child.end()) {
-    *out = it->second;
-    return NFLHIP_OK;
-  }
-  if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "baseconv_ntt: the composed plan's child context has to be created, which a stream capture cannot do");
-  nflhip_ctx *child = nullptr;
-  int rc = with_limb(ctx, [&](auto z) {
-    typedef decltype(z) T;
-    std::vector<T> P(count), roots(count), invk(count);
-    for (size_t i = 0; i < count; ++i) {
-      P[i] = (T)ctx->h_P[first + i];
-      roots[i] = (T)ctx->h_roots[first + i];
-      invk[i] = (T)ctx->h_invk[first + i];
-    }
-    return ctx_create_mode(&child, ctx->device, ctx->shape.limb_bits, ctx->shape.n, count, P.data(), roots.data(), invk.data(), ctx->kmax_log2, 0, ctx);
-  });
-  if (rc) return rc;
-  try {
-    ctx->bcn_child[key] = child;
-  } catch (const std::bad_alloc &) {
-    nflhip_ctx_destroy(child);
-    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
-  }
-  *out = child;
-  return NFLHIP_OK;
+  return child_in_map(ctx, ctx->bcn_child, {first, count}, count, [first](size_t i) { return first + i; }, cap,
+                      "baseconv_ntt: the composed plan's child context has to be created, which a stream capture cannot do", out);
 }
-static int bcn_scratch(nflhip_ctx *ctx, int slot, size_t need, bool cap) {  // under bcn_mu
-  if (ctx->bcn_scratch_bytes[slot] >= need) return NFLHIP_OK;
-  if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "baseconv_ntt: the composed plan's scratch has to grow, which a stream capture cannot do");
-  if (ctx->bcn_scratch[slot]) HIPCHK(ctx, hipFree(ctx->bcn_scratch[slot]));  // (synchronises: nothing still reads it)
-  ctx->bcn_scratch[slot] = nullptr;
-  ctx->bcn_scratch_bytes[slot] = 0;
-  HIPCHK(ctx, hipMalloc(&ctx->bcn_scratch[slot], need));
-  ctx->bcn_scratch_bytes[slot] = need;
-  return NFLHIP_OK;
+// ... the same for a caller that does not hold bcn_mu: the child over the rows [0, L)
+static int kept_rows_child(nflhip_ctx *ctx, size_t L, bool cap, nflhip_ctx **out) {
+  std::lock_guard<std::mutex> lk(ctx->bcn_mu);
+  int rc = bcn_child(ctx, 0, L, cap, out);
+  return rc ? rc : set_device(ctx);
 }
 static int baseconv_ntt_composed(nflhip_ctx *ctx, void *out, const void *in, const uint64_t *rec, size_t batch, size_t s0, size_t ks, size_t d0,
                                  size_t kd, bool centred, bool moddown, hipStream_t st) {
@@ -999,20 +1032,19 @@ static int baseconv_ntt_composed(nflhip_ctx *ctx, void *out, const void *in, con
   nflhip_ctx *cs = nullptr, *cd = nullptr;
   int rc = bcn_child(ctx, s0, ks, cap, &cs);
   if (!rc) rc = bcn_child(ctx, d0, kd, cap, &cd);
-  if (!rc) rc = bcn_scratch(ctx, 0, batch * ks * row, cap);
-  // (the second scratch starts d0 rows early: k_baseconv writes row d0 + j of a polynomial of kd rows, so the dense rows begin at
-  // row d0 of the buffer)
-  if (!rc && !moddown && !whole) rc = bcn_scratch(ctx, 1, (d0 + batch * kd) * row, cap);
   if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (!ctx->ev_bcn) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_bcn, hipEventDisableTiming));
-  if (!cap && ctx->ev_bcn_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_bcn, 0));  // a previous call on another stream
-  void *src = ctx->bcn_scratch[0];
+  const char *what = "baseconv_ntt: the composed plan's";
+  // (the second workspace starts d0 rows early: k_baseconv writes row d0 + j of a polynomial of kd rows, so the dense rows begin at
+  // row d0 of the buffer)
+  if (!moddown && !whole && (rc = ws_grow(ctx, ctx->bcn_ws[1], (d0 + batch * kd) * row, cap, what))) return rc;
+  if ((rc = ws_begin(ctx, ctx->bcn_ws[0], batch * ks * row, cap, st, what))) return rc;
+  void *src = ctx->bcn_ws[0].buf;
   HIPCHK(ctx, hipMemcpy2DAsync(src, ks * row, (const char *)in + s0 * row, nm * row, ks * row, batch, hipMemcpyDeviceToDevice, st));
   rc = nflhip_ntt_inv_dev(cs, src, batch, st);
   if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  void *conv = moddown || whole ? out : ctx->bcn_scratch[1];  // where k_baseconv's polynomial 0, row 0 would be
+  void *conv = moddown || whole ? out : ctx->bcn_ws[1].buf;  // where k_baseconv's polynomial 0, row 0 would be
   const size_t onm = moddown || !whole ? kd : nm;
   hipError_t e = with_limb(ctx, [&](auto z) {
     typedef decltype(z) T;
@@ -1032,11 +1064,7 @@ static int baseconv_ntt_composed(nflhip_ctx *ctx, void *out, const void *in, con
   } else if (!whole) {
     HIPCHK(ctx, hipMemcpy2DAsync((char *)out + d0 * row, nm * row, dense, kd * row, kd * row, batch, hipMemcpyDeviceToDevice, st));
   }
-  if (!cap) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_bcn, st));
-    ctx->ev_bcn_valid = true;
-  }
-  return NFLHIP_OK;
+  return ws_end(ctx, ctx->bcn_ws[0], cap, st);
 }
 // Where the one-launch kernel serves by default: when its rows fit the LDS and a row has up to 2048 words.  Measured against the
 // composed plan in one run, alternated (profiles/r13_baseconv_ntt.txt), composed / fused: x1.43 - x1.78 for the mod-ups
@@ -1044,8 +1072,11 @@ static int baseconv_ntt_composed(nflhip_ctx *ctx, void *out, const void *in, con
 // 16 KiB) and x0.88 at u64/4096/4 (32 KiB) -- at 4096 words the generated register-tiled transforms of the composed plan outrun the
 // radix-4 LDS transforms by more than the gather and the extra passes cost, whatever the row's bytes: the rule is in words, as
 // decompose_fused_on.  Contexts created under NFLHIP_VARIANT=hipcc compose.
+static bool rows_take_lds_conversions(const nflhip_ctx *ctx) {  // THE rule in words; the plans built on the conversions ask it too
+  return ctx->shape.n <= 2048;
+}
 static bool baseconv_ntt_fused_on(const nflhip_ctx *ctx) {
-  return !ctx->shape.compiled_only && ctx->shape.n <= 2048;
+  return !ctx->shape.compiled_only && rows_take_lds_conversions(ctx);
 }
 static int baseconv_ntt_run(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t s0, size_t ks, size_t d0, size_t kd, int flags,
                             bool centred, bool moddown, hipStream_t st) {
@@ -1085,35 +1116,9 @@ int nflhip_moddown_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_
 // which read it (dot_key and the two one-launch kernels).
 static int level_child(nflhip_ctx *ctx, size_t K, size_t level, bool cap, nflhip_ctx **out) {
   std::lock_guard<std::mutex> lk(ctx->bcn_mu);
-  const std::array<size_t, 2> key = {K, level};
-  auto it = ctx->lvl_child.find(key);
-  if (it != ctx->lvl_child.end()) {
-    *out = it->second;
-    return NFLHIP_OK;
-  }
-  if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "level: the first call at a (k_special, level) creates its context, which a stream capture cannot do");
-  const size_t nm = ctx->shape.nm, count = level + K;
-  nflhip_ctx *child = nullptr;
-  int rc = with_limb(ctx, [&](auto z) {
-    typedef decltype(z) T;
-    std::vector<T> P(count), roots(count), invk(count);
-    for (size_t i = 0; i < count; ++i) {
-      const size_t j = i < level ? i : nm - count + i;  // phys(i)
-      P[i] = (T)ctx->h_P[j];
-      roots[i] = (T)ctx->h_roots[j];
-      invk[i] = (T)ctx->h_invk[j];
-    }
-    return ctx_create_mode(&child, ctx->device, ctx->shape.limb_bits, ctx->shape.n, count, P.data(), roots.data(), invk.data(), ctx->kmax_log2, 0, ctx);
-  });
-  if (rc) return rc;
-  try {
-    ctx->lvl_child[key] = child;
-  } catch (const std::bad_alloc &) {
-    nflhip_ctx_destroy(child);
-    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
-  }
-  *out = child;
-  return NFLHIP_OK;
+  const size_t count = level + K, hole = ctx->shape.nm - count;
+  return child_in_map(ctx, ctx->lvl_child, {K, level}, count, [level, hole](size_t i) { return i < level ? i : hole + i; }, cap,
+                      "level: the first call at a (k_special, level) creates its context, which a stream capture cannot do", out);
 }
 // acc = [addend +] sum_d a(., d) (.) key[d][c]: nflhip_dot_dev with the key as the shared second operand, a term every two polynomials;
 // kl: the key lies in the parent's layout (ctx is a level context)
@@ -1146,7 +1151,9 @@ static int dot_key(nflhip_ctx *ctx, void *out, const nflhip_dot_operand *a, cons
 // 2 batch polynomials when out1 follows out0 in memory (Engine.key_switch_ntt allocates them so), else one per output.
 // The records are those of baseconv_record: every digit's and the mod-down's are built BEFORE anything is enqueued, so a repeated
 // modulus is refused with the builder's message and nothing written.
-static int keyswitch_records(nflhip_ctx *ctx, size_t K, size_t alpha, hipStream_t st, const uint64_t *const **recs) {  // under ks_mu
+// UNDER ks_mu, which is not recursive and which this function therefore never takes: keyswitch_run holds it for its whole call, the
+// other three callers take it around this fetch alone (after their own mutex, before bcn_mu).
+static int keyswitch_records(nflhip_ctx *ctx, size_t K, size_t alpha, hipStream_t st, const uint64_t *const **recs) try {
   const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha;
   std::vector<const uint64_t *> h(dnum);
   const uint64_t *down = nullptr;
@@ -1171,6 +1178,8 @@ static int keyswitch_records(nflhip_ctx *ctx, size_t K, size_t alpha, hipStream_
   }
   *recs = (const uint64_t *const *)it->second;
   return NFLHIP_OK;
+} catch (const std::bad_alloc &) {
+  return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
 }
 // Which plan serves by default.  Measured against the sequence in one run, alternated (profiles/r14_keyswitch.txt),
 // sequence / plan: the one-launch kernel x1.11 / x1.10 at u64/1024/4 (alpha 1 / 3) and x1.05 at u64/2048/4; the composed plan x0.84 /
@@ -1180,54 +1189,92 @@ static int keyswitch_records(nflhip_ctx *ctx, size_t K, size_t alpha, hipStream_
 // composed plan for rows above 2048 words and the sequence for shorter ones, where the composed plan measured slower.
 static int keyswitch_default_plan(const nflhip_ctx *ctx, size_t L, size_t dnum, bool centred) {
   if (!ctx->shape.compiled_only && keyswitch_fused_fits(L, dnum, ctx->shape.n, ctx->word, centred)) return NFLHIP_KEYSWITCH_FUSED;
-  return ctx->shape.n > 2048 ? NFLHIP_KEYSWITCH_COMPOSED : NFLHIP_KEYSWITCH_SEQUENCE;
+  return rows_take_lds_conversions(ctx) ? NFLHIP_KEYSWITCH_SEQUENCE : NFLHIP_KEYSWITCH_COMPOSED;
+}
+// The mod-up of every digit of `batch` polynomials on L rows, by one of two routes with the same words:
+//   per digit   X = the input embedded in nm rows; nflhip_baseconv_ntt_dev per digit: U = [dnum][batch][nm][n], the operand {U, 1, batch}
+//   all digits  X = the input, L rows dense; one inverse transform by the child over rows [0, L), k_modup_digits, one forward transform
+//               of this context over batch dnum polynomials: U = [batch][dnum][nm][n], the operand {U, dnum, 1}
+// The route is the CALLER's: the key switch takes it from its plan (the sequence is per digit, the composed plan all digits), the
+// entries built on the mod-up from modup_default_route -- so a context created under NFLHIP_VARIANT=hipcc with rows up to 2048 words
+// goes per digit in the key switch's default plan and all digits in theirs.
+enum ModupRoute { kModupPerDigit, kModupAllDigits };
+static ModupRoute modup_default_route(const nflhip_ctx *ctx) { return baseconv_ntt_fused_on(ctx) ? kModupPerDigit : kModupAllDigits; }
+static size_t modup_x_bytes(const nflhip_ctx *ctx, ModupRoute route, size_t batch, size_t L) {
+  return batch * (route == kModupPerDigit ? ctx->shape.nm : L) * ctx->shape.n * ctx->word;
+}
+// X from an input that lies elsewhere (the merged multiplication has none: its tensor kernel writes X)
+static int modup_copy_in(nflhip_ctx *ctx, ModupRoute route, void *X, const void *in, size_t batch, size_t L, hipStream_t st) {
+  const size_t row = ctx->shape.n * ctx->word, pb = ctx->shape.nm * row, qb = L * row;
+  if (route == kModupPerDigit) HIPCHK(ctx, hipMemcpy2DAsync(X, pb, in, qb, qb, batch, hipMemcpyDeviceToDevice, st));
+  else HIPCHK(ctx, hipMemcpyAsync(X, in, batch * qb, hipMemcpyDeviceToDevice, st));
+  return NFLHIP_OK;
+}
+// U and its operand *u from X; `child`: the context over rows [0, L) (all digits); `what`: the entry, for an error's text
+static int modup_run(nflhip_ctx *ctx, nflhip_ctx *child, ModupRoute route, void *U, void *X, const uint64_t *const *recs, size_t batch, size_t L,
+                     size_t alpha, bool centred, const char *what, hipStream_t st, nflhip_dot_operand *u) {
+  const size_t nm = ctx->shape.nm, dnum = (L + alpha - 1) / alpha, pb = nm * ctx->shape.n * ctx->word;
+  int rc;
+  if (route == kModupPerDigit) {
+    for (size_t d = 0; d < dnum; ++d)
+      if ((rc = nflhip_baseconv_ntt_dev(ctx, (char *)U + d * batch * pb, X, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm,
+                                        centred ? NFLHIP_BASECONV_CENTERED : 0, st)))
+        return rc;
+    *u = {U, 1, batch};
+  } else {
+    if ((rc = nflhip_ntt_inv_dev(child, X, batch, st)) || (rc = set_device(ctx))) return rc;
+    hipError_t e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_modup_digits<T>(ctx->shape, ctx->tabs, (T *)U, (const T *)X, recs, batch, L, alpha, centred, st);
+    });
+    if (e != hipSuccess) return hipfail(ctx, e, (std::string(what) + ": mod-up").c_str());
+    if ((rc = nflhip_ntt_fwd_dev(ctx, U, batch * dnum, st))) return rc;
+    *u = {U, dnum, 1};
+  }
+  return set_device(ctx);
+}
+// The mod-down of the two sums acc = [2][batch][nm][n] by the last `drop` rows: one call of 2 batch polynomials when out1 follows out0
+// in memory (the Engine allocates them so), else one per output
+static bool moddown_pair_adjacent(const nflhip_ctx *ctx, const void *out0, const void *out1, size_t batch, size_t drop) {
+  return (const char *)out1 == (const char *)out0 + batch * (ctx->shape.nm - drop) * ctx->shape.n * ctx->word;
+}
+static int moddown_pair(nflhip_ctx *ctx, void *out0, void *out1, const void *acc, size_t batch, size_t drop, bool floor, hipStream_t st) {
+  const int mdflags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
+  int rc;
+  if (moddown_pair_adjacent(ctx, out0, out1, batch, drop)) {
+    rc = nflhip_moddown_ntt_dev(ctx, out0, acc, 2 * batch, drop, mdflags, st);
+  } else {
+    rc = nflhip_moddown_ntt_dev(ctx, out0, acc, batch, drop, mdflags, st);
+    if (!rc) rc = nflhip_moddown_ntt_dev(ctx, out1, (const char *)acc + poly_bytes(ctx, batch), batch, drop, mdflags, st);
+  }
+  return rc ? rc : set_device(ctx);
 }
 static int keyswitch_run(nflhip_ctx *ctx, void *out0, void *out1, const void *in, const void *key, size_t batch, size_t K, size_t alpha, int flags,
                          hipStream_t st, const KeyLevel *kl = nullptr) {
   std::lock_guard<std::mutex> lk(ctx->ks_mu);
-  const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha, row = ctx->shape.n * ctx->word, pb = nm * row;
+  const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha, pb = nm * ctx->shape.n * ctx->word;
   const bool centred = (flags & NFLHIP_KEYSWITCH_CENTERED) != 0, floor = (flags & NFLHIP_KEYSWITCH_FLOOR) != 0, cap = is_capturing(st);
   const uint64_t *const *recs = nullptr;
-  int rc;
-  try {
-    rc = keyswitch_records(ctx, K, alpha, st, &recs);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
-  }
+  int rc = keyswitch_records(ctx, K, alpha, st, &recs);
   if (rc) return rc;
   int plan = flags & (NFLHIP_KEYSWITCH_COMPOSED | NFLHIP_KEYSWITCH_FUSED | NFLHIP_KEYSWITCH_SEQUENCE);
   if (plan == NFLHIP_KEYSWITCH_FUSED && !keyswitch_fused_fits(L, dnum, ctx->shape.n, ctx->word, centred))
     return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "keyswitch: the rows of this call do not fit the one-launch kernel's LDS");
   if (!plan) plan = keyswitch_default_plan(ctx, L, dnum, centred);
   // what a call while capturing may do: repeat a (k_special, alpha, plan, modes) already served at this batch or a larger one
-  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | (flags & (NFLHIP_KEYSWITCH_CENTERED | NFLHIP_KEYSWITCH_FLOOR)))};
-  auto wit = ctx->ks_warm.find(wkey);
-  if (cap && (wit == ctx->ks_warm.end() || wit->second < batch))
+  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | (flags & (NFLHIP_KEYSWITCH_CENTERED | NFLHIP_KEYSWITCH_FLOOR)))}, wsizes = {batch, 0, 0};
+  if (cap && !warm_covers(ctx->ks_warm, wkey, wsizes))
     return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "keyswitch: the first call for a (k_special, alpha, plan), or for a larger batch, allocates, which a stream capture cannot do");
-  const size_t xb = plan == NFLHIP_KEYSWITCH_SEQUENCE ? batch * pb : plan == NFLHIP_KEYSWITCH_COMPOSED ? batch * L * row : 0;
-  const size_t ub = plan == NFLHIP_KEYSWITCH_FUSED ? 0 : batch * dnum * pb, ab = 2 * batch * pb, need = xb + ub + ab;
+  const bool fused = plan == NFLHIP_KEYSWITCH_FUSED;
+  const ModupRoute route = plan == NFLHIP_KEYSWITCH_SEQUENCE ? kModupPerDigit : kModupAllDigits;
+  const size_t xb = fused ? 0 : modup_x_bytes(ctx, route, batch, L), ub = fused ? 0 : batch * dnum * pb, ab = 2 * batch * pb;
   if ((rc = set_device(ctx))) return rc;
   nflhip_ctx *child = nullptr;
-  if (plan == NFLHIP_KEYSWITCH_COMPOSED) {
-    std::lock_guard<std::mutex> l2(ctx->bcn_mu);
-    if ((rc = bcn_child(ctx, 0, L, cap, &child))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-  }
-  if (ctx->ks_scratch_bytes < need) {
-    if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "keyswitch: the scratch has to grow, which a stream capture cannot do");
-    if (ctx->ks_scratch) HIPCHK(ctx, hipFree(ctx->ks_scratch));  // (synchronises: nothing still reads it)
-    ctx->ks_scratch = nullptr;
-    ctx->ks_scratch_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->ks_scratch, need));
-    ctx->ks_scratch_bytes = need;
-  }
-  if (!ctx->ev_ks) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_ks, hipEventDisableTiming));
-  if (!cap && ctx->ev_ks_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_ks, 0));  // a previous call on another stream
-  char *X = (char *)ctx->ks_scratch, *U = X + xb, *acc = U + ub;
-  const int bcflags = centred ? NFLHIP_BASECONV_CENTERED : 0;
-  hipError_t e = hipSuccess;
-  if (plan == NFLHIP_KEYSWITCH_FUSED) {
-    e = with_limb(ctx, [&](auto z) {
+  if (plan == NFLHIP_KEYSWITCH_COMPOSED && (rc = kept_rows_child(ctx, L, cap, &child))) return rc;
+  if ((rc = ws_begin(ctx, ctx->ks_ws, xb + ub + ab, cap, st, "keyswitch: the"))) return rc;
+  char *X = (char *)ctx->ks_ws.buf, *U = X + xb, *acc = U + ub;
+  if (fused) {
+    hipError_t e = with_limb(ctx, [&](auto z) {
       typedef decltype(z) T;
       if (kl) return launch_modup_dot_fused_level<T>(ctx->shape, ctx->tabs, (T *)acc, (const T *)in, (const T *)key, recs, batch, L, alpha, centred, *kl, st);
       return launch_modup_dot_fused<T>(ctx->shape, ctx->tabs, (T *)acc, (const T *)in, (const T *)key, recs, batch, L, alpha, centred, st);
@@ -1236,42 +1283,13 @@ static int keyswitch_run(nflhip_ctx *ctx, void *out0, void *out1, const void *in
     if (e != hipSuccess) return hipfail(ctx, e, "keyswitch (fused)");
   } else {
     nflhip_dot_operand a;
-    if (plan == NFLHIP_KEYSWITCH_SEQUENCE) {
-      HIPCHK(ctx, hipMemcpy2DAsync(X, pb, in, L * row, L * row, batch, hipMemcpyDeviceToDevice, st));
-      for (size_t d = 0; d < dnum; ++d)
-        if ((rc = nflhip_baseconv_ntt_dev(ctx, U + d * batch * pb, X, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm, bcflags, st))) return rc;
-      a = {U, 1, batch};
-    } else {
-      HIPCHK(ctx, hipMemcpyAsync(X, in, batch * L * row, hipMemcpyDeviceToDevice, st));
-      if ((rc = nflhip_ntt_inv_dev(child, X, batch, st)) || (rc = set_device(ctx))) return rc;
-      e = with_limb(ctx, [&](auto z) {
-        typedef decltype(z) T;
-        return launch_modup_digits<T>(ctx->shape, ctx->tabs, (T *)U, (const T *)X, recs, batch, L, alpha, centred, st);
-      });
-      if (e != hipSuccess) return hipfail(ctx, e, "keyswitch: mod-up");
-      if ((rc = nflhip_ntt_fwd_dev(ctx, U, batch * dnum, st))) return rc;
-      a = {U, dnum, 1};
-    }
+    if ((rc = modup_copy_in(ctx, route, X, in, batch, L, st))) return rc;
+    if ((rc = modup_run(ctx, child, route, U, X, recs, batch, L, alpha, centred, "keyswitch", st, &a))) return rc;
     for (size_t c = 0; c < 2; ++c)
       if ((rc = dot_key(ctx, acc + c * batch * pb, &a, key, c, nullptr, batch, dnum, kl, st))) return rc;
   }
-  const int mdflags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
-  if ((char *)out1 == (char *)out0 + batch * L * row) {
-    rc = nflhip_moddown_ntt_dev(ctx, out0, acc, 2 * batch, K, mdflags, st);
-  } else {
-    rc = nflhip_moddown_ntt_dev(ctx, out0, acc, batch, K, mdflags, st);
-    if (!rc) rc = nflhip_moddown_ntt_dev(ctx, out1, acc + batch * pb, batch, K, mdflags, st);
-  }
-  if (rc || (rc = set_device(ctx))) return rc;
-  if (!cap) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_ks, st));
-    ctx->ev_ks_valid = true;
-    try {
-      size_t &w = ctx->ks_warm[wkey];
-      if (w < batch) w = batch;
-    } catch (const std::bad_alloc &) {
-    }
-  }
+  if ((rc = moddown_pair(ctx, out0, out1, acc, batch, K, floor, st)) || (rc = ws_end(ctx, ctx->ks_ws, cap, st))) return rc;
+  if (!cap) warm_note(ctx->ks_warm, wkey, wsizes);
   return NFLHIP_OK;
 }
 size_t nflhip_keyswitch_digits(const nflhip_ctx *ctx, size_t k_special, size_t alpha) { return keyswitch_digits(ctx, k_special, alpha); }
@@ -1288,10 +1306,8 @@ int nflhip_keyswitch_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const 
 //   sequence  per rotation nflhip_keyswitch_ntt_dev (its default plan) into T0, T1 = [batch][L][n], c0 added by nflhip_pointwise_dev on
 //             the child context over rows [0, L) -- or, where that entry cannot serve (a pointer off 16 bytes, a batch that is no whole
 //             number of 16-byte groups), by nflhip_dot_dev as c0 + T0 (.) 1 into T2 --, then nflhip_automorphism_dev twice
-//   hoisted   the mod-up once into U, by the two routes of keyswitch_run (per-digit nflhip_baseconv_ntt_dev from X = c1 embedded in nm
-//             rows, U = [dnum][batch][nm][n]; or X = c1 inverse-transformed, k_modup_digits, one forward transform, U =
-//             [batch][dnum][nm][n]); k_dot_multi into S = [2 count][batch][nm][n]; one mod-down into Y = [2 count][batch][L][n];
-//             k_permute_add_ntt
+//   hoisted   the mod-up of c1 once into U (modup_run, the route modup_default_route's); k_dot_multi into S = [2 count][batch][nm][n];
+//             one mod-down into Y = [2 count][batch][L][n]; k_permute_add_ntt
 // Default: hoisted for count >= 2, the sequence for count == 1 (a single rotation has no mod-up to share and the key switch's own
 // default plan is the measured best there).
 // Lock order: rot_mu, then ks_mu, then bcn_mu.
@@ -1304,44 +1320,25 @@ static int rotate_run(nflhip_ctx *ctx, void *const *out0s, void *const *out1s, c
   int rc;
   {  // the tables first: a repeated modulus is refused with the builder's message before anything is enqueued
     std::lock_guard<std::mutex> l2(ctx->ks_mu);
-    try {
-      rc = keyswitch_records(ctx, K, alpha, st, &recs);
-    } catch (const std::bad_alloc &) {
-      return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
-    }
+    rc = keyswitch_records(ctx, K, alpha, st, &recs);
   }
   if (rc) return rc;
   int plan = flags & (NFLHIP_ROTATE_SEQUENCE | NFLHIP_ROTATE_HOISTED);
   if (!plan) plan = count >= 2 ? NFLHIP_ROTATE_HOISTED : NFLHIP_ROTATE_SEQUENCE;
   const int modes = flags & (NFLHIP_ROTATE_CENTERED | NFLHIP_ROTATE_FLOOR);
   // what a call while capturing may do: repeat a (k_special, alpha, plan, modes) already served at this batch and count * batch or larger
-  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes)};
-  auto wit = ctx->rot_warm.find(wkey);
-  if (cap && (wit == ctx->rot_warm.end() || wit->second[0] < batch || wit->second[1] < count * batch))
+  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes)}, wsizes = {batch, count * batch, 0};
+  if (cap && !warm_covers(ctx->rot_warm, wkey, wsizes))
     return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "rotate: the first call for a (k_special, alpha, plan), or for a larger batch, allocates, which a stream capture cannot do");
-  const bool seq = plan == NFLHIP_ROTATE_SEQUENCE, perdigit = !ctx->shape.compiled_only && ctx->shape.n <= 2048;
+  const bool seq = plan == NFLHIP_ROTATE_SEQUENCE;
+  const ModupRoute route = modup_default_route(ctx);
   // sequence: T0, T1, T2 and a polynomial of ones; hoisted: X, U, S, Y
-  const size_t xb = seq ? 3 * batch * qb + qb : perdigit ? batch * pb : batch * qb;
+  const size_t xb = seq ? 3 * batch * qb + qb : modup_x_bytes(ctx, route, batch, L);
   const size_t ub = seq ? 0 : batch * dnum * pb, sb = seq ? 0 : 2 * count * batch * pb, yb = seq ? 0 : 2 * count * batch * qb;
-  const size_t need = xb + ub + sb + yb;
   if ((rc = set_device(ctx))) return rc;
   nflhip_ctx *child = nullptr;
-  {
-    std::lock_guard<std::mutex> l2(ctx->bcn_mu);
-    if ((rc = bcn_child(ctx, 0, L, cap, &child))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-  }
-  if (ctx->rot_scratch_bytes < need) {
-    if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "rotate: the scratch has to grow, which a stream capture cannot do");
-    if (ctx->rot_scratch) HIPCHK(ctx, hipFree(ctx->rot_scratch));  // (synchronises: nothing still reads it)
-    ctx->rot_scratch = nullptr;
-    ctx->rot_scratch_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->rot_scratch, need));
-    ctx->rot_scratch_bytes = need;
-  }
-  if (!ctx->ev_rot) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_rot, hipEventDisableTiming));
-  if (!cap && ctx->ev_rot_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_rot, 0));  // a previous call on another stream
-  char *X = (char *)ctx->rot_scratch;
+  if ((rc = kept_rows_child(ctx, L, cap, &child)) || (rc = ws_begin(ctx, ctx->rot_ws, xb + ub + sb + yb, cap, st, "rotate: the"))) return rc;
+  char *X = (char *)ctx->rot_ws.buf;
   if (seq) {
     char *T0 = X, *T1 = T0 + batch * qb, *T2 = T1 + batch * qb, *ones = T2 + batch * qb;
     const bool pw = (((uintptr_t)T0 | (uintptr_t)c0) & 15u) == 0 && (batch * qb) % 16 == 0;  // what nflhip_pointwise_dev serves
@@ -1365,26 +1362,9 @@ static int rotate_run(nflhip_ctx *ctx, void *const *out0s, void *const *out1s, c
     if ((rc = set_device(ctx))) return rc;
   } else {
     char *U = X + xb, *S = U + ub, *Y = S + sb;
-    size_t a_gs, a_ts;
-    if (perdigit) {
-      HIPCHK(ctx, hipMemcpy2DAsync(X, pb, c1, qb, qb, batch, hipMemcpyDeviceToDevice, st));
-      for (size_t d = 0; d < dnum; ++d)
-        if ((rc = nflhip_baseconv_ntt_dev(ctx, U + d * batch * pb, X, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm,
-                                          centred ? NFLHIP_BASECONV_CENTERED : 0, st)))
-          return rc;
-      a_gs = 1, a_ts = batch;
-    } else {
-      HIPCHK(ctx, hipMemcpyAsync(X, c1, batch * qb, hipMemcpyDeviceToDevice, st));
-      if ((rc = nflhip_ntt_inv_dev(child, X, batch, st)) || (rc = set_device(ctx))) return rc;
-      hipError_t e = with_limb(ctx, [&](auto z) {
-        typedef decltype(z) T;
-        return launch_modup_digits<T>(ctx->shape, ctx->tabs, (T *)U, (const T *)X, recs, batch, L, alpha, centred, st);
-      });
-      if (e != hipSuccess) return hipfail(ctx, e, "rotate: mod-up");
-      if ((rc = nflhip_ntt_fwd_dev(ctx, U, batch * dnum, st))) return rc;
-      a_gs = dnum, a_ts = 1;
-    }
-    if ((rc = set_device(ctx))) return rc;
+    nflhip_dot_operand u;
+    if ((rc = modup_copy_in(ctx, route, X, c1, batch, L, st))) return rc;
+    if ((rc = modup_run(ctx, child, route, U, X, recs, batch, L, alpha, centred, "rotate", st, &u))) return rc;
     void *douts[2 * NFLHIP_ROTATE_MAX_OUTPUTS], *pouts[2 * NFLHIP_ROTATE_MAX_OUTPUTS];
     const void *dbs[2 * NFLHIP_ROTATE_MAX_OUTPUTS], *pins[2 * NFLHIP_ROTATE_MAX_OUTPUTS];
     uint64_t pks[2 * NFLHIP_ROTATE_MAX_OUTPUTS];
@@ -1401,8 +1381,8 @@ static int rotate_run(nflhip_ctx *ctx, void *const *out0s, void *const *out1s, c
       }
     hipError_t e = with_limb(ctx, [&](auto z) {
       typedef decltype(z) T;
-      return launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, a_gs, a_ts, (const T *const *)dbs, 2, 2 * count, batch,
-                                 dnum, 1, st);
+      return launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, u.group_stride, u.term_stride, (const T *const *)dbs, 2,
+                                 2 * count, batch, dnum, 1, st);
     });
     if (e != hipSuccess) return hipfail(ctx, e, "rotate: inner products");
     if ((rc = nflhip_moddown_ntt_dev(ctx, Y, S, 2 * count * batch, K, floor ? NFLHIP_MODDOWN_FLOOR : 0, st)) || (rc = set_device(ctx))) return rc;
@@ -1413,16 +1393,8 @@ static int rotate_run(nflhip_ctx *ctx, void *const *out0s, void *const *out1s, c
     });
     if (e != hipSuccess) return hipfail(ctx, e, "rotate: permutation");
   }
-  if (!cap) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_rot, st));
-    ctx->ev_rot_valid = true;
-    try {
-      std::array<size_t, 2> &w = ctx->rot_warm[wkey];
-      if (w[0] < batch) w[0] = batch;
-      if (w[1] < count * batch) w[1] = count * batch;
-    } catch (const std::bad_alloc &) {
-    }
-  }
+  if ((rc = ws_end(ctx, ctx->rot_ws, cap, st))) return rc;
+  if (!cap) warm_note(ctx->rot_warm, wkey, wsizes);
   return NFLHIP_OK;
 }
 int nflhip_rotate_hoisted_ntt_dev(nflhip_ctx *ctx, void *const *d_out0s, void *const *d_out1s, const void *d_c0, const void *d_c1,
@@ -1456,7 +1428,7 @@ int nflhip_automorphism_mac_dev(nflhip_ctx *ctx, void *d_out, const void *d_adde
 //             nflhip_dot_dev into T, nflhip_automorphism_dev into P, nflhip_dot_dev (one term, the addend in place) of P against the
 //             weight into A = [2][batch][nm][n]; nflhip_moddown_ntt_dev; per term nflhip_automorphism_dev of c0 and nflhip_dot_dev
 //             with the addend in place on the child context over rows [0, L)
-//   hoisted   the mod-up by the two routes of rotate_run into U; k_dot_multi into S = [2 keyed][batch][nm][n]; k_permute_mac_ntt with
+//   hoisted   the mod-up as in rotate_run into U; k_dot_multi into S = [2 keyed][batch][nm][n]; k_permute_mac_ntt with
 //             blockIdx.y the component into A; one mod-down straight into out0 / out1; k_permute_mac_ntt on L rows, the addend in
 //             place, once for out0 (the c0 terms) and once for out1 (the unkeyed terms), where there are any
 // Default: hoisted, always.  The starting rule (hoisted from two keyed terms on) did not survive the measurement: with ONE keyed term
@@ -1472,11 +1444,7 @@ static int lintrans_run(nflhip_ctx *ctx, void *out0, void *out1, const void *c0,
   int rc;
   {  // the tables first: a repeated modulus is refused with the builder's message before anything is enqueued
     std::lock_guard<std::mutex> l2(ctx->ks_mu);
-    try {
-      rc = keyswitch_records(ctx, K, alpha, st, &recs);
-    } catch (const std::bad_alloc &) {
-      return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
-    }
+    rc = keyswitch_records(ctx, K, alpha, st, &recs);
   }
   if (rc) return rc;
   // the keyed terms, in order; the rest are the unrotated diagonals
@@ -1499,61 +1467,28 @@ static int lintrans_run(nflhip_ctx *ctx, void *out0, void *out1, const void *c0,
   int plan = flags & (NFLHIP_LINTRANS_SEQUENCE | NFLHIP_LINTRANS_HOISTED);
   if (!plan) plan = NFLHIP_LINTRANS_HOISTED;
   const int modes = flags & (NFLHIP_LINTRANS_CENTERED | NFLHIP_LINTRANS_FLOOR);
-  const bool adjacent = (char *)out1 == (char *)out0 + batch * qb;
-  const size_t down = keyed ? (adjacent ? 2 * batch : batch) : 0;  // the polynomials of one mod-down call
+  const size_t down = !keyed ? 0 : moddown_pair_adjacent(ctx, out0, out1, batch, K) ? 2 * batch : batch;  // the polynomials of one mod-down call
   // what a call while capturing may do: repeat a (k_special, alpha, plan, modes) already served at this batch, keyed * batch and mod-down or larger
-  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes)};
-  auto wit = ctx->lt_warm.find(wkey);
-  if (cap && (wit == ctx->lt_warm.end() || wit->second[0] < batch || wit->second[1] < keyed * batch || wit->second[2] < down))
+  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes)}, wsizes = {batch, keyed * batch, down};
+  if (cap && !warm_covers(ctx->lt_warm, wkey, wsizes))
     return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "lintrans: the first call for a (k_special, alpha, plan), or for a larger batch, allocates, which a stream capture cannot do");
-  const bool seq = plan == NFLHIP_LINTRANS_SEQUENCE, perdigit = seq || (!ctx->shape.compiled_only && ctx->shape.n <= 2048);
+  const bool seq = plan == NFLHIP_LINTRANS_SEQUENCE;
+  const ModupRoute route = seq ? kModupPerDigit : modup_default_route(ctx);
   // sequence: X, U, T, P, A and the permuted c0 on L rows; hoisted: X, U, S, A
-  const size_t xb = !keyed ? 0 : perdigit ? batch * pb : batch * qb, ub = keyed ? batch * dnum * pb : 0;
+  const size_t xb = keyed ? modup_x_bytes(ctx, route, batch, L) : 0, ub = keyed ? batch * dnum * pb : 0;
   const size_t sb = !keyed ? 0 : seq ? 2 * batch * pb : 2 * keyed * batch * pb, ab = keyed ? 2 * batch * pb : 0, tb = seq && c0 ? batch * qb : 0;
-  const size_t need = xb + ub + sb + ab + tb;
   if ((rc = set_device(ctx))) return rc;
   nflhip_ctx *child = nullptr;
-  {
-    std::lock_guard<std::mutex> l2(ctx->bcn_mu);
-    if ((rc = bcn_child(ctx, 0, L, cap, &child))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-  }
-  if (ctx->lt_scratch_bytes < need) {
-    if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "lintrans: the scratch has to grow, which a stream capture cannot do");
-    if (ctx->lt_scratch) HIPCHK(ctx, hipFree(ctx->lt_scratch));  // (synchronises: nothing still reads it)
-    ctx->lt_scratch = nullptr;
-    ctx->lt_scratch_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->lt_scratch, need));
-    ctx->lt_scratch_bytes = need;
-  }
-  if (!ctx->ev_lt) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_lt, hipEventDisableTiming));
-  if (!cap && ctx->ev_lt_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_lt, 0));  // a previous call on another stream
-  char *X = (char *)ctx->lt_scratch, *U = X + xb, *S = U + ub, *A = S + sb, *T0 = A + ab;
+  if ((rc = kept_rows_child(ctx, L, cap, &child)) || (rc = ws_begin(ctx, ctx->lt_ws, xb + ub + sb + ab + tb, cap, st, "lintrans: the"))) return rc;
+  char *X = (char *)ctx->lt_ws.buf, *U = X + xb, *S = U + ub, *A = S + sb, *T0 = A + ab;
   const size_t pw = pb / ctx->word;  // words of a polynomial of nm rows
   if (keyed) {
-    size_t a_gs, a_ts;  // U's layout: the strides of the digits operand, in polynomials
-    if (perdigit) {
-      HIPCHK(ctx, hipMemcpy2DAsync(X, pb, c1, qb, qb, batch, hipMemcpyDeviceToDevice, st));
-      for (size_t d = 0; d < dnum; ++d)
-        if ((rc = nflhip_baseconv_ntt_dev(ctx, U + d * batch * pb, X, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm,
-                                          centred ? NFLHIP_BASECONV_CENTERED : 0, st)))
-          return rc;
-      a_gs = 1, a_ts = batch;
-    } else {
-      HIPCHK(ctx, hipMemcpyAsync(X, c1, batch * qb, hipMemcpyDeviceToDevice, st));
-      if ((rc = nflhip_ntt_inv_dev(child, X, batch, st)) || (rc = set_device(ctx))) return rc;
-      hipError_t e = with_limb(ctx, [&](auto z) {
-        typedef decltype(z) T;
-        return launch_modup_digits<T>(ctx->shape, ctx->tabs, (T *)U, (const T *)X, recs, batch, L, alpha, centred, st);
-      });
-      if (e != hipSuccess) return hipfail(ctx, e, "lintrans: mod-up");
-      if ((rc = nflhip_ntt_fwd_dev(ctx, U, batch * dnum, st))) return rc;
-      a_gs = dnum, a_ts = 1;
-    }
-    if ((rc = set_device(ctx))) return rc;
+    nflhip_dot_operand a;  // the digits
+    if ((rc = modup_copy_in(ctx, route, X, c1, batch, L, st))) return rc;
+    if ((rc = modup_run(ctx, child, route, U, X, recs, batch, L, alpha, centred, "lintrans", st, &a))) return rc;
     if (seq) {
       char *T = S, *P = S + batch * pb;
-      const nflhip_dot_operand a = {U, a_gs, a_ts}, pa = {P, 1, 0};
+      const nflhip_dot_operand pa = {P, 1, 0};
       for (size_t m = 0; m < keyed; ++m)
         for (size_t c = 0; c < 2; ++c) {
           const nflhip_dot_operand b = {(const char *)kkeys[m] + c * pb, 0, 2}, w = {kw[m], 0, 0};
@@ -1574,22 +1509,15 @@ static int lintrans_run(nflhip_ctx *ctx, void *out0, void *out1, const void *c0,
       }
       hipError_t e = with_limb(ctx, [&](auto z) {
         typedef decltype(z) T;
-        hipError_t r = launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, a_gs, a_ts, (const T *const *)dbs, 2, 2 * keyed,
-                                           batch, dnum, 1, st);
+        hipError_t r = launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, a.group_stride, a.term_stride,
+                                           (const T *const *)dbs, 2, 2 * keyed, batch, dnum, 1, st);
         if (r != hipSuccess) return r;
         return launch_permute_mac_ntt<T>(ctx->shape, ctx->tabs, (T *)A, nullptr, (const T *const *)mins, (const T *const *)kw, kks, (int)keyed, batch,
                                          nm, 2, batch * pw, batch * pw, 0, st);
       });
       if (e != hipSuccess) return hipfail(ctx, e, "lintrans: inner products and weighted sum");
     }
-    const int mdflags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
-    if (adjacent) {
-      rc = nflhip_moddown_ntt_dev(ctx, out0, A, 2 * batch, K, mdflags, st);
-    } else {
-      rc = nflhip_moddown_ntt_dev(ctx, out0, A, batch, K, mdflags, st);
-      if (!rc) rc = nflhip_moddown_ntt_dev(ctx, out1, A + batch * pb, batch, K, mdflags, st);
-    }
-    if (rc || (rc = set_device(ctx))) return rc;
+    if ((rc = moddown_pair(ctx, out0, out1, A, batch, K, floor, st))) return rc;
   }
   // the terms on L rows: every diagonal against sigma(c0) into out0, the unrotated unkeyed ones against c1 into out1
   if (!keyed && !c0) HIPCHK(ctx, hipMemsetAsync(out0, 0, batch * qb, st));  // (out1 has a term: with no keyed one, every term is unkeyed)
@@ -1618,17 +1546,8 @@ static int lintrans_run(nflhip_ctx *ctx, void *out0, void *out1, const void *c0,
     });
     if (e != hipSuccess) return hipfail(ctx, e, "lintrans: the terms on the kept rows");
   }
-  if (!cap) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_lt, st));
-    ctx->ev_lt_valid = true;
-    try {
-      std::array<size_t, 3> &w = ctx->lt_warm[wkey];
-      if (w[0] < batch) w[0] = batch;
-      if (w[1] < keyed * batch) w[1] = keyed * batch;
-      if (w[2] < down) w[2] = down;
-    } catch (const std::bad_alloc &) {
-    }
-  }
+  if ((rc = ws_end(ctx, ctx->lt_ws, cap, st))) return rc;
+  if (!cap) warm_note(ctx->lt_warm, wkey, wsizes);
   return NFLHIP_OK;
 }
 int nflhip_lintrans_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_c0, const void *d_c1, const void *const *d_keys,
@@ -1662,7 +1581,7 @@ int nflhip_tensor_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, void *d_o
 //             first); A_c = X_c (.) C by a one-term nflhip_dot_dev, C the constant polynomial of pi; per-digit nflhip_baseconv_ntt_dev
 //             from X_2 into U = [dnum][batch][nm][n]; nflhip_dot_dev into A_c with A_c as the addend
 //   merged    k_tensor_ntt once: d2 into X (embedded in nm rows for the per-digit route, else L rows dense), pi d_c into A; the mod-up
-//             by the two routes of rotate_run; nflhip_dot_dev into A_c with A_c as the addend
+//             as in rotate_run; nflhip_dot_dev into A_c with A_c as the addend
 //   fused     k_tensor_modup_dot_fused straight from the inputs to A; bounded as the key switch's one-launch kernel
 // then nflhip_moddown_ntt_dev -- one call of 2 batch polynomials when out1 follows out0 in memory, else one per output.  Every read
 // of a and b is enqueued before the mod-down, so an output may be an input.
@@ -1727,11 +1646,7 @@ static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0,
   int rc;
   {  // the tables first: a repeated modulus is refused with the builder's message before anything is enqueued
     std::lock_guard<std::mutex> l2(ctx->ks_mu);
-    try {
-      rc = keyswitch_records(ctx, K, alpha, st, &recs);
-    } catch (const std::bad_alloc &) {
-      return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
-    }
+    rc = keyswitch_records(ctx, K, alpha, st, &recs);
   }
   // the mod-down by K + 1 rows: its record is built HERE only so that a repeated modulus is refused before anything is enqueued; the
   // mod-down entry below looks it up again itself
@@ -1750,34 +1665,20 @@ static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0,
   if (!plan) plan = mulrelin_default_plan(ctx, L, dnum, centred);
   const int modes = flags & (NFLHIP_MULRELIN_CENTERED | NFLHIP_MULRELIN_FLOOR | NFLHIP_MULRELIN_RESCALE);
   // what a call while capturing may do: repeat a (k_special, alpha, plan, modes) already served at this batch or a larger one
-  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes)};
-  auto wit = ctx->mr_warm.find(wkey);
-  if (cap && (wit == ctx->mr_warm.end() || wit->second < batch))
+  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes)}, wsizes = {batch, 0, 0};
+  if (cap && !warm_covers(ctx->mr_warm, wkey, wsizes))
     return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "mulrelin: the first call for a (k_special, alpha, plan), or for a larger batch, allocates, which a stream capture cannot do");
   const bool seq = plan == NFLHIP_MULRELIN_SEQUENCE, fused = plan == NFLHIP_MULRELIN_FUSED;
-  const bool perdigit = seq || (!ctx->shape.compiled_only && n <= 2048);
+  const ModupRoute route = seq ? kModupPerDigit : modup_default_route(ctx);
   // sequence: S, D, X, U, A; merged: X, U, A; fused: A
-  const size_t sb = seq ? 7 * batch * qb : 0, xb = fused ? 0 : seq ? 3 * batch * pb : perdigit ? batch * pb : batch * qb;
-  const size_t ub = fused ? 0 : batch * dnum * pb, ab = 2 * batch * pb, need = sb + xb + ub + ab;
+  const size_t sb = seq ? 7 * batch * qb : 0, xb = fused ? 0 : seq ? 3 * batch * pb : modup_x_bytes(ctx, route, batch, L);
+  const size_t ub = fused ? 0 : batch * dnum * pb, ab = 2 * batch * pb;
   if ((rc = set_device(ctx))) return rc;
   nflhip_ctx *child = nullptr;
-  if (!fused) {  // the L-row context: the sequence's tensor product, the merged plan's inverse transform
-    std::lock_guard<std::mutex> l2(ctx->bcn_mu);
-    if ((rc = bcn_child(ctx, 0, L, cap, &child))) return rc;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-  }
-  if (ctx->mr_scratch_bytes < need) {
-    if (cap) return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "mulrelin: the scratch has to grow, which a stream capture cannot do");
-    if (ctx->mr_scratch) HIPCHK(ctx, hipFree(ctx->mr_scratch));  // (synchronises: nothing still reads it)
-    ctx->mr_scratch = nullptr;
-    ctx->mr_scratch_bytes = 0;
-    HIPCHK(ctx, hipMalloc(&ctx->mr_scratch, need));
-    ctx->mr_scratch_bytes = need;
-  }
-  if (!ctx->ev_mr) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_mr, hipEventDisableTiming));
-  if (!cap && ctx->ev_mr_valid) HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_mr, 0));  // a previous call on another stream
-  char *S = (char *)ctx->mr_scratch, *X = S + sb, *U = X + xb, *A = U + ub;
-  const int bcflags = centred ? NFLHIP_BASECONV_CENTERED : 0;
+  // (the L-row context: the sequence's tensor product, the merged plan's inverse transform)
+  if (!fused && (rc = kept_rows_child(ctx, L, cap, &child))) return rc;
+  if ((rc = ws_begin(ctx, ctx->mr_ws, sb + xb + ub + ab, cap, st, "mulrelin: the"))) return rc;
+  char *S = (char *)ctx->mr_ws.buf, *X = S + sb, *U = X + xb, *A = U + ub;
   nflhip_dot_operand u = {nullptr, 0, 0};
   if (fused) {
     hipError_t e = with_limb(ctx, [&](auto z) {
@@ -1805,51 +1706,21 @@ static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0,
       const nflhip_dot_operand x = {X + k * batch * pb, 1, 0};
       if ((rc = nflhip_dot_dev(ctx, A + k * batch * pb, &x, &c, nullptr, batch, 1, 0, st))) return rc;
     }
-    for (size_t d = 0; d < dnum; ++d)
-      if ((rc = nflhip_baseconv_ntt_dev(ctx, U + d * batch * pb, X2, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm, bcflags, st))) return rc;
-    u = {U, 1, batch};
+    if ((rc = modup_run(ctx, child, route, U, X2, recs, batch, L, alpha, centred, "mulrelin", st, &u))) return rc;
   } else {
     const size_t pw = pb / ctx->word, qw = qb / ctx->word;
     hipError_t e = with_limb(ctx, [&](auto z) {
       typedef decltype(z) T;
       return launch_tensor_ntt<T>(ctx->shape, ctx->tabs, (T *)A, (T *)(A + batch * pb), (T *)X, (const T *)a0, (const T *)a1, (const T *)b0, (const T *)b1,
-                                  batch, L, nm, pw, perdigit ? pw : qw, pi, st);
+                                  batch, L, nm, pw, route == kModupPerDigit ? pw : qw, pi, st);
     });
     if (e != hipSuccess) return hipfail(ctx, e, "mulrelin: tensor");
-    if (perdigit) {
-      for (size_t d = 0; d < dnum; ++d)
-        if ((rc = nflhip_baseconv_ntt_dev(ctx, U + d * batch * pb, X, batch, d * alpha, std::min(alpha, L - d * alpha), 0, nm, bcflags, st))) return rc;
-      u = {U, 1, batch};
-    } else {
-      if ((rc = nflhip_ntt_inv_dev(child, X, batch, st)) || (rc = set_device(ctx))) return rc;
-      e = with_limb(ctx, [&](auto z) {
-        typedef decltype(z) T;
-        return launch_modup_digits<T>(ctx->shape, ctx->tabs, (T *)U, (const T *)X, recs, batch, L, alpha, centred, st);
-      });
-      if (e != hipSuccess) return hipfail(ctx, e, "mulrelin: mod-up");
-      if ((rc = nflhip_ntt_fwd_dev(ctx, U, batch * dnum, st))) return rc;
-      u = {U, dnum, 1};
-    }
+    if ((rc = modup_run(ctx, child, route, U, X, recs, batch, L, alpha, centred, "mulrelin", st, &u))) return rc;  // (no copy-in: the tensor wrote X)
   }
   for (size_t c = 0; c < 2 && !fused; ++c)
     if ((rc = dot_key(ctx, A + c * batch * pb, &u, key, c, A + c * batch * pb, batch, dnum, kl, st))) return rc;
-  const int mdflags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
-  if ((char *)out1 == (char *)out0 + batch * kept * row) {
-    rc = nflhip_moddown_ntt_dev(ctx, out0, A, 2 * batch, down, mdflags, st);
-  } else {
-    rc = nflhip_moddown_ntt_dev(ctx, out0, A, batch, down, mdflags, st);
-    if (!rc) rc = nflhip_moddown_ntt_dev(ctx, out1, A + batch * pb, batch, down, mdflags, st);
-  }
-  if (rc || (rc = set_device(ctx))) return rc;
-  if (!cap) {
-    HIPCHK(ctx, hipEventRecord(ctx->ev_mr, st));
-    ctx->ev_mr_valid = true;
-    try {
-      size_t &w = ctx->mr_warm[wkey];
-      if (w < batch) w = batch;
-    } catch (const std::bad_alloc &) {
-    }
-  }
+  if ((rc = moddown_pair(ctx, out0, out1, A, batch, down, floor, st)) || (rc = ws_end(ctx, ctx->mr_ws, cap, st))) return rc;
+  if (!cap) warm_note(ctx->mr_warm, wkey, wsizes);
   return NFLHIP_OK;
 }
 int nflhip_mulrelin_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_a0, const void *d_a1, const void *d_b0, const void *d_b1,
@@ -1866,31 +1737,36 @@ int nflhip_mulrelin_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const v
 size_t nflhip_keyswitch_level_digits(const nflhip_ctx *ctx, size_t k_special, size_t alpha, size_t level) {
   return keyswitch_level_digits(ctx, k_special, alpha, level);
 }
+// where a call at `level` runs: on the context itself at the top (the key is in its layout: *kl is not for use), else on the level
+// context with the key's KeyLevel
+static int level_context(nflhip_ctx *ctx, size_t K, size_t level, hipStream_t st, nflhip_ctx **run, KeyLevel *kl) {
+  const size_t nm = ctx->shape.nm, L = nm - K;
+  *run = ctx;
+  *kl = {nm, level, L - level};
+  if (level == L) return NFLHIP_OK;
+  int rc = set_device(ctx);
+  return rc ? rc : level_child(ctx, K, level, is_capturing(st), run);
+}
 int nflhip_keyswitch_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_in, const void *d_key, size_t batch, size_t k_special,
                                    size_t alpha, size_t level, int flags, void *stream) {
   int rc = level_check(ctx, k_special, level, "keyswitch");  // in full, before any device use
   if (!rc) rc = keyswitch_check(ctx, d_out0, d_out1, d_in, d_key, batch, k_special, alpha, flags, level);
   if (rc || batch == 0) return rc;
-  const size_t nm = ctx->shape.nm, L = nm - k_special;
-  hipStream_t st = (hipStream_t)stream;
-  if (level == L) return keyswitch_run(ctx, d_out0, d_out1, d_in, d_key, batch, k_special, alpha, flags, st);
-  nflhip_ctx *child = nullptr;
-  if ((rc = set_device(ctx)) || (rc = level_child(ctx, k_special, level, is_capturing(st), &child))) return rc;
-  const KeyLevel kl = {nm, level, L - level};
-  return keyswitch_run(child, d_out0, d_out1, d_in, d_key, batch, k_special, std::min(alpha, level), flags, st, &kl);
+  nflhip_ctx *run = nullptr;
+  KeyLevel kl;
+  if ((rc = level_context(ctx, k_special, level, (hipStream_t)stream, &run, &kl))) return rc;
+  return keyswitch_run(run, d_out0, d_out1, d_in, d_key, batch, k_special, std::min(alpha, level), flags, (hipStream_t)stream, run == ctx ? nullptr : &kl);
 }
 int nflhip_mulrelin_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_a0, const void *d_a1, const void *d_b0, const void *d_b1,
                                   const void *d_key, size_t batch, size_t k_special, size_t alpha, size_t level, int flags, void *stream) {
   int rc = level_check(ctx, k_special, level, "mulrelin");  // in full, before any device use
   if (!rc) rc = mulrelin_check(ctx, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, alpha, flags, level);
   if (rc || batch == 0) return rc;
-  const size_t nm = ctx->shape.nm, L = nm - k_special;
-  hipStream_t st = (hipStream_t)stream;
-  if (level == L) return mulrelin_run(ctx, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, alpha, flags, st);
-  nflhip_ctx *child = nullptr;
-  if ((rc = set_device(ctx)) || (rc = level_child(ctx, k_special, level, is_capturing(st), &child))) return rc;
-  const KeyLevel kl = {nm, level, L - level};
-  return mulrelin_run(child, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, std::min(alpha, level), flags, st, &kl);
+  nflhip_ctx *run = nullptr;
+  KeyLevel kl;
+  if ((rc = level_context(ctx, k_special, level, (hipStream_t)stream, &run, &kl))) return rc;
+  return mulrelin_run(run, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, std::min(alpha, level), flags, (hipStream_t)stream,
+                      run == ctx ? nullptr : &kl);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,
@@ -2571,17 +2447,13 @@ int nflhip_gauss_noise_dev(nflhip_ctx *ctx, int64_t *d_out, uint64_t first_sampl
 // ---------------------------------------------------------------------------
 // core::ntt / core::inv_ntt: the cyclic transform of single rows
 // ---------------------------------------------------------------------------
-static int row_child(nflhip_ctx *ctx, size_t cm, int inverse_tables, nflhip_ctx **out) {
+static int row_child(nflhip_ctx *ctx, size_t cm, int inverse_tables, hipStream_t st, nflhip_ctx **out) {
   std::lock_guard<std::mutex> lk(ctx->row_mu);
   if (ctx->row_ctx.empty()) ctx->row_ctx.assign(2 * ctx->shape.nm, nullptr);
   nflhip_ctx *&slot = ctx->row_ctx[2 * cm + (inverse_tables ? 1 : 0)];
   if (!slot) {
-    const int rc = with_limb(ctx, [&](auto z) {   // one word of each parameter table, in the limb type's own width
-      typedef decltype(z) T;
-      const T p = (T)ctx->h_P[cm], root = (T)ctx->h_roots[cm], invk = (T)ctx->h_invk[cm];
-      return ctx_create_mode(&slot, ctx->device, ctx->shape.limb_bits, ctx->shape.n, 1, &p, &root, &invk, ctx->kmax_log2,
-                             inverse_tables ? 2 : 1);
-    });
+    const int rc = child_create(ctx, 1, [cm](size_t) { return cm; }, inverse_tables ? 2 : 1, is_capturing(st),
+                                "ntt_row: the first call for a (modulus, table set) creates its context, which a stream capture cannot do", &slot);
     if (rc) return rc;
   }
   *out = slot;
@@ -2595,7 +2467,7 @@ int nflhip_ntt_row_dev(nflhip_ctx *ctx, void *d_rows, size_t cm, int mode, size_
   if (rows == 0) return NFLHIP_OK;
   if (!d_rows) return fail(ctx, NFLHIP_ERR_INVALID, "NULL data pointer");
   nflhip_ctx *child = nullptr;
-  int rc = row_child(ctx, cm, mode & NFLHIP_ROW_INVERSE_TABLES, &child);
+  int rc = row_child(ctx, cm, mode & NFLHIP_ROW_INVERSE_TABLES, (hipStream_t)stream, &child);
   if (rc) return rc;
   auto bitrev = [&]() -> int {   // core::inv_ntt: permut, ntt, permut (core.hpp:549-554)
     if (!(mode & NFLHIP_ROW_BITREV_IO)) return NFLHIP_OK;

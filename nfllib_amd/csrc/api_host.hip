@@ -294,12 +294,21 @@ struct Staged {
     else if (h) HIPCHK(ctx, hipMemcpyAsync(ctx->stage[slot], h, bytes, hipMemcpyHostToDevice, ctx->hstream));
     return NFLHIP_OK;
   }
-  int out(void *h, int slot, size_t bytes) {
-    if (!ctx->stage_host[slot]) HIPCHK(ctx, hipMemcpyAsync(h, ctx->stage[slot], bytes, hipMemcpyDeviceToHost, ctx->hstream));
+  // `count` results of `bytes` each, one behind the other in the slot
+  int outs(void *const *h, size_t count, int slot, size_t bytes) {
+    const char *s = (const char *)ctx->stage[slot];
+    if (!ctx->stage_host[slot])
+      for (size_t k = 0; k < count; ++k) HIPCHK(ctx, hipMemcpyAsync(h[k], s + k * bytes, bytes, hipMemcpyDeviceToHost, ctx->hstream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
     pending = false;
-    if (ctx->stage_host[slot]) std::memcpy(h, ctx->stage[slot], bytes);
+    if (ctx->stage_host[slot])
+      for (size_t k = 0; k < count; ++k) std::memcpy(h[k], s + k * bytes, bytes);
     return NFLHIP_OK;
+  }
+  int out(void *h, int slot, size_t bytes) { return outs(&h, 1, slot, bytes); }
+  int out2(void *h0, void *h1, int slot, size_t bytes) {
+    void *const h[2] = {h0, h1};
+    return outs(h, 2, slot, bytes);
   }
 };
 
@@ -441,56 +450,32 @@ int nflhip_moddown_ntt(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t ba
 }
 
 // hybrid key switching: in, the key and both outputs are staged whole (the outputs share one slot, out1 behind out0, so that the
-// mod-down runs as one batch)
-int nflhip_keyswitch_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_in, const void *h_key, size_t batch, size_t k_special,
-                         size_t alpha, int flags) {
-  int rc = keyswitch_check(ctx, h_out0, h_out1, h_in, h_key, batch, k_special, alpha, flags);
-  if (rc || batch == 0) return rc;
-  if ((rc = set_device(ctx))) return rc;
-  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * (nm - k_special) * row;
-  const size_t kb = 2 * keyswitch_digits(ctx, k_special, alpha) * nm * row;
-  Staged s(ctx);
-  if ((rc = s.in(0, h_in, ob)) || (rc = s.in(1, h_key, kb)) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
-  char *o = (char *)ctx->stage[2];
-  if ((rc = nflhip_keyswitch_ntt_dev(ctx, o, o + ob, ctx->stage[0], ctx->stage[1], batch, k_special, alpha, flags, (void *)ctx->hstream))) return rc;
-  if (!ctx->stage_host[2]) {
-    HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));
-    HIPCHK(ctx, hipMemcpyAsync(h_out1, o + ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
-  }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
-  s.pending = false;
-  if (ctx->stage_host[2]) {
-    std::memcpy(h_out0, o, ob);
-    std::memcpy(h_out1, o + ob, ob);
-  }
-  return NFLHIP_OK;
-}
-
-// the same at a level: the operands have `level` rows, and of the key the digits that are read are staged (the outputs share one
-// slot, out1 behind out0, so that the mod-down runs as one batch)
-int nflhip_keyswitch_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_in, const void *h_key, size_t batch, size_t k_special,
-                               size_t alpha, size_t level, int flags) {
-  int rc = level_check(ctx, k_special, level, "keyswitch");
-  if (!rc) rc = keyswitch_check(ctx, h_out0, h_out1, h_in, h_key, batch, k_special, alpha, flags, level);
-  if (rc || batch == 0) return rc;
-  if ((rc = set_device(ctx))) return rc;
+// mod-down runs as one batch).  The body of both entries, the arguments checked: the operands have `level` rows (the top-level entry:
+// all nmoduli - k_special, where the level entry on the device forwards), and of the key the digits that are read are staged.
+static int keyswitch_host(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_in, const void *h_key, size_t batch, size_t k_special,
+                          size_t alpha, size_t level, int flags) {
+  int rc = set_device(ctx);
+  if (rc) return rc;
   const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * level * row;
   const size_t kb = 2 * keyswitch_level_digits(ctx, k_special, alpha, level) * nm * row;
   Staged s(ctx);
   if ((rc = s.in(0, h_in, ob)) || (rc = s.in(1, h_key, kb)) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
   char *o = (char *)ctx->stage[2];
   if ((rc = nflhip_keyswitch_level_ntt_dev(ctx, o, o + ob, ctx->stage[0], ctx->stage[1], batch, k_special, alpha, level, flags, (void *)ctx->hstream))) return rc;
-  if (!ctx->stage_host[2]) {
-    HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));
-    HIPCHK(ctx, hipMemcpyAsync(h_out1, o + ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
-  }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
-  s.pending = false;
-  if (ctx->stage_host[2]) {
-    std::memcpy(h_out0, o, ob);
-    std::memcpy(h_out1, o + ob, ob);
-  }
-  return NFLHIP_OK;
+  return s.out2(h_out0, h_out1, 2, ob);
+}
+int nflhip_keyswitch_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_in, const void *h_key, size_t batch, size_t k_special,
+                         size_t alpha, int flags) {
+  int rc = keyswitch_check(ctx, h_out0, h_out1, h_in, h_key, batch, k_special, alpha, flags);
+  if (rc || batch == 0) return rc;
+  return keyswitch_host(ctx, h_out0, h_out1, h_in, h_key, batch, k_special, alpha, ctx->shape.nm - k_special, flags);
+}
+int nflhip_keyswitch_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_in, const void *h_key, size_t batch, size_t k_special,
+                               size_t alpha, size_t level, int flags) {
+  int rc = level_check(ctx, k_special, level, "keyswitch");
+  if (!rc) rc = keyswitch_check(ctx, h_out0, h_out1, h_in, h_key, batch, k_special, alpha, flags, level);
+  if (rc || batch == 0) return rc;
+  return keyswitch_host(ctx, h_out0, h_out1, h_in, h_key, batch, k_special, alpha, level, flags);
 }
 
 // hoisted rotations: c1 (and c0 behind it), every key and every output are staged whole (the outputs share one slot, out0s then out1s)
@@ -504,7 +489,7 @@ int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const
   Staged s(ctx);
   if ((rc = s.in(0, nullptr, 2 * ob)) || (rc = s.in(1, nullptr, count * kb)) || (rc = s.in(2, nullptr, 2 * count * ob))) return rc;
   char *c = (char *)ctx->stage[0], *k = (char *)ctx->stage[1], *o = (char *)ctx->stage[2];
-  const bool hc = ctx->stage_host[0], hk = ctx->stage_host[1], ho = ctx->stage_host[2];
+  const bool hc = ctx->stage_host[0], hk = ctx->stage_host[1];
   if (hc) std::memcpy(c, h_c1, ob);
   else HIPCHK(ctx, hipMemcpyAsync(c, h_c1, ob, hipMemcpyHostToDevice, ctx->hstream));
   if (h_c0 && hc) std::memcpy(c + ob, h_c0, ob);
@@ -520,19 +505,12 @@ int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const
   }
   if ((rc = nflhip_rotate_hoisted_ntt_dev(ctx, o0, o1, h_c0 ? c + ob : nullptr, c, keys, ks, count, batch, k_special, alpha, flags, (void *)ctx->hstream)))
     return rc;
-  if (!ho)
-    for (size_t m = 0; m < count; ++m) {
-      HIPCHK(ctx, hipMemcpyAsync(h_out0s[m], o0[m], ob, hipMemcpyDeviceToHost, ctx->hstream));
-      HIPCHK(ctx, hipMemcpyAsync(h_out1s[m], o1[m], ob, hipMemcpyDeviceToHost, ctx->hstream));
-    }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
-  s.pending = false;
-  if (ho)
-    for (size_t m = 0; m < count; ++m) {
-      std::memcpy(h_out0s[m], o0[m], ob);
-      std::memcpy(h_out1s[m], o1[m], ob);
-    }
-  return NFLHIP_OK;
+  void *hs[2 * NFLHIP_ROTATE_MAX_OUTPUTS];  // as the slot holds them: out0s, then out1s
+  for (size_t m = 0; m < count; ++m) {
+    hs[m] = h_out0s[m];
+    hs[count + m] = h_out1s[m];
+  }
+  return s.outs(hs, 2 * count, 2, ob);
 }
 
 // weighted sums of automorphisms: every input, every weight and the output (the addend copied into it) are staged whole
@@ -586,17 +564,7 @@ int nflhip_lintrans_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void 
   }
   if ((rc = nflhip_lintrans_ntt_dev(ctx, o, o + ob, h_c0 ? c + ob : nullptr, c, keys, ws, ks, count, batch, k_special, alpha, flags, (void *)ctx->hstream)))
     return rc;
-  if (!ctx->stage_host[2]) {
-    HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));
-    HIPCHK(ctx, hipMemcpyAsync(h_out1, o + ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
-  }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
-  s.pending = false;
-  if (ctx->stage_host[2]) {
-    std::memcpy(h_out0, o, ob);
-    std::memcpy(h_out1, o + ob, ob);
-  }
-  return NFLHIP_OK;
+  return s.out2(h_out0, h_out1, 2, ob);
 }
 
 // the tensor product: the inputs share one slot (a0, a1, then b0, b1 unless it is the square), the three outputs another
@@ -618,57 +586,17 @@ int nflhip_tensor_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, void *h_out2,
                                   (void *)ctx->hstream)))
     return rc;
   void *const hout[3] = {h_out0, h_out1, h_out2};
-  if (!ctx->stage_host[2])
-    for (size_t k = 0; k < 3; ++k) HIPCHK(ctx, hipMemcpyAsync(hout[k], o + k * ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
-  s.pending = false;
-  if (ctx->stage_host[2])
-    for (size_t k = 0; k < 3; ++k) std::memcpy(hout[k], o + k * ob, ob);
-  return NFLHIP_OK;
+  return s.outs(hout, 3, 2, ob);
 }
 
 // ciphertext multiplication: the inputs (one slot), the key and both outputs are staged whole (the outputs share one slot, out1
-// behind out0, so that the mod-down runs as one batch)
-int nflhip_mulrelin_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0, const void *h_b1,
-                        const void *h_key, size_t batch, size_t k_special, size_t alpha, int flags) {
-  int rc = mulrelin_check(ctx, h_out0, h_out1, h_a0, h_a1, h_b0, h_b1, h_key, batch, k_special, alpha, flags);
-  if (rc || batch == 0) return rc;
-  if ((rc = set_device(ctx))) return rc;
-  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ib = batch * (nm - k_special) * row;
-  const size_t ob = (flags & NFLHIP_MULRELIN_RESCALE) ? ib - batch * row : ib, nin = h_b0 ? 4 : 2;
-  const size_t kb = 2 * keyswitch_digits(ctx, k_special, alpha) * nm * row;
-  Staged s(ctx);
-  if ((rc = s.in(0, nullptr, nin * ib)) || (rc = s.in(1, h_key, kb)) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
-  char *i = (char *)ctx->stage[0], *o = (char *)ctx->stage[2];
-  const void *const hin[4] = {h_a0, h_a1, h_b0, h_b1};
-  for (size_t k = 0; k < nin; ++k) {
-    if (ctx->stage_host[0]) std::memcpy(i + k * ib, hin[k], ib);
-    else HIPCHK(ctx, hipMemcpyAsync(i + k * ib, hin[k], ib, hipMemcpyHostToDevice, ctx->hstream));
-  }
-  if ((rc = nflhip_mulrelin_ntt_dev(ctx, o, o + ob, i, i + ib, h_b0 ? i + 2 * ib : nullptr, h_b0 ? i + 3 * ib : nullptr, ctx->stage[1], batch, k_special,
-                                    alpha, flags, (void *)ctx->hstream)))
-    return rc;
-  if (!ctx->stage_host[2]) {
-    HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));
-    HIPCHK(ctx, hipMemcpyAsync(h_out1, o + ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
-  }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
-  s.pending = false;
-  if (ctx->stage_host[2]) {
-    std::memcpy(h_out0, o, ob);
-    std::memcpy(h_out1, o + ob, ob);
-  }
-  return NFLHIP_OK;
-}
-
-// the same at a level: the operands have `level` rows, and of the key the digits that are read are staged (the outputs share one
-// slot, out1 behind out0, so that the mod-down runs as one batch)
-int nflhip_mulrelin_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0, const void *h_b1,
-                              const void *h_key, size_t batch, size_t k_special, size_t alpha, size_t level, int flags) {
-  int rc = level_check(ctx, k_special, level, "mulrelin");
-  if (!rc) rc = mulrelin_check(ctx, h_out0, h_out1, h_a0, h_a1, h_b0, h_b1, h_key, batch, k_special, alpha, flags, level);
-  if (rc || batch == 0) return rc;
-  if ((rc = set_device(ctx))) return rc;
+// behind out0, so that the mod-down runs as one batch).  The body of both entries, the arguments checked: the operands have `level`
+// rows (the top-level entry: all nmoduli - k_special, where the level entry on the device forwards), and of the key the digits that
+// are read are staged.
+static int mulrelin_host(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0, const void *h_b1,
+                         const void *h_key, size_t batch, size_t k_special, size_t alpha, size_t level, int flags) {
+  int rc = set_device(ctx);
+  if (rc) return rc;
   const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ib = batch * level * row;
   const size_t ob = (flags & NFLHIP_MULRELIN_RESCALE) ? ib - batch * row : ib, nin = h_b0 ? 4 : 2;
   const size_t kb = 2 * keyswitch_level_digits(ctx, k_special, alpha, level) * nm * row;
@@ -683,17 +611,20 @@ int nflhip_mulrelin_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const
   if ((rc = nflhip_mulrelin_level_ntt_dev(ctx, o, o + ob, i, i + ib, h_b0 ? i + 2 * ib : nullptr, h_b0 ? i + 3 * ib : nullptr, ctx->stage[1], batch, k_special,
                                           alpha, level, flags, (void *)ctx->hstream)))
     return rc;
-  if (!ctx->stage_host[2]) {
-    HIPCHK(ctx, hipMemcpyAsync(h_out0, o, ob, hipMemcpyDeviceToHost, ctx->hstream));
-    HIPCHK(ctx, hipMemcpyAsync(h_out1, o + ob, ob, hipMemcpyDeviceToHost, ctx->hstream));
-  }
-  HIPCHK(ctx, hipStreamSynchronize(ctx->hstream));
-  s.pending = false;
-  if (ctx->stage_host[2]) {
-    std::memcpy(h_out0, o, ob);
-    std::memcpy(h_out1, o + ob, ob);
-  }
-  return NFLHIP_OK;
+  return s.out2(h_out0, h_out1, 2, ob);
+}
+int nflhip_mulrelin_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0, const void *h_b1,
+                        const void *h_key, size_t batch, size_t k_special, size_t alpha, int flags) {
+  int rc = mulrelin_check(ctx, h_out0, h_out1, h_a0, h_a1, h_b0, h_b1, h_key, batch, k_special, alpha, flags);
+  if (rc || batch == 0) return rc;
+  return mulrelin_host(ctx, h_out0, h_out1, h_a0, h_a1, h_b0, h_b1, h_key, batch, k_special, alpha, ctx->shape.nm - k_special, flags);
+}
+int nflhip_mulrelin_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0, const void *h_b1,
+                              const void *h_key, size_t batch, size_t k_special, size_t alpha, size_t level, int flags) {
+  int rc = level_check(ctx, k_special, level, "mulrelin");
+  if (!rc) rc = mulrelin_check(ctx, h_out0, h_out1, h_a0, h_a1, h_b0, h_b1, h_key, batch, k_special, alpha, flags, level);
+  if (rc || batch == 0) return rc;
+  return mulrelin_host(ctx, h_out0, h_out1, h_a0, h_a1, h_b0, h_b1, h_key, batch, k_special, alpha, level, flags);
 }
 
 // sums of products across polynomials: the operands are `terms` times the size of the result, so the call is staged whole

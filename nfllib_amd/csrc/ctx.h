@@ -18,6 +18,19 @@ namespace nflhip {
 int set_error(int code, const std::string &msg);  // api.hip: the calling thread's nflhip_last_error text
 }
 
+// A context-owned device buffer that calls on any stream share (api.hip ws_begin / ws_end / ws_free): it grows on demand, never while
+// capturing, and successive calls are ordered on it by an event that is recorded and waited on outside any capture.
+struct Workspace {
+  void *buf = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;
+  bool ev_valid = false;
+};
+// What a call while capturing may repeat (api.hip warm_covers / warm_note): per (k_special, alpha, plan | modes) the largest sizes
+// served so far outside a capture -- up to three per family, the unused ones 0.
+typedef std::map<std::array<size_t, 3>, std::array<size_t, 3>> WarmMap;
+typedef std::map<std::array<size_t, 2>, struct nflhip_ctx *> ChildMap;
+
 struct nflhip_ctx {
   int device = 0;
   nflhip::Shape shape{};
@@ -64,71 +77,53 @@ struct nflhip_ctx {
   std::mutex row_mu;
   std::vector<nflhip_ctx *> row_ctx;  // [2 * cm + inverse_tables]
   // composed NTT-form rescale (api.hip rescale_composed): child contexts over the last modulus alone and over the first nm - 1,
-  // created on first use, and the scratch that holds the inverse-transformed dropped rows; calls are ordered on it by ev_resc
+  // created on first use, never while capturing, and the workspace that holds the inverse-transformed dropped rows.  Under resc_mu.
   std::mutex resc_mu;
   nflhip_ctx *resc_last = nullptr, *resc_kept = nullptr;
-  void *resc_scratch = nullptr;
-  size_t resc_scratch_bytes = 0;
-  hipEvent_t ev_resc = nullptr;
-  bool ev_resc_valid = false;
+  Workspace resc_ws;
   // RNS base conversion / mod-down (api.hip baseconv_record): the device record of every pair of row ranges used so far, keyed by
   // (s0, ks, d0, kd, moddown); built and uploaded on first use under bconv_mu, freed with the context
   std::mutex bconv_mu;
   std::map<std::array<size_t, 5>, void *> bconv;
   // composed NTT-form base conversion / mod-down (api.hip baseconv_ntt_composed): child contexts over row ranges of this one,
-  // keyed by (first row, count) and created on first use; scratch 0 holds the gathered source rows [batch][ks][n], scratch 1 the
-  // converted rows of a destination range that is not the whole context; calls are ordered on both by ev_bcn.  All under bcn_mu.
+  // keyed by (first row, count) and created on first use; workspace 0 holds the gathered source rows [batch][ks][n], workspace 1 the
+  // converted rows of a destination range that is not the whole context; calls are ordered on both by the event of workspace 0 (the
+  // event of workspace 1 is never created).  All under bcn_mu.
   std::mutex bcn_mu;
-  std::map<std::array<size_t, 2>, nflhip_ctx *> bcn_child;
+  ChildMap bcn_child;
+  Workspace bcn_ws[2];
   // leveled key switching / multiplication (api.hip level_child): the context over the rows [0, level) and [nm - k_special, nm) of
   // this one, keyed by (k_special, level), created on first use, never while capturing, destroyed with this context; its records,
-  // scratch, events and warm maps are its own.  Under bcn_mu.
-  std::map<std::array<size_t, 2>, nflhip_ctx *> lvl_child;
-  void *bcn_scratch[2] = {nullptr, nullptr};
-  size_t bcn_scratch_bytes[2] = {0, 0};
-  hipEvent_t ev_bcn = nullptr;
-  bool ev_bcn_valid = false;
-  // hybrid key switching (api.hip keyswitch_run): per (k_special, alpha) the device array of its digits' record pointers; per
-  // (k_special, alpha, plan) the largest batch served so far (what a call while capturing may repeat); one scratch for the embedded /
-  // inverse-transformed input, the mod-upped digits and the two sums, calls ordered on it by ev_ks.  All under ks_mu.
+  // workspaces and warm maps are its own.  Under bcn_mu.
+  ChildMap lvl_child;
+  // hybrid key switching (api.hip keyswitch_run): per (k_special, alpha) the device array of its digits' record pointers; the warm
+  // map's size is the batch; one workspace for the embedded / inverse-transformed input, the mod-upped digits and the two sums.  All
+  // under ks_mu.
   std::mutex ks_mu;
   std::map<std::array<size_t, 2>, void *> ks_recs;
-  std::map<std::array<size_t, 3>, size_t> ks_warm;
-  void *ks_scratch = nullptr;
-  size_t ks_scratch_bytes = 0;
-  hipEvent_t ev_ks = nullptr;
-  bool ev_ks_valid = false;
-  // hoisted rotations (api.hip rotate_run): per (k_special, alpha, plan | modes) the largest batch and the largest count * batch served
-  // so far (what a call while capturing may repeat); one scratch for the mod-up's input, the digits, the sums and the mod-down's
-  // result (the sequence: one key switch's two results), calls ordered on it by ev_rot.  All under rot_mu, which is taken BEFORE
-  // ks_mu and bcn_mu.
+  WarmMap ks_warm;
+  Workspace ks_ws;
+  // hoisted rotations (api.hip rotate_run): the warm map's sizes are the batch and count * batch; one workspace for the mod-up's
+  // input, the digits, the sums and the mod-down's result (the sequence: one key switch's two results).  All under rot_mu, which is
+  // taken BEFORE ks_mu and bcn_mu.
   std::mutex rot_mu;
-  std::map<std::array<size_t, 3>, std::array<size_t, 2>> rot_warm;
-  void *rot_scratch = nullptr;
-  size_t rot_scratch_bytes = 0;
-  hipEvent_t ev_rot = nullptr;
-  bool ev_rot_valid = false;
-  // slot linear transforms (api.hip lintrans_run): per (k_special, alpha, plan | modes) the largest batch, the largest keyed * batch and
-  // the largest mod-down served so far (what a call while capturing may repeat); one scratch for the mod-up's input, the digits, the
-  // key-switch sums and the two accumulated sums, calls ordered on it by ev_lt.  All under lt_mu, which is taken BEFORE ks_mu and bcn_mu.
+  WarmMap rot_warm;
+  Workspace rot_ws;
+  // slot linear transforms (api.hip lintrans_run): the warm map's sizes are the batch, keyed * batch and the polynomials of one
+  // mod-down call; one workspace for the mod-up's input, the digits, the key-switch sums and the two accumulated sums.  All under
+  // lt_mu, which is taken BEFORE ks_mu and bcn_mu.
   std::mutex lt_mu;
-  std::map<std::array<size_t, 3>, std::array<size_t, 3>> lt_warm;
-  void *lt_scratch = nullptr;
-  size_t lt_scratch_bytes = 0;
-  hipEvent_t ev_lt = nullptr;
-  bool ev_lt_valid = false;
+  WarmMap lt_warm;
+  Workspace lt_ws;
   // ciphertext multiplication (api.hip mulrelin_run): per k_special one device block -- nm pairs (pi_j = P mod p_j, its Shoup
   // companion; zeros on the special rows), then the constant polynomial [nm][n] that holds pi_j in every word of row j (the
-  // sequence's one-term dot) -- built on the host at the first call for that k_special; per (k_special, alpha, plan | modes) the
-  // largest batch served so far (what a call while capturing may repeat); one scratch for the tensor's components, the mod-up's
-  // input, the digits and the two sums, calls ordered on it by ev_mr.  All under mr_mu, which is taken BEFORE ks_mu and bcn_mu.
+  // sequence's one-term dot) -- built on the host at the first call for that k_special; the warm map's size is the batch; one
+  // workspace for the tensor's components, the mod-up's input, the digits and the two sums.  All under mr_mu, which is taken BEFORE
+  // ks_mu and bcn_mu.
   std::mutex mr_mu;
   std::map<size_t, void *> mr_pi;
-  std::map<std::array<size_t, 3>, size_t> mr_warm;
-  void *mr_scratch = nullptr;
-  size_t mr_scratch_bytes = 0;
-  hipEvent_t ev_mr = nullptr;
-  bool ev_mr_valid = false;
+  WarmMap mr_warm;
+  Workspace mr_ws;
 };
 
 void pipe_destroy(nflhip_ctx *ctx);  // api_host.hip: frees the context's host-pointer pipeline
@@ -306,19 +301,31 @@ inline int level_check(const nflhip_ctx *ctx, size_t k_special, size_t level, co
   if (level == 0 || level > ctx->shape.nm - k_special) return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": the level is out of range (1 to nmoduli - k_special)");
   return NFLHIP_OK;
 }
+// The head of the checks of the four entries over a (k_special, alpha) key (`what`): the context, the flag bits against the entry's
+// plan and mode masks, one plan flag at most, then -- where the entry counts keys -- `count_error`, the message of a count out of
+// range (NULL: in range), then k_special, alpha and the rows.
+inline int keyswitch_family_check(const nflhip_ctx *ctx, const char *what, int flags, int plans, int modes, const char *count_error,
+                                  size_t k_special, size_t alpha) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  const std::string w(what);
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, w + ": a cyclic row context has no modulus chain");
+  const int plan = flags & plans;
+  if (flags & ~(plans | modes)) return fail(ctx, NFLHIP_ERR_INVALID, w + ": unknown flag bits");
+  if (plan & (plan - 1)) return fail(ctx, NFLHIP_ERR_INVALID, w + ": one plan flag at most");
+  if (count_error) return fail(ctx, NFLHIP_ERR_INVALID, count_error);
+  const size_t nm = ctx->shape.nm;
+  if (k_special == 0 || k_special >= nm) return fail(ctx, NFLHIP_ERR_INVALID, w + ": k_special is out of range (1 to nmoduli - 1)");
+  if (keyswitch_digits(ctx, k_special, alpha) == 0) return fail(ctx, NFLHIP_ERR_INVALID, w + ": alpha is out of range (1 to nmoduli - k_special)");
+  if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, w + ": more than 65535 rows");
+  return NFLHIP_OK;
+}
 // (level: the operands' rows and the digits of a call below the top level, 1 <= level <= L checked by level_check; 0: the top level)
 inline int keyswitch_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *in, const void *key, size_t batch,
                            size_t k_special, size_t alpha, int flags, size_t level = 0) {
-  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
-  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: a cyclic row context has no modulus chain");
-  const int plans = NFLHIP_KEYSWITCH_COMPOSED | NFLHIP_KEYSWITCH_FUSED | NFLHIP_KEYSWITCH_SEQUENCE, plan = flags & plans;
-  if (flags & ~(plans | NFLHIP_KEYSWITCH_CENTERED | NFLHIP_KEYSWITCH_FLOOR)) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: unknown flag bits");
-  if (plan & (plan - 1)) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: one plan flag at most");
+  int rc = keyswitch_family_check(ctx, "keyswitch", flags, NFLHIP_KEYSWITCH_COMPOSED | NFLHIP_KEYSWITCH_FUSED | NFLHIP_KEYSWITCH_SEQUENCE,
+                                  NFLHIP_KEYSWITCH_CENTERED | NFLHIP_KEYSWITCH_FLOOR, nullptr, k_special, alpha);
+  if (rc || batch == 0) return rc;
   const size_t nm = ctx->shape.nm, dnum = keyswitch_digits(ctx, k_special, alpha);
-  if (k_special == 0 || k_special >= nm) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: k_special is out of range (1 to nmoduli - 1)");
-  if (dnum == 0) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: alpha is out of range (1 to nmoduli - k_special)");
-  if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "keyswitch: more than 65535 rows");
-  if (batch == 0) return NFLHIP_OK;
   if (!out0 || !out1 || !in || !key) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
   const size_t row = ctx->shape.n * ctx->word, L = level ? level : nm - k_special, kd = level ? (level + alpha - 1) / alpha : dnum;
   size_t ob, sb, kb, polys;
@@ -367,17 +374,11 @@ inline int dot_multi_check(const nflhip_ctx *ctx, void *const *outs, const nflhi
 // their builder, api.hip keyswitch_records), before any device use
 inline int rotate_check(const nflhip_ctx *ctx, void *const *out0s, void *const *out1s, const void *c0, const void *c1, const void *const *keys,
                         const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
-  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
-  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: a cyclic row context has no modulus chain");
-  const int plans = NFLHIP_ROTATE_SEQUENCE | NFLHIP_ROTATE_HOISTED, plan = flags & plans;
-  if (flags & ~(plans | NFLHIP_ROTATE_CENTERED | NFLHIP_ROTATE_FLOOR)) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: unknown flag bits");
-  if (plan == plans) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: one plan flag at most");
-  if (count == 0 || count > NFLHIP_ROTATE_MAX_OUTPUTS) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: the number of rotations is out of range (1 to 16)");
+  int rc = keyswitch_family_check(ctx, "rotate", flags, NFLHIP_ROTATE_SEQUENCE | NFLHIP_ROTATE_HOISTED, NFLHIP_ROTATE_CENTERED | NFLHIP_ROTATE_FLOOR,
+                                  count == 0 || count > NFLHIP_ROTATE_MAX_OUTPUTS ? "rotate: the number of rotations is out of range (1 to 16)" : nullptr,
+                                  k_special, alpha);
+  if (rc || batch == 0) return rc;
   const size_t nm = ctx->shape.nm, dnum = keyswitch_digits(ctx, k_special, alpha);
-  if (k_special == 0 || k_special >= nm) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: k_special is out of range (1 to nmoduli - 1)");
-  if (dnum == 0) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: alpha is out of range (1 to nmoduli - k_special)");
-  if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: more than 65535 rows");
-  if (batch == 0) return NFLHIP_OK;
   if (!ks) return fail(ctx, NFLHIP_ERR_INVALID, "NULL multiplier array");
   for (size_t m = 0; m < count; ++m)
     if ((ks[m] & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "rotate: the exponent k must be odd");
@@ -429,17 +430,11 @@ inline int mac_check(const nflhip_ctx *ctx, const void *out, const void *addend,
 // builder, api.hip keyswitch_records), before any device use
 inline int lintrans_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *c0, const void *c1, const void *const *keys,
                           const void *const *weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
-  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
-  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: a cyclic row context has no modulus chain");
-  const int plans = NFLHIP_LINTRANS_SEQUENCE | NFLHIP_LINTRANS_HOISTED, plan = flags & plans;
-  if (flags & ~(plans | NFLHIP_LINTRANS_CENTERED | NFLHIP_LINTRANS_FLOOR)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: unknown flag bits");
-  if (plan == plans) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: one plan flag at most");
-  if (count == 0 || count > NFLHIP_LINTRANS_MAX_TERMS) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: the number of terms is out of range (1 to 16)");
+  int rc = keyswitch_family_check(ctx, "lintrans", flags, NFLHIP_LINTRANS_SEQUENCE | NFLHIP_LINTRANS_HOISTED, NFLHIP_LINTRANS_CENTERED | NFLHIP_LINTRANS_FLOOR,
+                                  count == 0 || count > NFLHIP_LINTRANS_MAX_TERMS ? "lintrans: the number of terms is out of range (1 to 16)" : nullptr,
+                                  k_special, alpha);
+  if (rc || batch == 0) return rc;
   const size_t nm = ctx->shape.nm, dnum = keyswitch_digits(ctx, k_special, alpha);
-  if (k_special == 0 || k_special >= nm) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: k_special is out of range (1 to nmoduli - 1)");
-  if (dnum == 0) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: alpha is out of range (1 to nmoduli - k_special)");
-  if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: more than 65535 rows");
-  if (batch == 0) return NFLHIP_OK;
   if (!ks) return fail(ctx, NFLHIP_ERR_INVALID, "NULL multiplier array");
   for (size_t m = 0; m < count; ++m)
     if ((ks[m] & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: the exponent k must be odd");
@@ -493,16 +488,10 @@ inline int tensor_check(const nflhip_ctx *ctx, const void *out0, const void *out
 // builder, api.hip keyswitch_records), before any device use
 inline int mulrelin_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *a0, const void *a1, const void *b0,
                           const void *b1, const void *key, size_t batch, size_t k_special, size_t alpha, int flags, size_t level = 0) {
-  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
-  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: a cyclic row context has no modulus chain");
-  const int plans = NFLHIP_MULRELIN_SEQUENCE | NFLHIP_MULRELIN_MERGED | NFLHIP_MULRELIN_FUSED, plan = flags & plans;
-  if (flags & ~(plans | NFLHIP_MULRELIN_CENTERED | NFLHIP_MULRELIN_FLOOR | NFLHIP_MULRELIN_RESCALE))
-    return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: unknown flag bits");
-  if (plan & (plan - 1)) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: one plan flag at most");
+  int rc = keyswitch_family_check(ctx, "mulrelin", flags, NFLHIP_MULRELIN_SEQUENCE | NFLHIP_MULRELIN_MERGED | NFLHIP_MULRELIN_FUSED,
+                                  NFLHIP_MULRELIN_CENTERED | NFLHIP_MULRELIN_FLOOR | NFLHIP_MULRELIN_RESCALE, nullptr, k_special, alpha);
+  if (rc) return rc;
   const size_t nm = ctx->shape.nm, dnum = keyswitch_digits(ctx, k_special, alpha);
-  if (k_special == 0 || k_special >= nm) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: k_special is out of range (1 to nmoduli - 1)");
-  if (dnum == 0) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: alpha is out of range (1 to nmoduli - k_special)");
-  if (nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: more than 65535 rows");
   // (level: as keyswitch_check)
   const size_t row = ctx->shape.n * ctx->word, L = level ? level : nm - k_special, kd = level ? (level + alpha - 1) / alpha : dnum;
   if ((flags & NFLHIP_MULRELIN_RESCALE) && L < 2)

@@ -235,6 +235,65 @@ def test_graph_capture_replays_identically(engine_factory, oracle_factory):
         assert np.array_equal(e.to_host(y), want_n)
 
 
+@pytest.mark.parametrize("compiled,n,nm", [(True, 64, 3), (False, 4096, 2)])
+def test_two_streams_share_the_composed_plans_scratch(compiled, n, nm, engine_factory, compiled_engine_factory, oracle_factory):
+    """the NTT form's default plan composes on both contexts -- a compiled one at any degree, a default one from rows of 32 KiB on --
+    so calls alternating between two streams share the one scratch and its event"""
+    import torch
+    e = (compiled_engine_factory if compiled else engine_factory)(64, n, nm)
+    big, small = oracle_factory(64, n, nm), oracle_factory(64, n, nm - 1)
+    a, b = random_batch(e.P, n, 2, e.np_dtype, 31), random_batch(e.P, n, 2, e.np_dtype, 32)
+    wa, wb = small.ntt(rescale_rns(a, e.P)), small.ntt(rescale_rns(b, e.P))
+    dA, dB = e.to_device(big.ntt(a)), e.to_device(big.ntt(b))
+    ya = torch.zeros((2, nm - 1, n), dtype=torch.int64, device="cuda:0")
+    yb = torch.zeros_like(ya)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    for _ in range(3):
+        e.rescale(dA, ntt=True, out=ya, stream=s1)
+        e.rescale(dB, ntt=True, out=yb, stream=s2)
+    torch.cuda.synchronize()
+    assert np.array_equal(e.to_host(ya), wa) and np.array_equal(e.to_host(yb), wb)
+
+
+def test_first_composed_call_while_capturing_is_refused_and_the_stream_stays_usable(oracle_factory):
+    import ctypes as C
+    import torch
+    from nfllib_amd import Engine, _lib
+    saved = os.environ.get("NFLHIP_VARIANT")
+    os.environ["NFLHIP_VARIANT"] = "hipcc"
+    try:
+        e = Engine(64, 64, 3, device=0)                        # a context of its own: no child context, no scratch yet
+    finally:
+        if saved is None:
+            os.environ.pop("NFLHIP_VARIANT", None)
+        else:
+            os.environ["NFLHIP_VARIANT"] = saved
+    try:
+        a = random_batch(e.P, 64, 2, e.np_dtype, 33)
+        want = oracle_factory(64, 64, 2).ntt(rescale_rns(a, e.P))
+        dA = e.to_device(oracle_factory(64, 64, 3).ntt(a))
+        y = torch.full((2, 2, 64), 7, dtype=torch.int64, device="cuda:0")
+        z = torch.zeros(4, device="cuda:0")
+        st = torch.cuda.Stream()
+        sp = C.c_void_p(st.cuda_stream)
+        resc = _lib.lib.nflhip_rescale_dev
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(st):
+            with torch.cuda.graph(g, stream=st):
+                z.add_(1)
+                rc = resc(e.ctx, y.data_ptr(), dA.data_ptr(), 2, _lib.FORM_NTT, sp)
+        torch.cuda.synchronize()
+        assert rc == _lib.ERR_UNSUPPORTED
+        assert (e.to_host(y) == 7).all()                       # nothing was enqueued
+        assert resc(e.ctx, y.data_ptr(), dA.data_ptr(), 2, _lib.FORM_NTT, sp) == 0      # the same stream, after the capture
+        st.synchronize()
+        assert np.array_equal(e.to_host(y), want)
+    finally:
+        e.close()
+
+
 @pytest.fixture(scope="module")
 def cpp_programs(tmp_path_factory):
     from test_rescale_cpu import build_cpp
