@@ -351,6 +351,81 @@ template <class P> class device_batch {
                                                            P::nmoduli, flags, key.queue()), "mul_relin_level_ntt");
     key.sync();
   }
+  // Hoisted rotations and slot linear transforms at a level (include/nflhip.h "rotations and linear transforms at a level"): this
+  // ring's moduli count is the level Lv; key_batches[m] is a batch of the ring with M moduli holding the 2 dnum_L polynomials of the ONE
+  // top-level Galois key of rotation m (NULL: the unrotated diagonal of a linear transform), weight_batches[m] one holding the ONE
+  // top-level diagonal.  The last K moduli of the keys' ring are the special ones, K explicit as in nfl::rotate_hoisted_level_ntt<K>;
+  // Lv <= M - K is checked at compile time.  Streams as in assign_rotations / assign_linear_transform.
+  template <size_t K, class Q>
+  static void assign_rotations_level(device_batch *const *out0s, device_batch *const *out1s, const device_batch *c0, const device_batch &c1,
+                                     const device_batch<Q> *const *key_batches, const uint64_t *ks, size_t count, size_t alpha, bool centered = false,
+                                     bool floor = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && K >= 1 && K < Q::nmoduli &&
+                      P::nmoduli <= Q::nmoduli - K,
+                  "assign_rotations_level: the keys' ring has the same limbs and degree, K special moduli and at least Lv others");
+    if (alpha == 0 || alpha > Q::nmoduli - K) throw std::runtime_error("nfl(hip): rotations_level: alpha is out of range (1 to the keys' ordinary moduli)");
+    if (count == 0 || count > NFLHIP_ROTATE_MAX_OUTPUTS) throw std::runtime_error("nfl(hip): rotations_level: 1 to 16 rotations");
+    const device_batch<Q> &key0 = *key_batches[0];
+    void *o0[NFLHIP_ROTATE_MAX_OUTPUTS], *o1[NFLHIP_ROTATE_MAX_OUTPUTS];
+    const void *kp[NFLHIP_ROTATE_MAX_OUTPUTS];
+    if (c0 && c0->size() != c1.size()) throw std::runtime_error("nfl(hip): batch sizes differ");
+    if ((c0 && c0->device() != key0.device()) || c1.device() != key0.device()) throw std::runtime_error("nfl(hip): rotation operands on different devices");
+    for (size_t m = 0; m < count; ++m) {
+      if (out0s[m]->size() != c1.size() || out1s[m]->size() != c1.size()) throw std::runtime_error("nfl(hip): batch sizes differ");
+      if (key_batches[m]->size() != 2 * ((Q::nmoduli - K + alpha - 1) / alpha))
+        throw std::runtime_error("nfl(hip): a key batch holds the 2 * dnum polynomials of the top level");
+      if (out0s[m]->device() != key0.device() || out1s[m]->device() != key0.device() || key_batches[m]->device() != key0.device())
+        throw std::runtime_error("nfl(hip): rotation operands on different devices");
+      o0[m] = out0s[m]->d_;
+      o1[m] = out1s[m]->d_;
+      kp[m] = key_batches[m]->data();
+    }
+    c1.sync();
+    c1.strict("rotations_level");
+    if (c0) c0->strict("rotations_level");
+    for (size_t m = 0; m < count; ++m) key_batches[m]->strict("rotations_level");
+    const int flags = (centered ? NFLHIP_ROTATE_CENTERED : 0) | (floor ? NFLHIP_ROTATE_FLOOR : 0);
+    const void *const p0 = c0 ? c0->d_ : nullptr;
+    detail::check(key0.ctx(), nflhip_rotate_hoisted_level_ntt_dev(key0.ctx(), o0, o1, p0, c1.d_, kp, ks, count, c1.n_, K, alpha,
+                                                                  P::nmoduli, flags, key0.queue()), "rotate_hoisted_level_ntt");
+    key0.sync();
+  }
+  template <size_t K, class Q>
+  static void assign_linear_transform_level(device_batch &out0, device_batch &out1, const device_batch *c0, const device_batch &c1,
+                                            const device_batch<Q> *const *key_batches, const device_batch<Q> *const *weight_batches,
+                                            const uint64_t *ks, size_t count, size_t alpha, bool centered = false, bool floor = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && K >= 1 && K < Q::nmoduli &&
+                      P::nmoduli <= Q::nmoduli - K,
+                  "assign_linear_transform_level: the keys' ring has the same limbs and degree, K special moduli and at least Lv others");
+    if (alpha == 0 || alpha > Q::nmoduli - K) throw std::runtime_error("nfl(hip): linear transform level: alpha is out of range (1 to the keys' ordinary moduli)");
+    if (count == 0 || count > NFLHIP_LINTRANS_MAX_TERMS) throw std::runtime_error("nfl(hip): linear transform level: 1 to 16 terms");
+    const device_batch<Q> &w0 = *weight_batches[0];
+    const void *kp[NFLHIP_LINTRANS_MAX_TERMS], *wp[NFLHIP_LINTRANS_MAX_TERMS];
+    if ((c0 && c0->size() != c1.size()) || out0.size() != c1.size() || out1.size() != c1.size()) throw std::runtime_error("nfl(hip): batch sizes differ");
+    if ((c0 && c0->device() != w0.device()) || c1.device() != w0.device() || out0.device() != w0.device() || out1.device() != w0.device())
+      throw std::runtime_error("nfl(hip): linear transform operands on different devices");
+    for (size_t m = 0; m < count; ++m) {
+      if (key_batches[m] && key_batches[m]->size() != 2 * ((Q::nmoduli - K + alpha - 1) / alpha))
+        throw std::runtime_error("nfl(hip): a key batch holds the 2 * dnum polynomials of the top level");
+      if (weight_batches[m]->size() != 1) throw std::runtime_error("nfl(hip): a weight batch holds one polynomial");
+      if ((key_batches[m] && key_batches[m]->device() != w0.device()) || weight_batches[m]->device() != w0.device())
+        throw std::runtime_error("nfl(hip): linear transform operands on different devices");
+      kp[m] = key_batches[m] ? key_batches[m]->data() : nullptr;
+      wp[m] = (*weight_batches[m]).data();
+    }
+    c1.sync();
+    c1.strict("linear transform level");
+    if (c0) c0->strict("linear transform level");
+    for (size_t m = 0; m < count; ++m) {
+      if (key_batches[m]) key_batches[m]->strict("linear transform level");
+      weight_batches[m]->strict("linear transform level");
+    }
+    const int flags = (centered ? NFLHIP_LINTRANS_CENTERED : 0) | (floor ? NFLHIP_LINTRANS_FLOOR : 0);
+    const void *const p0 = c0 ? c0->d_ : nullptr;
+    detail::check(w0.ctx(), nflhip_lintrans_level_ntt_dev(w0.ctx(), out0.d_, out1.d_, p0, c1.d_, kp, wp, ks, count, c1.n_, K, alpha,
+                                                          P::nmoduli, flags, w0.queue()), "linear_transform_level_ntt");
+    w0.sync();
+  }
   // Sums of products across polynomials (include/nflhip.h): this batch holds `groups` polynomials, a and b groups * terms each,
   // term-minor: (*this)[g] = sum_j a[g * terms + j] * b[g * terms + j].  assign_matvec: v holds the `terms` polynomials every
   // group shares, (*this)[g] = sum_j m[g * terms + j] * v[j].  The operands must be other batches.

@@ -579,6 +579,116 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out1._p = d1;
   }
 
+  // Hoisted rotations and slot linear transforms at a level (nfl::rotate_hoisted_level_ntt<K> / linear_transform_level_ntt<K> below;
+  // include/nflhip.h "rotations and linear transforms at a level").  This ring type is the KEYS' and the diagonals': NbModuli moduli,
+  // the last K special -- explicit, as in key_switch_level_into.  c0, c1 and the outputs live in the ring with LO <= NbModuli - K
+  // moduli, the level.  keys[m] is the ONE top-level Galois key of rotation m, 2 dnum_L polynomials [term][component], of which only
+  // the 2 dnum_l LIVE ones, dnum_l = ceil(LO / alpha), are touched and gathered -- whole polynomials of this ring, so that the entry
+  // finds phys(r) itself; a live polynomial that is empty (moved from) is refused, a dead one is never looked at.  weights[m] is one
+  // whole polynomial of this ring, the top-level diagonal.  Buffer layouts, ordering, payloads and errors as rotate_into /
+  // linear_transform_into with dnum_l for dnum.  Never fused into a queue's rewrites.
+  template <size_t K, size_t LO> static void rotate_level_into(poly_p<T, Degree, LO> *out0s, poly_p<T, Degree, LO> *out1s,
+                                                               poly_p<T, Degree, LO> const *c0, poly_p<T, Degree, LO> const &c1,
+                                                               poly_p const *const *keys, const uint64_t *ks, size_t count, size_t alpha,
+                                                               bool centered, bool floor) {
+    static_assert(K >= 1 && K < NbModuli && LO >= 1 && LO <= NbModuli - K, "nfl::rotate_hoisted_level_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+    typedef poly_p<T, Degree, LO> out_t;
+    if (alpha == 0 || alpha > NbModuli - K) throw std::runtime_error("nfl(hip): rotate_hoisted_level_ntt: alpha is out of range (1 to the key ring's ordinary moduli)");
+    if (count == 0 || count > NFLHIP_ROTATE_MAX_OUTPUTS) throw std::runtime_error("nfl(hip): rotate_hoisted_level_ntt: 1 to 16 rotations");
+    const size_t rlive = 2 * ((LO + alpha - 1) / alpha), pb = sizeof(T) * Degree * NbModuli;
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    typename out_t::ptr_type s0 = c0 ? c0->_p : typename out_t::ptr_type(), s1 = c1._p;  // (hold the inputs while the launches are enqueued)
+    std::vector<typename out_t::ptr_type> d0, d1;
+    std::vector<ptr_type> held;  // (and the live key polynomials' payloads)
+    void *o0[NFLHIP_ROTATE_MAX_OUTPUTS], *o1[NFLHIP_ROTATE_MAX_OUTPUTS];
+    const void *kp[NFLHIP_ROTATE_MAX_OUTPUTS];
+    for (size_t m = 0; m < count; ++m) {
+      d0.push_back(out_t::fresh());
+      d1.push_back(out_t::fresh());
+      o0[m] = d0[m]->dev_wo();
+      o1[m] = d1[m]->dev_wo();
+      for (size_t t = 0; t < rlive; ++t) {
+        if (!keys[m][t]._p) throw std::runtime_error("nfl(hip): a live key polynomial is empty (moved from)");
+        held.push_back(keys[m][t]._p);
+      }
+    }
+    const void *p0 = c0 ? s0->dev_ro() : nullptr, *p1 = s1->dev_ro();
+    void *kgat = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &kgat, count * rlive * pb), "rotate_hoisted_level_ntt");
+    int rc = NFLHIP_OK;
+    for (size_t m = 0; m < count; ++m) {
+      kp[m] = static_cast<char *>(kgat) + m * rlive * pb;
+      for (size_t t = 0; t < rlive && rc == NFLHIP_OK; ++t)
+        rc = nflhip_memcpy_d2d(ctx_t::get(), static_cast<char *>(kgat) + (m * rlive + t) * pb, held[m * rlive + t]->dev_ro(), pb, ctx_t::queue());
+    }
+    if (rc == NFLHIP_OK) rc = nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue());
+    const int flags = (centered ? NFLHIP_ROTATE_CENTERED : 0) | (floor ? NFLHIP_ROTATE_FLOOR : 0);
+    if (rc == NFLHIP_OK) rc = nflhip_rotate_hoisted_level_ntt_dev(ctx_t::get(), o0, o1, p0, p1, kp, ks, count, 1, K, alpha, LO, flags, ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered keys go)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), kgat);
+      throw std::runtime_error("nfl(hip): rotate_hoisted_level_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), kgat);
+    detail::check(ctx_t::get(), rs, "rotate_hoisted_level_ntt");
+    for (size_t m = 0; m < count; ++m) {
+      out0s[m]._p = d0[m];
+      out1s[m]._p = d1[m];
+    }
+  }
+  template <size_t K, size_t LO> static void linear_transform_level_into(poly_p<T, Degree, LO> &out0, poly_p<T, Degree, LO> &out1,
+                                                                         poly_p<T, Degree, LO> const *c0, poly_p<T, Degree, LO> const &c1,
+                                                                         poly_p const *const *keys, poly_p const *const *weights, const uint64_t *ks,
+                                                                         size_t count, size_t alpha, bool centered, bool floor) {
+    static_assert(K >= 1 && K < NbModuli && LO >= 1 && LO <= NbModuli - K, "nfl::linear_transform_level_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+    typedef poly_p<T, Degree, LO> out_t;
+    if (alpha == 0 || alpha > NbModuli - K) throw std::runtime_error("nfl(hip): linear_transform_level_ntt: alpha is out of range (1 to the key ring's ordinary moduli)");
+    if (count == 0 || count > NFLHIP_LINTRANS_MAX_TERMS) throw std::runtime_error("nfl(hip): linear_transform_level_ntt: 1 to 16 terms");
+    const size_t tlive = 2 * ((LO + alpha - 1) / alpha), pb = sizeof(T) * Degree * NbModuli, tpolys = tlive + 1;
+    const size_t wbytes = pb;  // (a diagonal is a whole polynomial of this ring at every level: the entry reads its rows at phys(r))
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    typename out_t::ptr_type s0 = c0 ? c0->_p : typename out_t::ptr_type(), s1 = c1._p;  // (hold the inputs while the launches are enqueued)
+    typename out_t::ptr_type d0 = out_t::fresh(), d1 = out_t::fresh();
+    std::vector<ptr_type> held;  // (the live key polynomials' and the diagonals' payloads: tpolys slots per term, a NULL key's left empty)
+    for (size_t m = 0; m < count; ++m) {
+      for (size_t t = 0; t < tlive; ++t) {
+        if (keys[m] && !keys[m][t]._p) throw std::runtime_error("nfl(hip): a live key polynomial is empty (moved from)");
+        held.push_back(keys[m] ? keys[m][t]._p : ptr_type());
+      }
+      held.push_back(weights[m]->_p);
+    }
+    const void *p0 = c0 ? s0->dev_ro() : nullptr, *p1 = s1->dev_ro();
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo();
+    void *kgat = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &kgat, count * tpolys * pb), "linear_transform_level_ntt");
+    const void *kp[NFLHIP_LINTRANS_MAX_TERMS], *wp[NFLHIP_LINTRANS_MAX_TERMS];
+    int rc = NFLHIP_OK;
+    for (size_t m = 0; m < count; ++m) {
+      kp[m] = keys[m] ? static_cast<char *>(kgat) + m * tpolys * pb : nullptr;
+      wp[m] = static_cast<char *>(kgat) + (m * tpolys + tlive) * pb;
+      for (size_t t = 0; t < tpolys && rc == NFLHIP_OK; ++t)
+        if (held[m * tpolys + t])
+          rc = nflhip_memcpy_d2d(ctx_t::get(), static_cast<char *>(kgat) + (m * tpolys + t) * pb, held[m * tpolys + t]->dev_ro(),
+                                 t < tlive ? pb : wbytes, ctx_t::queue());
+    }
+    if (rc == NFLHIP_OK) rc = nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue());
+    const int flags = (centered ? NFLHIP_LINTRANS_CENTERED : 0) | (floor ? NFLHIP_LINTRANS_FLOOR : 0);
+    if (rc == NFLHIP_OK) rc = nflhip_lintrans_level_ntt_dev(ctx_t::get(), o0, o1, p0, p1, kp, wp, ks, count, 1, K, alpha, LO, flags, ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered keys go)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), kgat);
+      throw std::runtime_error("nfl(hip): linear_transform_level_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), kgat);
+    detail::check(ctx_t::get(), rs, "linear_transform_level_ntt");
+    out0._p = d0;
+    out1._p = d1;
+  }
+
   // The tensor product (nfl::tensor_ntt below): the deferred queue of this ring type runs first, then one launch on its stream.  The
   // results get payloads of their own, so an output may be an input and copy-on-write sharers of the outputs' old values keep them.
   static void tensor_into(poly_p &out0, poly_p &out1, poly_p &out2, poly_p const &a0, poly_p const &a1, poly_p const *b0, poly_p const *b1) {
@@ -1090,6 +1200,83 @@ void linear_transform_ntt(poly_p<T, D, L> &out0, poly_p<T, D, L> &out1, poly_p<T
                           poly_p<T, D, M> const *const *keys, poly_p<T, D, M> const *const *weights, const uint64_t *ks, size_t count, size_t alpha,
                           bool centered = false, bool floor = false) {
   poly_p<T, D, M>::template linear_transform_into<L>(out0, out1, c0, c1, keys, weights, ks, count, alpha, centered, floor);
+}
+
+/* The two BELOW the top level (include/nflhip.h "rotations and linear transforms at a level"): c0, c1 and the outputs in the ring with Lv
+ * moduli, the level; keys[m] the ONE top-level Galois key of rotation m in the ring with M moduli whose last K are the special ones,
+ * 2 dnum_L polynomials in [term][component] order (the first 2 ceil(Lv / alpha) are read), or NULL for the unrotated diagonal of a
+ * linear transform; weights[m] the ONE top-level diagonal, a polynomial of the ring with M moduli.  K cannot be deduced from the types
+ * any more and is the explicit template argument: nfl::rotate_hoisted_level_ntt<K>(out0s, out1s, c0, c1, keys, ks, count, alpha).
+ * Lv <= M - K is checked at compile time.  Only the rows [0, Lv) and the K special rows of the keys and diagonals are read.  Never
+ * fused into a queue's rewrites. */
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void rotate_hoisted_level_ntt(poly<T, D, Lv> *out0s, poly<T, D, Lv> *out1s, poly<T, D, Lv> const *c0, poly<T, D, Lv> const &c1,
+                              poly<T, D, M> const *const *keys, const uint64_t *ks, size_t count, size_t alpha, bool centered = false,
+                              bool floor = false) {
+  static_assert(K >= 1 && K < M && Lv >= 1 && Lv <= M - K, "nfl::rotate_hoisted_level_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+  typedef poly<T, D, Lv> S;
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  if (count == 0 || count > NFLHIP_ROTATE_MAX_OUTPUTS) throw std::runtime_error("nfl(hip): rotate_hoisted_level_ntt: 1 to 16 rotations");
+  S *t0[NFLHIP_ROTATE_MAX_OUTPUTS], *t1[NFLHIP_ROTATE_MAX_OUTPUTS];  // (an output may be an input)
+  void *o0[NFLHIP_ROTATE_MAX_OUTPUTS], *o1[NFLHIP_ROTATE_MAX_OUTPUTS];
+  const void *kp[NFLHIP_ROTATE_MAX_OUTPUTS];
+  for (size_t m = 0; m < count; ++m) {
+    t0[m] = S::make_temp();
+    t1[m] = S::make_temp();
+    o0[m] = t0[m]->data();
+    o1[m] = t1[m]->data();
+    kp[m] = (*keys[m]).cdata();
+  }
+  const int flags = (centered ? NFLHIP_ROTATE_CENTERED : 0) | (floor ? NFLHIP_ROTATE_FLOOR : 0);
+  const int rc = nflhip_rotate_hoisted_level_ntt(P::ctx(), o0, o1, c0 ? c0->cdata() : nullptr, c1.cdata(), kp, ks, count, 1, K, alpha, Lv, flags);
+  for (size_t m = 0; m < count; ++m) {
+    if (rc == 0) {
+      std::memcpy(static_cast<void *>(out0s[m].data()), t0[m]->cdata(), sizeof(S));
+      std::memcpy(static_cast<void *>(out1s[m].data()), t1[m]->cdata(), sizeof(S));
+    }
+    S::drop_temp(t0[m]);
+    S::drop_temp(t1[m]);
+  }
+  detail::check(P::ctx(), rc, "rotate_hoisted_level_ntt");
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void rotate_hoisted_level_ntt(poly_p<T, D, Lv> *out0s, poly_p<T, D, Lv> *out1s, poly_p<T, D, Lv> const *c0, poly_p<T, D, Lv> const &c1,
+                              poly_p<T, D, M> const *const *keys, const uint64_t *ks, size_t count, size_t alpha, bool centered = false,
+                              bool floor = false) {
+  poly_p<T, D, M>::template rotate_level_into<K, Lv>(out0s, out1s, c0, c1, keys, ks, count, alpha, centered, floor);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void linear_transform_level_ntt(poly<T, D, Lv> &out0, poly<T, D, Lv> &out1, poly<T, D, Lv> const *c0, poly<T, D, Lv> const &c1,
+                                poly<T, D, M> const *const *keys, poly<T, D, M> const *const *weights, const uint64_t *ks, size_t count, size_t alpha,
+                                bool centered = false, bool floor = false) {
+  static_assert(K >= 1 && K < M && Lv >= 1 && Lv <= M - K, "nfl::linear_transform_level_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+  typedef poly<T, D, Lv> S;
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  if (count == 0 || count > NFLHIP_LINTRANS_MAX_TERMS) throw std::runtime_error("nfl(hip): linear_transform_level_ntt: 1 to 16 terms");
+  const void *kp[NFLHIP_LINTRANS_MAX_TERMS], *wp[NFLHIP_LINTRANS_MAX_TERMS];
+  for (size_t m = 0; m < count; ++m) {
+    kp[m] = keys[m] ? keys[m]->cdata() : nullptr;
+    wp[m] = weights[m]->cdata();
+  }
+  S *t0 = S::make_temp(), *t1 = S::make_temp();  // (an output may be an input)
+  const int flags = (centered ? NFLHIP_LINTRANS_CENTERED : 0) | (floor ? NFLHIP_LINTRANS_FLOOR : 0);
+  const int rc = nflhip_lintrans_level_ntt(P::ctx(), t0->data(), t1->data(), c0 ? c0->cdata() : nullptr, c1.cdata(), kp, wp, ks, count, 1, K, alpha, Lv,
+                                           flags);
+  if (rc == 0) {
+    std::memcpy(static_cast<void *>(out0.data()), t0->cdata(), sizeof(S));
+    std::memcpy(static_cast<void *>(out1.data()), t1->cdata(), sizeof(S));
+  }
+  S::drop_temp(t0);
+  S::drop_temp(t1);
+  detail::check(P::ctx(), rc, "linear_transform_level_ntt");
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void linear_transform_level_ntt(poly_p<T, D, Lv> &out0, poly_p<T, D, Lv> &out1, poly_p<T, D, Lv> const *c0, poly_p<T, D, Lv> const &c1,
+                                poly_p<T, D, M> const *const *keys, poly_p<T, D, M> const *const *weights, const uint64_t *ks, size_t count,
+                                size_t alpha, bool centered = false, bool floor = false) {
+  poly_p<T, D, M>::template linear_transform_level_into<K, Lv>(out0, out1, c0, c1, keys, weights, ks, count, alpha, centered, floor);
 }
 
 /* Sums of products across polynomials (include/nflhip.h): out = sum_{j < terms} a[j] * b[j], element-wise in every row -- the

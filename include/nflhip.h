@@ -650,6 +650,38 @@ int nflhip_mulrelin_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const
                               const void *h_b1, const void *h_key, size_t batch, size_t k_special, size_t alpha, size_t level,
                               int flags);   /* staged host variant */
 
+/* ---- rotations and linear transforms at a level: one Galois key and one diagonal for every level ----
+ * nflhip_rotate_hoisted_ntt_dev and nflhip_lintrans_ntt_dev on a ciphertext below the context's top level, with the ONE top-level
+ * Galois key per rotation and the ONE top-level diagonal per term.  Levels, live rows A_l, phys(r) and the digits are those of
+ * "leveled key switching" above.
+ *   c0, c1, outputs  [batch][l][degree], NTT form, the dense layout over the first l moduli
+ *   keys[m]          unchanged: [dnum_L][2][nmoduli][degree], the convention of "hoisted rotations" (from s to sigma_(k^-1)(s)).
+ *                    Only keys[m][d][c][phys(r)] is read, for d < dnum_l and r < l + k_special
+ *   weights[m]       (linear transform) unchanged: [nmoduli][degree], the diagonal in NTT form over the full context.  Rows A_l are
+ *                    read in the pass on l + k_special rows and rows [0, l) in the passes on the kept rows; rows [l, L) are never
+ *                    read.  Row j of an encoded diagonal is its residue mod p_j whatever the level, so one diagonal serves every level
+ * Definition, word for word: with C_l and key_l as above and weight_l[m][r] = weights[m][phys(r)], a level-l call returns the words
+ * of nflhip_rotate_hoisted_ntt_dev / nflhip_lintrans_ntt_dev on C_l with those keys and weights, k_special and min(alpha, l).  For
+ * l = L it is that entry on this context itself.  ks, flags, plans, modes, the limits (16 rotations / terms), the NULL-key terms and
+ * the overlap rules are those of the two entries with L read as l; the extent of a key that may not overlap an output is its first
+ * dnum_l digits.  The level context is the one of the key switch at that (k_special, l); records, scratch and the first-call,
+ * larger-batch and while-capturing rules are per level as there.  The kernels that read a key or a diagonal on l + k_special rows
+ * (k_dot_multi, k_permute_mac_ntt) have instances that know the parent's pitch and the hole of L - l rows.
+ * NFLHIP_ERR_INVALID, nothing enqueued: what the two entries refuse, and level == 0, level > L.
+ * The host variants stage the operands, the 2 dnum_l key polynomials per rotation that are read and the whole diagonals. */
+int nflhip_rotate_hoisted_level_ntt_dev(nflhip_ctx *ctx, void *const *d_out0s, void *const *d_out1s, const void *d_c0, const void *d_c1,
+                                        const void *const *d_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special,
+                                        size_t alpha, size_t level, int flags, void *stream);
+int nflhip_rotate_hoisted_level_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const *h_out1s, const void *h_c0, const void *h_c1,
+                                    const void *const *h_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special,
+                                    size_t alpha, size_t level, int flags);   /* staged host variant */
+int nflhip_lintrans_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_c0, const void *d_c1,
+                                  const void *const *d_keys, const void *const *d_weights, const uint64_t *ks, size_t count, size_t batch,
+                                  size_t k_special, size_t alpha, size_t level, int flags, void *stream);
+int nflhip_lintrans_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_c0, const void *h_c1,
+                              const void *const *h_keys, const void *const *h_weights, const uint64_t *ks, size_t count, size_t batch,
+                              size_t k_special, size_t alpha, size_t level, int flags);   /* staged host variant */
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

@@ -100,6 +100,10 @@ SYMBOLS = [
     ("nflhip_keyswitch_level_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _i]),
     ("nflhip_mulrelin_level_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _i, _vp]),
     ("nflhip_mulrelin_level_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _i]),
+    ("nflhip_rotate_hoisted_level_ntt_dev", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_rotate_hoisted_level_ntt", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _sz, _i]),
+    ("nflhip_lintrans_level_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_lintrans_level_ntt", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _sz, _i]),
     ("nflhip_gadget_mul_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),

@@ -1113,7 +1113,7 @@ int nflhip_moddown_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_
 // [0, level) and [nm - K, nm) of this one -- a subsequence of the moduli, in their order: created on first use, never while
 // capturing, destroyed with this context.  keyswitch_run and mulrelin_run then run on it as they are, with its own records, scratch,
 // events and warm maps; the key alone stays in this context's layout, described by a KeyLevel that travels to the three launchers
-// which read it (dot_key and the two one-launch kernels).
+// which read it (dot_key and the two one-launch kernels).  rotate_run and lintrans_run run on it likewise (kernels_level_rotate.hip).
 static int level_child(nflhip_ctx *ctx, size_t K, size_t level, bool cap, nflhip_ctx **out) {
   std::lock_guard<std::mutex> lk(ctx->bcn_mu);
   const size_t count = level + K, hole = ctx->shape.nm - count;
@@ -1310,9 +1310,13 @@ int nflhip_keyswitch_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const 
 //             one mod-down into Y = [2 count][batch][L][n]; k_permute_add_ntt
 // Default: hoisted for count >= 2, the sequence for count == 1 (a single rotation has no mod-up to share and the key switch's own
 // default plan is the measured best there).
+// kl: ctx is a level context and the keys lie in its parent's layout (nflhip_rotate_hoisted_level_ntt_dev): the sequence calls
+// keyswitch_run with it -- the public entry would read the key in this context's layout --, the hoisted plan the k_dot_multi instances
+// of kernels_level_rotate.hip, the component pointers keys[m] + c knm n words.  Everything else is this context's own.
 // Lock order: rot_mu, then ks_mu, then bcn_mu.
 static int rotate_run(nflhip_ctx *ctx, void *const *out0s, void *const *out1s, const void *c0, const void *c1, const void *const *keys,
-                      const uint64_t *ks, size_t count, size_t batch, size_t K, size_t alpha, int flags, hipStream_t st) {
+                      const uint64_t *ks, size_t count, size_t batch, size_t K, size_t alpha, int flags, hipStream_t st,
+                      const KeyLevel *kl = nullptr) {
   std::lock_guard<std::mutex> lk(ctx->rot_mu);
   const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha, row = ctx->shape.n * ctx->word, pb = nm * row, qb = L * row;
   const bool centred = (flags & NFLHIP_ROTATE_CENTERED) != 0, floor = (flags & NFLHIP_ROTATE_FLOOR) != 0, cap = is_capturing(st);
@@ -1347,7 +1351,10 @@ static int rotate_run(nflhip_ctx *ctx, void *const *out0s, void *const *out1s, c
       HIPCHK(ctx, hipMemset2DAsync(ones, ctx->word, 1, 1, L * ctx->shape.n, st));
     }
     for (size_t m = 0; m < count; ++m) {
-      if ((rc = nflhip_keyswitch_ntt_dev(ctx, T0, T1, c1, keys[m], batch, K, alpha, modes, st))) return rc;  // (the mode bits are the key switch's)
+      // (the mode bits are the key switch's; at a level the public entry would read the key in this context's layout)
+      if ((rc = kl ? keyswitch_run(ctx, T0, T1, c1, keys[m], batch, K, alpha, modes, st, kl)
+                   : nflhip_keyswitch_ntt_dev(ctx, T0, T1, c1, keys[m], batch, K, alpha, modes, st)))
+        return rc;
       const char *y0 = T0;
       if (c0 && pw) {
         if ((rc = nflhip_pointwise_dev(child, NFLHIP_OP_ADD, T0, T0, c0, nullptr, batch, st))) return rc;
@@ -1373,7 +1380,7 @@ static int rotate_run(nflhip_ctx *ctx, void *const *out0s, void *const *out1s, c
       for (size_t c = 0; c < 2; ++c) {
         const size_t p = 2 * m + c;
         douts[p] = S + p * batch * pb;
-        dbs[p] = (const char *)keys[m] + c * pb;
+        dbs[p] = (const char *)keys[m] + c * (kl ? kl->knm * row : pb);
         pins[p] = Y + p * batch * qb;
         pouts[p] = c ? out1s[m] : out0s[m];
         pks[p] = ks[m];
@@ -1381,6 +1388,9 @@ static int rotate_run(nflhip_ctx *ctx, void *const *out0s, void *const *out1s, c
       }
     hipError_t e = with_limb(ctx, [&](auto z) {
       typedef decltype(z) T;
+      if (kl)
+        return launch_dot_multi_level<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, u.group_stride, u.term_stride,
+                                         (const T *const *)dbs, 2 * count, batch, dnum, 1, *kl, st);
       return launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, u.group_stride, u.term_stride, (const T *const *)dbs, 2,
                                  2 * count, batch, dnum, 1, st);
     });
@@ -1434,9 +1444,14 @@ int nflhip_automorphism_mac_dev(nflhip_ctx *ctx, void *d_out, const void *d_adde
 // Default: hoisted, always.  The starting rule (hoisted from two keyed terms on) did not survive the measurement: with ONE keyed term
 // the hoisted plan measured x1.07 - x1.18 against the sequence, well beyond the blocks' spread, and with none it is the one-launch
 // primitive against a loop of automorphism + dot (profiles/r16_lintrans.txt).  The sequence is the cross-check.
+// kl: ctx is a level context and the keys AND the weights lie in its parent's layout (nflhip_lintrans_level_ntt_dev).  Sequence: the
+// key dots through dot_key, the one-term dot against the weight on all rows through the level-key operand too (one term, so the term
+// stride is moot; no gather, no copy).  Hoisted: the instances of kernels_level_rotate.hip for k_dot_multi and for the
+// k_permute_mac_ntt pass on all rows.  The passes on the kept rows need nothing: rows [0, level) of a parent-layout weight are a prefix.
 // Lock order: lt_mu, then ks_mu, then bcn_mu.
 static int lintrans_run(nflhip_ctx *ctx, void *out0, void *out1, const void *c0, const void *c1, const void *const *keys, const void *const *weights,
-                        const uint64_t *ks, size_t count, size_t batch, size_t K, size_t alpha, int flags, hipStream_t st) {
+                        const uint64_t *ks, size_t count, size_t batch, size_t K, size_t alpha, int flags, hipStream_t st,
+                        const KeyLevel *kl = nullptr) {
   std::lock_guard<std::mutex> lk(ctx->lt_mu);
   const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha, row = ctx->shape.n * ctx->word, pb = nm * row, qb = L * row;
   const bool centred = (flags & NFLHIP_LINTRANS_CENTERED) != 0, floor = (flags & NFLHIP_LINTRANS_FLOOR) != 0, cap = is_capturing(st);
@@ -1491,11 +1506,15 @@ static int lintrans_run(nflhip_ctx *ctx, void *out0, void *out1, const void *c0,
       const nflhip_dot_operand pa = {P, 1, 0};
       for (size_t m = 0; m < keyed; ++m)
         for (size_t c = 0; c < 2; ++c) {
-          const nflhip_dot_operand b = {(const char *)kkeys[m] + c * pb, 0, 2}, w = {kw[m], 0, 0};
           char *Ac = A + c * batch * pb;
-          if ((rc = nflhip_dot_dev(ctx, T, &a, &b, nullptr, batch, dnum, 0, st))) return rc;
+          if ((rc = dot_key(ctx, T, &a, kkeys[m], c, nullptr, batch, dnum, kl, st))) return rc;
           if ((rc = nflhip_automorphism_dev(ctx, P, T, batch, kks[m], NFLHIP_FORM_NTT, st))) return rc;
-          if ((rc = nflhip_dot_dev(ctx, Ac, &pa, &w, m ? Ac : nullptr, batch, 1, 0, st))) return rc;
+          if (kl) {  // the diagonal lies in the parent's layout as a key component does: the level-key operand, one term
+            if ((rc = dot_key(ctx, Ac, &pa, kw[m], 0, m ? Ac : nullptr, batch, 1, kl, st))) return rc;
+          } else {
+            const nflhip_dot_operand w = {kw[m], 0, 0};
+            if ((rc = nflhip_dot_dev(ctx, Ac, &pa, &w, m ? Ac : nullptr, batch, 1, 0, st))) return rc;
+          }
         }
     } else {
       void *douts[2 * NFLHIP_LINTRANS_MAX_TERMS];
@@ -1503,15 +1522,20 @@ static int lintrans_run(nflhip_ctx *ctx, void *out0, void *out1, const void *c0,
       for (size_t m = 0; m < keyed; ++m) {
         for (size_t c = 0; c < 2; ++c) {
           douts[2 * m + c] = S + (2 * m + c) * batch * pb;
-          dbs[2 * m + c] = (const char *)kkeys[m] + c * pb;
+          dbs[2 * m + c] = (const char *)kkeys[m] + c * (kl ? kl->knm * row : pb);
         }
         mins[m] = douts[2 * m];  // component c of term m lies c batch polynomials behind
       }
       hipError_t e = with_limb(ctx, [&](auto z) {
         typedef decltype(z) T;
-        hipError_t r = launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, a.group_stride, a.term_stride,
-                                           (const T *const *)dbs, 2, 2 * keyed, batch, dnum, 1, st);
+        hipError_t r = kl ? launch_dot_multi_level<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, a.group_stride, a.term_stride,
+                                                      (const T *const *)dbs, 2 * keyed, batch, dnum, 1, *kl, st)
+                          : launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, a.group_stride, a.term_stride,
+                                                (const T *const *)dbs, 2, 2 * keyed, batch, dnum, 1, st);
         if (r != hipSuccess) return r;
+        if (kl)  // (the passes on the kept rows below need nothing: rows [0, level) of a parent-layout diagonal are a prefix)
+          return launch_permute_mac_ntt_level<T>(ctx->shape, ctx->tabs, (T *)A, nullptr, (const T *const *)mins, (const T *const *)kw, kks, (int)keyed,
+                                                 batch, 2, batch * pw, batch * pw, *kl, st);
         return launch_permute_mac_ntt<T>(ctx->shape, ctx->tabs, (T *)A, nullptr, (const T *const *)mins, (const T *const *)kw, kks, (int)keyed, batch,
                                          nm, 2, batch * pw, batch * pw, 0, st);
       });
@@ -1767,6 +1791,33 @@ int nflhip_mulrelin_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, c
   if ((rc = level_context(ctx, k_special, level, (hipStream_t)stream, &run, &kl))) return rc;
   return mulrelin_run(run, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, std::min(alpha, level), flags, (hipStream_t)stream,
                       run == ctx ? nullptr : &kl);
+}
+// Hoisted rotations and linear transforms at a level (kernels_level_rotate.hip; include/nflhip.h "rotations and linear transforms at
+// a level"): rotate_run and lintrans_run on the level context, whose records, workspaces, events, warm maps and kept-rows child are
+// its own; the Galois keys and the diagonals stay in this context's layout and the KeyLevel travels to the launchers that read them.
+int nflhip_rotate_hoisted_level_ntt_dev(nflhip_ctx *ctx, void *const *d_out0s, void *const *d_out1s, const void *d_c0, const void *d_c1,
+                                        const void *const *d_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha,
+                                        size_t level, int flags, void *stream) {
+  int rc = level_check(ctx, k_special, level, "rotate");  // in full, before any device use
+  if (!rc) rc = rotate_check(ctx, d_out0s, d_out1s, d_c0, d_c1, d_keys, ks, count, batch, k_special, alpha, flags, level);
+  if (rc || batch == 0) return rc;
+  nflhip_ctx *run = nullptr;
+  KeyLevel kl;
+  if ((rc = level_context(ctx, k_special, level, (hipStream_t)stream, &run, &kl))) return rc;
+  return rotate_run(run, d_out0s, d_out1s, d_c0, d_c1, d_keys, ks, count, batch, k_special, std::min(alpha, level), flags, (hipStream_t)stream,
+                    run == ctx ? nullptr : &kl);
+}
+int nflhip_lintrans_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_c0, const void *d_c1, const void *const *d_keys,
+                                  const void *const *d_weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha,
+                                  size_t level, int flags, void *stream) {
+  int rc = level_check(ctx, k_special, level, "lintrans");  // in full, before any device use
+  if (!rc) rc = lintrans_check(ctx, d_out0, d_out1, d_c0, d_c1, d_keys, d_weights, ks, count, batch, k_special, alpha, flags, level);
+  if (rc || batch == 0) return rc;
+  nflhip_ctx *run = nullptr;
+  KeyLevel kl;
+  if ((rc = level_context(ctx, k_special, level, (hipStream_t)stream, &run, &kl))) return rc;
+  return lintrans_run(run, d_out0, d_out1, d_c0, d_c1, d_keys, d_weights, ks, count, batch, k_special, std::min(alpha, level), flags,
+                      (hipStream_t)stream, run == ctx ? nullptr : &kl);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

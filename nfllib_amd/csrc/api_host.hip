@@ -478,14 +478,15 @@ int nflhip_keyswitch_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, cons
   return keyswitch_host(ctx, h_out0, h_out1, h_in, h_key, batch, k_special, alpha, level, flags);
 }
 
-// hoisted rotations: c1 (and c0 behind it), every key and every output are staged whole (the outputs share one slot, out0s then out1s)
-int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const *h_out1s, const void *h_c0, const void *h_c1,
-                              const void *const *h_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
-  int rc = rotate_check(ctx, h_out0s, h_out1s, h_c0, h_c1, h_keys, ks, count, batch, k_special, alpha, flags);
-  if (rc || batch == 0) return rc;
-  if ((rc = set_device(ctx))) return rc;
-  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * (nm - k_special) * row;
-  const size_t kb = 2 * keyswitch_digits(ctx, k_special, alpha) * nm * row;
+// hoisted rotations: c1 (and c0 behind it), every key and every output are staged whole (the outputs share one slot, out0s then out1s).
+// The body of both entries, the arguments checked: the operands have `level` rows (the top-level entry: all nmoduli - k_special, where
+// the level entry on the device forwards), and of every key the digits that are read are staged.
+static int rotate_host(nflhip_ctx *ctx, void *const *h_out0s, void *const *h_out1s, const void *h_c0, const void *h_c1, const void *const *h_keys,
+                       const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, size_t level, int flags) {
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * level * row;
+  const size_t kb = 2 * keyswitch_level_digits(ctx, k_special, alpha, level) * nm * row;
   Staged s(ctx);
   if ((rc = s.in(0, nullptr, 2 * ob)) || (rc = s.in(1, nullptr, count * kb)) || (rc = s.in(2, nullptr, 2 * count * ob))) return rc;
   char *c = (char *)ctx->stage[0], *k = (char *)ctx->stage[1], *o = (char *)ctx->stage[2];
@@ -503,7 +504,8 @@ int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const
     o0[m] = o + m * ob;
     o1[m] = o + (count + m) * ob;
   }
-  if ((rc = nflhip_rotate_hoisted_ntt_dev(ctx, o0, o1, h_c0 ? c + ob : nullptr, c, keys, ks, count, batch, k_special, alpha, flags, (void *)ctx->hstream)))
+  if ((rc = nflhip_rotate_hoisted_level_ntt_dev(ctx, o0, o1, h_c0 ? c + ob : nullptr, c, keys, ks, count, batch, k_special, alpha, level, flags,
+                                                (void *)ctx->hstream)))
     return rc;
   void *hs[2 * NFLHIP_ROTATE_MAX_OUTPUTS];  // as the slot holds them: out0s, then out1s
   for (size_t m = 0; m < count; ++m) {
@@ -511,6 +513,20 @@ int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const
     hs[count + m] = h_out1s[m];
   }
   return s.outs(hs, 2 * count, 2, ob);
+}
+int nflhip_rotate_hoisted_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const *h_out1s, const void *h_c0, const void *h_c1,
+                              const void *const *h_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
+  int rc = rotate_check(ctx, h_out0s, h_out1s, h_c0, h_c1, h_keys, ks, count, batch, k_special, alpha, flags);
+  if (rc || batch == 0) return rc;
+  return rotate_host(ctx, h_out0s, h_out1s, h_c0, h_c1, h_keys, ks, count, batch, k_special, alpha, ctx->shape.nm - k_special, flags);
+}
+int nflhip_rotate_hoisted_level_ntt(nflhip_ctx *ctx, void *const *h_out0s, void *const *h_out1s, const void *h_c0, const void *h_c1,
+                                    const void *const *h_keys, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha,
+                                    size_t level, int flags) {
+  int rc = level_check(ctx, k_special, level, "rotate");
+  if (!rc) rc = rotate_check(ctx, h_out0s, h_out1s, h_c0, h_c1, h_keys, ks, count, batch, k_special, alpha, flags, level);
+  if (rc || batch == 0) return rc;
+  return rotate_host(ctx, h_out0s, h_out1s, h_c0, h_c1, h_keys, ks, count, batch, k_special, alpha, level, flags);
 }
 
 // weighted sums of automorphisms: every input, every weight and the output (the addend copied into it) are staged whole
@@ -538,14 +554,15 @@ int nflhip_automorphism_mac(nflhip_ctx *ctx, void *h_out, const void *h_addend, 
 }
 
 // slot linear transforms: c1 (and c0 behind it), every key, every weight and both outputs are staged whole (the outputs share one
-// slot, out1 behind out0, so that the mod-down runs as one batch)
-int nflhip_lintrans_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_c0, const void *h_c1, const void *const *h_keys,
-                        const void *const *h_weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
-  int rc = lintrans_check(ctx, h_out0, h_out1, h_c0, h_c1, h_keys, h_weights, ks, count, batch, k_special, alpha, flags);
-  if (rc || batch == 0) return rc;
-  if ((rc = set_device(ctx))) return rc;
-  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * (nm - k_special) * row, wb = nm * row;
-  const size_t kb = 2 * keyswitch_digits(ctx, k_special, alpha) * wb;
+// slot, out1 behind out0, so that the mod-down runs as one batch).  The body of both entries, as rotate_host; a weight is a whole
+// polynomial of this context at every level.
+static int lintrans_host(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_c0, const void *h_c1, const void *const *h_keys,
+                         const void *const *h_weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, size_t level,
+                         int flags) {
+  int rc = set_device(ctx);
+  if (rc) return rc;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * level * row, wb = nm * row;
+  const size_t kb = 2 * keyswitch_level_digits(ctx, k_special, alpha, level) * wb;
   Staged s(ctx);
   if ((rc = s.in(0, nullptr, 2 * ob)) || (rc = s.in(1, nullptr, count * (kb + wb))) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
   char *c = (char *)ctx->stage[0], *k = (char *)ctx->stage[1], *o = (char *)ctx->stage[2];
@@ -562,9 +579,24 @@ int nflhip_lintrans_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void 
     keys[m] = h_keys[m] ? km : nullptr;
     ws[m] = km + kb;
   }
-  if ((rc = nflhip_lintrans_ntt_dev(ctx, o, o + ob, h_c0 ? c + ob : nullptr, c, keys, ws, ks, count, batch, k_special, alpha, flags, (void *)ctx->hstream)))
+  if ((rc = nflhip_lintrans_level_ntt_dev(ctx, o, o + ob, h_c0 ? c + ob : nullptr, c, keys, ws, ks, count, batch, k_special, alpha, level, flags,
+                                          (void *)ctx->hstream)))
     return rc;
   return s.out2(h_out0, h_out1, 2, ob);
+}
+int nflhip_lintrans_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_c0, const void *h_c1, const void *const *h_keys,
+                        const void *const *h_weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
+  int rc = lintrans_check(ctx, h_out0, h_out1, h_c0, h_c1, h_keys, h_weights, ks, count, batch, k_special, alpha, flags);
+  if (rc || batch == 0) return rc;
+  return lintrans_host(ctx, h_out0, h_out1, h_c0, h_c1, h_keys, h_weights, ks, count, batch, k_special, alpha, ctx->shape.nm - k_special, flags);
+}
+int nflhip_lintrans_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_c0, const void *h_c1, const void *const *h_keys,
+                              const void *const *h_weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha,
+                              size_t level, int flags) {
+  int rc = level_check(ctx, k_special, level, "lintrans");
+  if (!rc) rc = lintrans_check(ctx, h_out0, h_out1, h_c0, h_c1, h_keys, h_weights, ks, count, batch, k_special, alpha, flags, level);
+  if (rc || batch == 0) return rc;
+  return lintrans_host(ctx, h_out0, h_out1, h_c0, h_c1, h_keys, h_weights, ks, count, batch, k_special, alpha, level, flags);
 }
 
 // the tensor product: the inputs share one slot (a0, a1, then b0, b1 unless it is the square), the three outputs another

@@ -373,7 +373,7 @@ inline int dot_multi_check(const nflhip_ctx *ctx, void *const *outs, const nflhi
 // nflhip_rotate_hoisted_ntt_dev / nflhip_rotate_hoisted_ntt: every argument check short of the tables (a repeated modulus is found by
 // their builder, api.hip keyswitch_records), before any device use
 inline int rotate_check(const nflhip_ctx *ctx, void *const *out0s, void *const *out1s, const void *c0, const void *c1, const void *const *keys,
-                        const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
+                        const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags, size_t level = 0) {
   int rc = keyswitch_family_check(ctx, "rotate", flags, NFLHIP_ROTATE_SEQUENCE | NFLHIP_ROTATE_HOISTED, NFLHIP_ROTATE_CENTERED | NFLHIP_ROTATE_FLOOR,
                                   count == 0 || count > NFLHIP_ROTATE_MAX_OUTPUTS ? "rotate: the number of rotations is out of range (1 to 16)" : nullptr,
                                   k_special, alpha);
@@ -385,11 +385,12 @@ inline int rotate_check(const nflhip_ctx *ctx, void *const *out0s, void *const *
   if (!out0s || !out1s || !c1 || !keys) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
   for (size_t m = 0; m < count; ++m)
     if (!out0s[m] || !out1s[m] || !keys[m]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
-  const size_t row = ctx->shape.n * ctx->word, L = nm - k_special;
+  // (level: as keyswitch_check)
+  const size_t row = ctx->shape.n * ctx->word, L = level ? level : nm - k_special, kd = level ? (level + alpha - 1) / alpha : dnum;
   size_t ob, sb, kb, polys;
-  // (sb: the largest scratch of either plan -- [batch][1 + dnum + 4 count][nm][n] -- on top of the key switch's own)
+  // (sb: the largest scratch of either plan -- [batch][1 + dnum + 4 count][nm][n] -- on top of the key switch's own; kb: the digits that are read)
   if (__builtin_mul_overflow(batch, L * row, &ob) || __builtin_mul_overflow(batch, dnum + 3 + 4 * count, &polys) ||
-      __builtin_mul_overflow(polys, nm * row, &sb) || __builtin_mul_overflow(2 * dnum, nm * row, &kb))
+      __builtin_mul_overflow(polys, nm * row, &sb) || __builtin_mul_overflow(2 * kd, nm * row, &kb))
     return fail(ctx, NFLHIP_ERR_INVALID, "rotate: the size overflows");
   for (size_t m = 0; m < 2 * count; ++m) {
     const void *o = m < count ? out0s[m] : out1s[m - count];
@@ -429,7 +430,8 @@ inline int mac_check(const nflhip_ctx *ctx, const void *out, const void *addend,
 // nflhip_lintrans_ntt_dev / nflhip_lintrans_ntt: every argument check short of the tables (a repeated modulus is found by their
 // builder, api.hip keyswitch_records), before any device use
 inline int lintrans_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *c0, const void *c1, const void *const *keys,
-                          const void *const *weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags) {
+                          const void *const *weights, const uint64_t *ks, size_t count, size_t batch, size_t k_special, size_t alpha, int flags,
+                          size_t level = 0) {
   int rc = keyswitch_family_check(ctx, "lintrans", flags, NFLHIP_LINTRANS_SEQUENCE | NFLHIP_LINTRANS_HOISTED, NFLHIP_LINTRANS_CENTERED | NFLHIP_LINTRANS_FLOOR,
                                   count == 0 || count > NFLHIP_LINTRANS_MAX_TERMS ? "lintrans: the number of terms is out of range (1 to 16)" : nullptr,
                                   k_special, alpha);
@@ -444,11 +446,12 @@ inline int lintrans_check(const nflhip_ctx *ctx, const void *out0, const void *o
     if (!keys[m] && (ks[m] & (2 * ctx->shape.n - 1)) != 1)
       return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: a NULL key goes with k = 1 mod 2 degree only (the unrotated diagonal)");
   }
-  const size_t row = ctx->shape.n * ctx->word, L = nm - k_special, wb = nm * row;
+  // (level: as keyswitch_check; a weight is a whole polynomial of this context at every level)
+  const size_t row = ctx->shape.n * ctx->word, L = level ? level : nm - k_special, wb = nm * row, kd = level ? (level + alpha - 1) / alpha : dnum;
   size_t ob, sb, kb, polys;
-  // (sb: the largest scratch of either plan -- [batch][dnum + 6 + 2 count][nm][n])
+  // (sb: the largest scratch of either plan -- [batch][dnum + 6 + 2 count][nm][n]; kb: the digits that are read)
   if (__builtin_mul_overflow(batch, L * row, &ob) || __builtin_mul_overflow(batch, dnum + 6 + 2 * count, &polys) ||
-      __builtin_mul_overflow(polys, wb, &sb) || __builtin_mul_overflow(2 * dnum, wb, &kb))
+      __builtin_mul_overflow(polys, wb, &sb) || __builtin_mul_overflow(2 * kd, wb, &kb))
     return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: the size overflows");
   if (ranges_overlap(out0, ob, out1, ob)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: the two outputs overlap");
   for (const void *o : {out0, out1}) {

@@ -224,6 +224,17 @@ template <typename T>
 hipError_t launch_tensor_modup_dot_fused_level(const Shape &s, const DevTables &t, T *acc, const T *a0, const T *a1, const T *b0, const T *b1,
                                                const T *key, const uint64_t *const *recs, const uint64_t *pi, size_t batch, size_t L, size_t alpha,
                                                int centred, const KeyLevel &kl, hipStream_t st);
+// the same layout for a hoisted rotation or a linear transform at a level (kernels_level_rotate.hip; include/nflhip.h "rotations and
+// linear transforms at a level").  launch_dot_multi with bs[o] = component c of a key in the parent's layout, key + c knm n words,
+// a term every 2 knm n words; launch_permute_mac_ntt (one staging buffer) on all rows of the level context with weights[t] = a
+// diagonal [knm][n] in the parent's layout.  Everything else is the level context's dense layout.
+template <typename T>
+hipError_t launch_dot_multi_level(const Shape &s, const DevTables &t, T *const *outs, const T *a, size_t a_gs, size_t a_ts, const T *const *bs,
+                                  size_t outputs, size_t groups, size_t terms, int tiled, const KeyLevel &kl, hipStream_t st);
+template <typename T>
+hipError_t launch_permute_mac_ntt_level(const Shape &s, const DevTables &t, T *out, const T *addend, const T *const *ins, const T *const *weights,
+                                        const uint64_t *ks, int terms, size_t batch, size_t comps, size_t in_cs, size_t out_cs, const KeyLevel &kl,
+                                        hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);

@@ -496,23 +496,37 @@ class Engine:
     def _rot_flags(self, centered, floor, plan):
         return (ROTATE_CENTERED if centered else 0) | (ROTATE_FLOOR if floor else 0) | self._ROT_PLAN[plan]
 
-    def rotate_hoisted_ntt(self, c0, c1, keys, ks, k_special, alpha, centered=False, floor=False, outs=None, plan=None, stream=None):
+    def _level_keys(self, keys, size, k_special, alpha, level):
+        """the key check of a call over several keys: whole keys of this context at the top level (level None), _level_key below it"""
+        if level is None:
+            kwords = 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly
+            return all(k is None or size(k) == kwords for k in keys)
+        for k in keys:
+            if k is not None:
+                self._level_key(size(k), k_special, alpha, level)
+        return True
+
+    def rotate_hoisted_ntt(self, c0, c1, keys, ks, k_special, alpha, centered=False, floor=False, outs=None, plan=None, stream=None, level=None):
         """the ciphertext (c0, c1), each an NTT-form [batch, L, n] batch with L = nm - k_special (c0 may be None), rotated by every
         k of ks (odd, at most 16) in one call: for each m the key switch of c1 against keys[m] = [dnum, 2, nm, n], + c0, then the
         NTT-form automorphism by ks[m] -- the permutation last, so the mod-up of c1 is shared.  keys[m] switches from s to
         sigma_(k^-1)(s): a standard Galois key for k becomes it by e.automorphism(key.view(-1, nm, n), kinv, ntt=True).  Returns a
         list of (out0, out1), each [batch, L, n]; `outs` = such a list, else all are views of one new tensor.  plan "sequence" /
         "hoisted" forces a plan.  The first call for a (k_special, alpha), or a larger batch or count, allocates: make it
-        before a graph capture."""
+        before a graph capture.
+        level=l (1 to L): c0, c1 and the results are [batch, l, n], a ciphertext below the top level, and every keys[m] is still the
+        ONE top-level Galois key (or its first ceil(l / alpha) digits at least), read as key_switch_ntt reads its key at a level."""
         L = self.nmoduli - k_special
+        if level is not None:
+            self.level_rows(level, k_special)
+            L = level
         keys, ks = list(keys), [self._k(k) for k in ks]
         if L <= 0 or c1.numel() % (L * self.degree) or not c1.is_contiguous() or (c0 is not None and (c0.shape != c1.shape or not c0.is_contiguous())):
-            raise ValueError("c0 and c1 are contiguous [batch, nm - k_special, n] tensors")
+            raise ValueError("c0 and c1 are contiguous [batch, nm - k_special (or level), n] tensors")
         if len(keys) != len(ks) or not 1 <= len(ks) <= ROTATE_MAX_OUTPUTS:
             raise ValueError("one key per rotation, 1 to 16 rotations")
         batch = c1.numel() // (L * self.degree)
-        kwords = 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly
-        if any(k.numel() != kwords or not k.is_contiguous() for k in keys):
+        if not self._level_keys(keys, lambda k: k.numel(), k_special, alpha, level) or any(not k.is_contiguous() for k in keys):
             raise ValueError("every key holds dnum * 2 polynomials of this context")
         if outs is None:
             both = _torch().empty((len(ks), 2, batch, L, self.degree), dtype=self.torch_dtype, device=c1.device)
@@ -521,19 +535,27 @@ class Engine:
         p1 = (C.c_void_p * len(ks))(*[o[1].data_ptr() for o in outs])
         pk = (C.c_void_p * len(ks))(*[k.data_ptr() for k in keys])
         kv = (C.c_uint64 * len(ks))(*ks)
+        if level is not None:
+            self._chk(self.lib.nflhip_rotate_hoisted_level_ntt_dev(self.ctx, p0, p1, _vp(c0), _vp(c1), pk, kv, len(ks), batch, k_special, alpha, level,
+                                                                   self._rot_flags(centered, floor, plan), self._stream(stream)))
+            return list(outs)
         self._chk(self.lib.nflhip_rotate_hoisted_ntt_dev(self.ctx, p0, p1, _vp(c0), _vp(c1), pk, kv, len(ks), batch, k_special, alpha,
                                                          self._rot_flags(centered, floor, plan), self._stream(stream)))
         return list(outs)
 
-    def h_rotate_hoisted_ntt(self, c0, c1, keys, ks, k_special, alpha, centered=False, floor=False, plan=None):
-        """host-pointer variant: numpy c0 (or None), c1 = [batch, L, n] and keys[m] = [dnum, 2, nm, n] -> a list of (out0, out1)"""
+    def h_rotate_hoisted_ntt(self, c0, c1, keys, ks, k_special, alpha, centered=False, floor=False, plan=None, level=None):
+        """host-pointer variant: numpy c0 (or None), c1 = [batch, L, n] and keys[m] = [dnum, 2, nm, n] -> a list of (out0, out1);
+        level as rotate_hoisted_ntt"""
         c1 = np.ascontiguousarray(c1, dtype=self.np_dtype)
         c0 = None if c0 is None else np.ascontiguousarray(c0, dtype=self.np_dtype)
         keys, ks = [np.ascontiguousarray(k, dtype=self.np_dtype) for k in keys], [self._k(k) for k in ks]
         L = self.nmoduli - k_special
-        kwords = 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly
-        if L <= 0 or c1.size % (L * self.degree) or (c0 is not None and c0.shape != c1.shape) or any(k.size != kwords for k in keys):
-            raise ValueError("c0, c1 are [batch, nm - k_special, n], every key [dnum, 2, nm, n]")
+        if level is not None:
+            self.level_rows(level, k_special)
+            L = level
+        if L <= 0 or c1.size % (L * self.degree) or (c0 is not None and c0.shape != c1.shape) or \
+                not self._level_keys(keys, lambda k: k.size, k_special, alpha, level):
+            raise ValueError("c0, c1 are [batch, nm - k_special (or level), n], every key [dnum, 2, nm, n]")
         if len(keys) != len(ks) or not 1 <= len(ks) <= ROTATE_MAX_OUTPUTS:
             raise ValueError("one key per rotation, 1 to 16 rotations")
         batch = c1.size // (L * self.degree)
@@ -542,6 +564,10 @@ class Engine:
         p1 = (C.c_void_p * len(ks))(*[o[1].ctypes.data for o in outs])
         pk = (C.c_void_p * len(ks))(*[k.ctypes.data for k in keys])
         kv = (C.c_uint64 * len(ks))(*ks)
+        if level is not None:
+            self._chk(self.lib.nflhip_rotate_hoisted_level_ntt(self.ctx, p0, p1, _vp(c0), _vp(c1), pk, kv, len(ks), batch, k_special, alpha, level,
+                                                               self._rot_flags(centered, floor, plan)))
+            return outs
         self._chk(self.lib.nflhip_rotate_hoisted_ntt(self.ctx, p0, p1, _vp(c0), _vp(c1), pk, kv, len(ks), batch, k_special, alpha,
                                                      self._rot_flags(centered, floor, plan)))
         return outs
@@ -595,23 +621,29 @@ class Engine:
     def _lt_flags(self, centered, floor, plan):
         return (LINTRANS_CENTERED if centered else 0) | (LINTRANS_FLOOR if floor else 0) | self._LT_PLAN[plan]
 
-    def linear_transform_ntt(self, c0, c1, keys, weights, ks, k_special, alpha, centered=False, floor=False, out=None, plan=None, stream=None):
+    def linear_transform_ntt(self, c0, c1, keys, weights, ks, k_special, alpha, centered=False, floor=False, out=None, plan=None, stream=None,
+                             level=None):
         """sum_m weights[m] * sigma_ks[m](ciphertext) in one call with ONE mod-down: (c0, c1) NTT-form [batch, L, n] batches with
         L = nm - k_special (c0 may be None); keys[m] = [dnum, 2, nm, n] by the convention of rotate_hoisted_ntt, or None for the
         unrotated diagonal (ks[m] = 1, no key switch); weights[m] = [nm, n], the diagonal in NTT form over all nm moduli (at most
         16 terms).  The key-switch sums are weighted and added on all nm rows before the mod-down, so the words differ from a
         weighted sum of rotate_hoisted_ntt results by that one rounding.  Returns (out0, out1), each [batch, L, n]; `out` = a
         pair of such tensors, else both are views of one new [2, batch, L, n] tensor.  plan "sequence" / "hoisted" forces a
-        plan.  The first call for a (k_special, alpha), or a larger batch or count, allocates: make it before a graph capture."""
+        plan.  The first call for a (k_special, alpha), or a larger batch or count, allocates: make it before a graph capture.
+        level=l (1 to L): c0, c1 and the results are [batch, l, n]; every keys[m] is still the ONE top-level Galois key (or its first
+        ceil(l / alpha) digits at least) and every weights[m] the ONE top-level diagonal [nm, n], of which the rows [l, L) are not
+        read: a diagonal encoded once serves every level, as a key does."""
         L = self.nmoduli - k_special
+        if level is not None:
+            self.level_rows(level, k_special)
+            L = level
         keys, weights, ks = list(keys), list(weights), [self._k(k) for k in ks]
         if L <= 0 or c1.numel() % (L * self.degree) or not c1.is_contiguous() or (c0 is not None and (c0.shape != c1.shape or not c0.is_contiguous())):
-            raise ValueError("c0 and c1 are contiguous [batch, nm - k_special, n] tensors")
+            raise ValueError("c0 and c1 are contiguous [batch, nm - k_special (or level), n] tensors")
         if not (len(keys) == len(weights) == len(ks)) or not 1 <= len(ks) <= LINTRANS_MAX_TERMS:
             raise ValueError("one key (or None) and one weight per term, 1 to 16 terms")
         batch = c1.numel() // (L * self.degree)
-        kwords = 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly
-        if any(k is not None and (k.numel() != kwords or not k.is_contiguous()) for k in keys):
+        if not self._level_keys(keys, lambda k: k.numel(), k_special, alpha, level) or any(k is not None and not k.is_contiguous() for k in keys):
             raise ValueError("every key holds dnum * 2 polynomials of this context")
         if any(w.numel() != self.words_per_poly or not w.is_contiguous() for w in weights):
             raise ValueError("every weight is one polynomial of this context")
@@ -621,22 +653,28 @@ class Engine:
         pk = (C.c_void_p * len(ks))(*[None if k is None else k.data_ptr() for k in keys])
         pw = (C.c_void_p * len(ks))(*[w.data_ptr() for w in weights])
         kv = (C.c_uint64 * len(ks))(*ks)
+        if level is not None:
+            self._chk(self.lib.nflhip_lintrans_level_ntt_dev(self.ctx, _vp(out[0]), _vp(out[1]), _vp(c0), _vp(c1), pk, pw, kv, len(ks), batch, k_special,
+                                                             alpha, level, self._lt_flags(centered, floor, plan), self._stream(stream)))
+            return out
         self._chk(self.lib.nflhip_lintrans_ntt_dev(self.ctx, _vp(out[0]), _vp(out[1]), _vp(c0), _vp(c1), pk, pw, kv, len(ks), batch, k_special,
                                                    alpha, self._lt_flags(centered, floor, plan), self._stream(stream)))
         return out
 
-    def h_linear_transform_ntt(self, c0, c1, keys, weights, ks, k_special, alpha, centered=False, floor=False, plan=None):
+    def h_linear_transform_ntt(self, c0, c1, keys, weights, ks, k_special, alpha, centered=False, floor=False, plan=None, level=None):
         """host-pointer variant: numpy c0 (or None), c1 = [batch, L, n], keys[m] = [dnum, 2, nm, n] or None, weights[m] = [nm, n]
-        -> (out0, out1)"""
+        -> (out0, out1); level as linear_transform_ntt"""
         c1 = np.ascontiguousarray(c1, dtype=self.np_dtype)
         c0 = None if c0 is None else np.ascontiguousarray(c0, dtype=self.np_dtype)
         keys = [None if k is None else np.ascontiguousarray(k, dtype=self.np_dtype) for k in keys]
         weights, ks = [np.ascontiguousarray(w, dtype=self.np_dtype) for w in weights], [self._k(k) for k in ks]
         L = self.nmoduli - k_special
-        kwords = 2 * self.keyswitch_digits(k_special, alpha) * self.words_per_poly
+        if level is not None:
+            self.level_rows(level, k_special)
+            L = level
         if L <= 0 or c1.size % (L * self.degree) or (c0 is not None and c0.shape != c1.shape) or \
-                any(k is not None and k.size != kwords for k in keys) or any(w.size != self.words_per_poly for w in weights):
-            raise ValueError("c0, c1 are [batch, nm - k_special, n], every key [dnum, 2, nm, n] or None, every weight [nm, n]")
+                not self._level_keys(keys, lambda k: k.size, k_special, alpha, level) or any(w.size != self.words_per_poly for w in weights):
+            raise ValueError("c0, c1 are [batch, nm - k_special (or level), n], every key [dnum, 2, nm, n] or None, every weight [nm, n]")
         if not (len(keys) == len(weights) == len(ks)) or not 1 <= len(ks) <= LINTRANS_MAX_TERMS:
             raise ValueError("one key (or None) and one weight per term, 1 to 16 terms")
         batch = c1.size // (L * self.degree)
@@ -644,6 +682,10 @@ class Engine:
         pk = (C.c_void_p * len(ks))(*[None if k is None else k.ctypes.data for k in keys])
         pw = (C.c_void_p * len(ks))(*[w.ctypes.data for w in weights])
         kv = (C.c_uint64 * len(ks))(*ks)
+        if level is not None:
+            self._chk(self.lib.nflhip_lintrans_level_ntt(self.ctx, _vp(out0), _vp(out1), _vp(c0), _vp(c1), pk, pw, kv, len(ks), batch, k_special, alpha,
+                                                         level, self._lt_flags(centered, floor, plan)))
+            return out0, out1
         self._chk(self.lib.nflhip_lintrans_ntt(self.ctx, _vp(out0), _vp(out1), _vp(c0), _vp(c1), pk, pw, kv, len(ks), batch, k_special, alpha,
                                                self._lt_flags(centered, floor, plan)))
         return out0, out1
