@@ -426,6 +426,53 @@ template <class P> class device_batch {
                                                           P::nmoduli, flags, w0.queue()), "linear_transform_level_ntt");
     w0.sync();
   }
+  // BSGS slot linear transforms (include/nflhip.h "BSGS slot linear transforms"): this batch type is the ciphertext's at its level;
+  // bkey_batches[i] / gkey_batches[j] hold the 2 * dnum_L polynomials of a step's top-level Galois key (NULL: the unrotated step),
+  // weight_batches[j * n1 + i] the one top-level diagonal (NULL: the zero diagonal).  Streams as in assign_linear_transform_level.
+  template <size_t K, class Q>
+  static void assign_bsgs_linear_transform(device_batch &out0, device_batch &out1, const device_batch *c0, const device_batch &c1,
+                                           const device_batch<Q> *const *bkey_batches, const uint64_t *bks, size_t n1,
+                                           const device_batch<Q> *const *gkey_batches, const uint64_t *gks, size_t n2,
+                                           const device_batch<Q> *const *weight_batches, size_t alpha, bool centered = false, bool floor = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && K >= 1 && K < Q::nmoduli &&
+                      P::nmoduli <= Q::nmoduli - K,
+                  "assign_bsgs_linear_transform: the keys' ring has the same limbs and degree, K special moduli and at least Lv others");
+    if (alpha == 0 || alpha > Q::nmoduli - K) throw std::runtime_error("nfl(hip): bsgs linear transform: alpha is out of range (1 to the keys' ordinary moduli)");
+    if (n1 == 0 || n1 > NFLHIP_BSGS_MAX_BABY || n2 == 0 || n2 > NFLHIP_BSGS_MAX_GIANT) throw std::runtime_error("nfl(hip): bsgs linear transform: 1 to 16 baby and giant steps");
+    const device_batch<Q> *w0 = nullptr;
+    for (size_t q = 0; q < n1 * n2 && !w0; ++q) w0 = weight_batches[q];
+    if (!w0) throw std::runtime_error("nfl(hip): bsgs linear transform: no diagonal");
+    const void *bp[NFLHIP_BSGS_MAX_BABY], *gp[NFLHIP_BSGS_MAX_GIANT], *wp[NFLHIP_BSGS_MAX_BABY * NFLHIP_BSGS_MAX_GIANT];
+    if ((c0 && c0->size() != c1.size()) || out0.size() != c1.size() || out1.size() != c1.size()) throw std::runtime_error("nfl(hip): batch sizes differ");
+    if ((c0 && c0->device() != w0->device()) || c1.device() != w0->device() || out0.device() != w0->device() || out1.device() != w0->device())
+      throw std::runtime_error("nfl(hip): bsgs linear transform operands on different devices");
+    for (size_t m = 0; m < n1 + n2; ++m) {
+      const device_batch<Q> *kb = m < n1 ? bkey_batches[m] : gkey_batches[m - n1];
+      if (kb && kb->size() != 2 * ((Q::nmoduli - K + alpha - 1) / alpha)) throw std::runtime_error("nfl(hip): a key batch holds the 2 * dnum polynomials of the top level");
+      if (kb && kb->device() != w0->device()) throw std::runtime_error("nfl(hip): bsgs linear transform operands on different devices");
+      (m < n1 ? bp[m] : gp[m - n1]) = kb ? kb->data() : nullptr;
+    }
+    for (size_t q = 0; q < n1 * n2; ++q) {
+      const device_batch<Q> *wb = weight_batches[q];
+      if (wb && wb->size() != 1) throw std::runtime_error("nfl(hip): a weight batch holds one polynomial");
+      if (wb && wb->device() != w0->device()) throw std::runtime_error("nfl(hip): bsgs linear transform operands on different devices");
+      wp[q] = wb ? wb->data() : nullptr;
+    }
+    c1.sync();
+    c1.strict("bsgs linear transform");
+    if (c0) c0->strict("bsgs linear transform");
+    for (size_t m = 0; m < n1 + n2; ++m) {
+      const device_batch<Q> *kb = m < n1 ? bkey_batches[m] : gkey_batches[m - n1];
+      if (kb) kb->strict("bsgs linear transform");
+    }
+    for (size_t q = 0; q < n1 * n2; ++q)
+      if (weight_batches[q]) weight_batches[q]->strict("bsgs linear transform");
+    const int flags = (centered ? NFLHIP_BSGS_CENTERED : 0) | (floor ? NFLHIP_BSGS_FLOOR : 0);
+    const void *const p0 = c0 ? c0->d_ : nullptr;
+    detail::check(w0->ctx(), nflhip_bsgs_ntt_dev(w0->ctx(), out0.d_, out1.d_, p0, c1.d_, bp, bks, n1, gp, gks, n2, wp, c1.n_, K, alpha,
+                                                 P::nmoduli, flags, w0->queue()), "bsgs_linear_transform_ntt");
+    w0->sync();
+  }
   // Sums of products across polynomials (include/nflhip.h): this batch holds `groups` polynomials, a and b groups * terms each,
   // term-minor: (*this)[g] = sum_j a[g * terms + j] * b[g * terms + j].  assign_matvec: v holds the `terms` polynomials every
   // group shares, (*this)[g] = sum_j m[g * terms + j] * v[j].  The operands must be other batches.

@@ -689,6 +689,58 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out1._p = d1;
   }
 
+  // BSGS slot linear transforms (nfl::bsgs_linear_transform_ntt<K> below; include/nflhip.h "BSGS slot linear transforms").  This ring type
+  // is the KEYS' and the diagonals'; the level is the operands' LO.  bkeys[i] / gkeys[j]: the 2 * dnum_L polynomials of a step's top-level
+  // Galois key, or NULL for the unrotated step; weights[j * n1 + i]: the top-level diagonal, or NULL for the zero diagonal.  Gathered as
+  // linear_transform_level_into gathers: of every key the 2 * dnum_l live polynomials, every diagonal whole; the baby keys first, then
+  // the giant keys, then the diagonals.  Never fused into a queue's rewrites.
+  template <size_t K, size_t LO> static void bsgs_into(poly_p<T, Degree, LO> &out0, poly_p<T, Degree, LO> &out1, poly_p<T, Degree, LO> const *c0,
+                                                       poly_p<T, Degree, LO> const &c1, poly_p const *const *bkeys, const uint64_t *bks, size_t n1,
+                                                       poly_p const *const *gkeys, const uint64_t *gks, size_t n2, poly_p const *const *weights,
+                                                       size_t alpha, bool centered, bool floor) {
+    static_assert(K >= 1 && K < NbModuli && LO >= 1 && LO <= NbModuli - K, "nfl::bsgs_linear_transform_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+    typedef poly_p<T, Degree, LO> out_t;
+    if (alpha == 0 || alpha > NbModuli - K) throw std::runtime_error("nfl(hip): bsgs_linear_transform_ntt: alpha is out of range (1 to the key ring's ordinary moduli)");
+    if (n1 == 0 || n1 > NFLHIP_BSGS_MAX_BABY || n2 == 0 || n2 > NFLHIP_BSGS_MAX_GIANT) throw std::runtime_error("nfl(hip): bsgs_linear_transform_ntt: 1 to 16 baby and giant steps");
+    const size_t klive = 2 * ((LO + alpha - 1) / alpha), pb = sizeof(T) * Degree * NbModuli, nkeys = n1 + n2, nw = n1 * n2;
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    typename out_t::ptr_type s0 = c0 ? c0->_p : typename out_t::ptr_type(), s1 = c1._p;  // (hold the inputs while the launches are enqueued)
+    typename out_t::ptr_type d0 = out_t::fresh(), d1 = out_t::fresh();
+    std::vector<ptr_type> held;  // (klive slots per key, a NULL key's left empty; then one slot per diagonal, a NULL one's left empty)
+    for (size_t m = 0; m < nkeys; ++m) {
+      poly_p const *key = m < n1 ? bkeys[m] : gkeys[m - n1];
+      for (size_t t = 0; t < klive; ++t) {
+        if (key && !key[t]._p) throw std::runtime_error("nfl(hip): a live key polynomial is empty (moved from)");
+        held.push_back(key ? key[t]._p : ptr_type());
+      }
+    }
+    for (size_t q = 0; q < nw; ++q) held.push_back(weights[q] ? weights[q]->_p : ptr_type());
+    const void *p0 = c0 ? s0->dev_ro() : nullptr, *p1 = s1->dev_ro();
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo();
+    void *kgat = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &kgat, held.size() * pb), "bsgs_linear_transform_ntt");
+    const void *kp[NFLHIP_BSGS_MAX_BABY + NFLHIP_BSGS_MAX_GIANT], *wp[NFLHIP_BSGS_MAX_BABY * NFLHIP_BSGS_MAX_GIANT];
+    int rc = NFLHIP_OK;
+    for (size_t t = 0; t < held.size() && rc == NFLHIP_OK; ++t)
+      if (held[t]) rc = nflhip_memcpy_d2d(ctx_t::get(), static_cast<char *>(kgat) + t * pb, held[t]->dev_ro(), pb, ctx_t::queue());
+    for (size_t m = 0; m < nkeys; ++m) kp[m] = held[m * klive] ? static_cast<char *>(kgat) + m * klive * pb : nullptr;
+    for (size_t q = 0; q < nw; ++q) wp[q] = held[nkeys * klive + q] ? static_cast<char *>(kgat) + (nkeys * klive + q) * pb : nullptr;
+    if (rc == NFLHIP_OK) rc = nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue());
+    const int flags = (centered ? NFLHIP_BSGS_CENTERED : 0) | (floor ? NFLHIP_BSGS_FLOOR : 0);
+    if (rc == NFLHIP_OK) rc = nflhip_bsgs_ntt_dev(ctx_t::get(), o0, o1, p0, p1, kp, bks, n1, kp + n1, gks, n2, wp, 1, K, alpha, LO, flags, ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered keys go)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), kgat);
+      throw std::runtime_error("nfl(hip): bsgs_linear_transform_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), kgat);
+    detail::check(ctx_t::get(), rs, "bsgs_linear_transform_ntt");
+    out0._p = d0;
+    out1._p = d1;
+  }
+
   // The tensor product (nfl::tensor_ntt below): the deferred queue of this ring type runs first, then one launch on its stream.  The
   // results get payloads of their own, so an output may be an input and copy-on-write sharers of the outputs' old values keep them.
   static void tensor_into(poly_p &out0, poly_p &out1, poly_p &out2, poly_p const &a0, poly_p const &a1, poly_p const *b0, poly_p const *b1) {
@@ -1277,6 +1329,44 @@ void linear_transform_level_ntt(poly_p<T, D, Lv> &out0, poly_p<T, D, Lv> &out1, 
                                 poly_p<T, D, M> const *const *keys, poly_p<T, D, M> const *const *weights, const uint64_t *ks, size_t count,
                                 size_t alpha, bool centered = false, bool floor = false) {
   poly_p<T, D, M>::template linear_transform_level_into<K, Lv>(out0, out1, c0, c1, keys, weights, ks, count, alpha, centered, floor);
+}
+
+/* BSGS slot linear transforms (include/nflhip.h "BSGS slot linear transforms"): sum_j sigma_{gks[j]}(sum_i weights[j * n1 + i] (.)
+ * sigma_{bks[i]}(c0, c1)) in one call with ONE mod-down of two polynomials.  The level comes from the operand types (Lv = M - K is the
+ * top); bkeys[i] / gkeys[j] point to the 2 * dnum_L polynomials of a step's top-level Galois key, or are NULL for the unrotated step
+ * (k = 1); weights[j * n1 + i] points to the top-level diagonal, or is NULL for the zero diagonal.  c0 may be NULL; an output may be an
+ * input.  On poly through the staged host entry; on poly_p on the resident values, gathered as linear_transform_level_ntt gathers. */
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void bsgs_linear_transform_ntt(poly<T, D, Lv> &out0, poly<T, D, Lv> &out1, poly<T, D, Lv> const *c0, poly<T, D, Lv> const &c1,
+                               poly<T, D, M> const *const *bkeys, const uint64_t *bks, size_t n1, poly<T, D, M> const *const *gkeys, const uint64_t *gks,
+                               size_t n2, poly<T, D, M> const *const *weights, size_t alpha, bool centered = false, bool floor = false) {
+  static_assert(K >= 1 && K < M && Lv >= 1 && Lv <= M - K, "nfl::bsgs_linear_transform_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+  typedef poly<T, D, Lv> S;
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  if (n1 == 0 || n1 > NFLHIP_BSGS_MAX_BABY || n2 == 0 || n2 > NFLHIP_BSGS_MAX_GIANT) throw std::runtime_error("nfl(hip): bsgs_linear_transform_ntt: 1 to 16 baby and giant steps");
+  const void *bp[NFLHIP_BSGS_MAX_BABY], *gp[NFLHIP_BSGS_MAX_GIANT], *wp[NFLHIP_BSGS_MAX_BABY * NFLHIP_BSGS_MAX_GIANT];
+  for (size_t i = 0; i < n1; ++i) bp[i] = bkeys[i] ? bkeys[i]->cdata() : nullptr;
+  for (size_t j = 0; j < n2; ++j) gp[j] = gkeys[j] ? gkeys[j]->cdata() : nullptr;
+  for (size_t q = 0; q < n1 * n2; ++q) wp[q] = weights[q] ? weights[q]->cdata() : nullptr;
+  S *t0 = S::make_temp(), *t1 = S::make_temp();  // (an output may be an input)
+  const int flags = (centered ? NFLHIP_BSGS_CENTERED : 0) | (floor ? NFLHIP_BSGS_FLOOR : 0);
+  const int rc = nflhip_bsgs_ntt(P::ctx(), t0->data(), t1->data(), c0 ? c0->cdata() : nullptr, c1.cdata(), bp, bks, n1, gp, gks, n2, wp, 1, K, alpha, Lv,
+                                 flags);
+  if (rc == 0) {
+    std::memcpy(static_cast<void *>(out0.data()), t0->cdata(), sizeof(S));
+    std::memcpy(static_cast<void *>(out1.data()), t1->cdata(), sizeof(S));
+  }
+  S::drop_temp(t0);
+  S::drop_temp(t1);
+  detail::check(P::ctx(), rc, "bsgs_linear_transform_ntt");
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t M>
+void bsgs_linear_transform_ntt(poly_p<T, D, Lv> &out0, poly_p<T, D, Lv> &out1, poly_p<T, D, Lv> const *c0, poly_p<T, D, Lv> const &c1,
+                               poly_p<T, D, M> const *const *bkeys, const uint64_t *bks, size_t n1, poly_p<T, D, M> const *const *gkeys,
+                               const uint64_t *gks, size_t n2, poly_p<T, D, M> const *const *weights, size_t alpha, bool centered = false,
+                               bool floor = false) {
+  poly_p<T, D, M>::template bsgs_into<K, Lv>(out0, out1, c0, c1, bkeys, bks, n1, gkeys, gks, n2, weights, alpha, centered, floor);
 }
 
 /* Sums of products across polynomials (include/nflhip.h): out = sum_{j < terms} a[j] * b[j], element-wise in every row -- the

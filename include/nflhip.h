@@ -682,6 +682,104 @@ int nflhip_lintrans_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const
                               const void *const *h_keys, const void *const *h_weights, const uint64_t *ks, size_t count, size_t batch,
                               size_t k_special, size_t alpha, size_t level, int flags);   /* staged host variant */
 
+/* ---- weighted sums of automorphisms into several outputs --------------------------------------
+ * nflhip_automorphism_mac_dev for `outputs` outputs that share the inputs and the multipliers -- the inner sums of the giant steps of
+ * a BSGS matrix-vector product, which all read the same permuted baby-step sums:
+ *     out_o[g][r][x] = addend_o[g][r][x] + sum_{t < terms} w_{o,t}[r][x] * in_t[g][r][src_{k_t}(x)]      mod p_r, canonical,
+ * o < outputs <= NFLHIP_MAC_MULTI_MAX_OUTPUTS, terms <= NFLHIP_MAC_MAX_TERMS, g < batch, r < rows <= nmoduli.
+ *   ins[t], ks[t]             shared by every output, as nflhip_automorphism_mac_dev takes them
+ *   weights[o * terms + t]    [>= rows][degree], or NULL: the zero weight, for which nothing is read
+ *   addends                   NULL, or addends[o] NULL or exactly outs[o]
+ * All four arrays are HOST arrays; the pointers travel by value in the kernel arguments, nothing is allocated and the call can be
+ * captured.  By definition the words are those of `outputs` calls of nflhip_automorphism_mac_dev (an output whose weights are all
+ * NULL is its addend, or zero).  A term's source chunk is staged and read permuted ONCE for the outputs of a launch.  flags: 0.
+ * NFLHIP_ERR_INVALID, nothing enqueued: what nflhip_automorphism_mac_dev refuses, outputs == 0 or > 16, an addend that is neither
+ * NULL nor its output, ANY overlap of an output with an input, a weight or another output.  batch == 0 returns NFLHIP_OK.
+ * The host variant stages every input, every weight, the addends and the outputs. */
+#define NFLHIP_MAC_MULTI_MAX_OUTPUTS 16
+int nflhip_automorphism_mac_multi_dev(nflhip_ctx *ctx, void *const *d_outs, const void *const *d_addends, const void *const *d_ins,
+                                      const void *const *d_weights, const uint64_t *ks, size_t outputs, size_t terms, size_t batch,
+                                      size_t rows, int flags, void *stream);
+int nflhip_automorphism_mac_multi(nflhip_ctx *ctx, void *const *h_outs, const void *const *h_addends, const void *const *h_ins,
+                                  const void *const *h_weights, const uint64_t *ks, size_t outputs, size_t terms, size_t batch,
+                                  size_t rows, int flags);   /* staged host variant */
+
+/* ---- BSGS slot linear transforms: giant steps before the one mod-down ---------------------------
+ * sum_j sigma_{g_j}( sum_i pt_{j,i} (.) sigma_{b_i}(ct) ) for n1 baby steps b_i and n2 giant steps g_j in one call: a matrix-vector
+ * product by n1 n2 diagonals with n1 + n2 Galois keys.  The babies' key-switch sums do not depend on the giant step, the giant step's
+ * key switch acts on sums that are still on all rows, and ONE mod-down of two polynomials closes the call (double hoisting taken to
+ * its end).  The context, K = k_special, alpha, the digit rule and the level rule are those of "hybrid key switching" and "leveled key
+ * switching"; nm_l = level + K rows are live.
+ *   level         l, 1 <= l <= L = nmoduli - K; l = L is the top level
+ *   c0, c1, out0, out1   [batch][l][degree], NTT form; c0 may be NULL
+ *   bkeys[i], bks[i]     i < n1 <= NFLHIP_BSGS_MAX_BABY: bks[i] odd; bkeys[i] the top-level Galois key [dnum_L][2][nmoduli][degree] by the
+ *                 convention of the hoisted rotations (from s to sigma_(k^-1)(s), the permutation last), or NULL for the unrotated
+ *                 baby step, which requires bks[i] = 1 mod 2 degree
+ *   gkeys[j], gks[j]     j < n2 <= NFLHIP_BSGS_MAX_GIANT: likewise; NULL is the unrotated giant step
+ *   weights[j n1 + i]    the top-level diagonal [nmoduli][degree] in NTT form, pre-rotated by sigma_{g_j}^-1 by the caller as every BSGS
+ *                 does; NULL is the zero diagonal and nothing is read for it.  Every j has at least one non-NULL weight
+ * Keys and weights are read as the level entries read them: rows phys(r) of the live rows and the first dnum_l digits only.
+ * Definition, word for word ("mod-down": nflhip_moddown_ntt_dev(., K) on the level context, rounding or NFLHIP_BSGS_FLOOR; "mod-up" and
+ * the key-switch sums: those of nflhip_keyswitch_ntt_dev, fast or NFLHIP_BSGS_CENTERED):
+ *     U_d      the mod-up of c1, every digit                                               (nm_l rows)   once
+ *     S_{i,c}  = sum_d U_d (.) bkeys[i][d][c]                        keyed i, c = 0, 1          (nm_l rows)
+ *     per giant step j:
+ *       V_{j,c} = sum_{keyed i} w_{j,i} (.) sigma^NTT_{b_i}(S_{i,c})                                (nm_l rows; zero with no keyed i)
+ *       W_{j,0} = sum_{all i}   w_{j,i} (.) sigma^NTT_{b_i}(c0)            (absent when c0 is NULL)  (l rows)
+ *       W_{j,1} = sum_{unkeyed i} w_{j,i} (.) c1                                                 (l rows)
+ *       gkeys[j] non-NULL:
+ *         v_j     = mod-down(V_{j,1}) + W_{j,1}                     (the mod-down skipped with no keyed i)   (l rows)
+ *         T_{j,c} = sum_d mod-up(v_j)_d (.) gkeys[j][d][c]                                       (nm_l rows)
+ *         A_0 += sigma^NTT_{g_j}(V_{j,0} + T_{j,0});   A_1 += sigma^NTT_{g_j}(T_{j,1});   O_0 += sigma^NTT_{g_j}(W_{j,0})
+ *       gkeys[j] NULL:
+ *         A_c += V_{j,c};   O_0 += W_{j,0};   O_1 += W_{j,1}
+ *     out_c = mod-down(A_c) + O_c                                   canonical, row by row mod p_r
+ * Every sum is exact mod p_r, so the order of the additions does not matter and both plans give the same words.
+ * It is a BSGS product: out0 + out1 s = sum_j sigma_{g_j}(sum_i pt_{j,i} sigma_{b_i}(c0 + c1 s)) + e with |e| at most
+ * n2 kb n T B + kg B + (kg + 1)(n + 1), B the bound of one key switch, kb / kg the keyed babies / giants, T = |pt|_inf
+ * (tests/test_bsgs_cpu.py).
+ * Plans, same words; `flags` may carry at most one plan flag:
+ *   NFLHIP_BSGS_SEQUENCE  the map through existing entries only: nflhip_baseconv_ntt_dev per digit, nflhip_dot_dev,
+ *                         nflhip_automorphism_dev, nflhip_automorphism_mac_dev, the element-wise addition (nflhip_pointwise_dev),
+ *                         nflhip_moddown_ntt_dev; out_c is a device copy of the sum.  No kernel of its own: the cross-check.
+ *                         NFLHIP_ERR_UNSUPPORTED, nothing enqueued, where batch polynomials are no whole number of 16-byte groups
+ *                         (rows under 16 bytes), which the element-wise addition does not serve.
+ *   NFLHIP_BSGS_HOISTED   the mod-up of c1 once; ONE k_dot_multi launch for every S; the giant steps in groups of 4: the several-output
+ *                         weighted-sum kernel for the group's V (both components in one grid), ONE mod-down over the group's V_{.,1},
+ *                         W_{.,1} added on l rows, ONE mod-up over group * batch polynomials, the inner products with V_{j,0} as the
+ *                         addend of T_{j,0}, one weightless permute-and-accumulate into A_c; after the last group one mod-down of A
+ *                         into out0 / out1 and the passes on l rows.  Whatever has no term is skipped.
+ *   none                  hoisted.
+ * Scratch, context-owned (per level), in polynomials of nm_l rows (p) and of l rows (q), G = min(4, giants of one kind): hoisted
+ *     batch (1 p | 1 q) + batch dnum p [U] + 2 kb batch p [S] + 2 batch p [A] + 2 G batch p [V, T] + G batch q [v]
+ *     + G batch (1 p | 1 q) + G batch dnum p [the giants' mod-up] + n2 batch q [W_{.,0}];
+ * the sequence batch (2 dnum + 2 kb + 9) p + 7 batch q at most.  G = 4 bounds the giants' share of the scratch at four
+ * ciphertexts' worth of digits whatever n2 is, and is a whole number of the several-output kernel's launches.
+ * The first call for a (k_special, alpha, level, plan, modes) and kinds of steps (keyed babies or none, keyed giants or none, c0 or
+ * none), or for a larger batch, more keyed babies or more giants, builds tables and allocates (it synchronises): make
+ * it before capturing into a hipGraph; while capturing it is NFLHIP_ERR_UNSUPPORTED, nothing is enqueued and the stream stays usable.
+ * Calls on different streams are ordered on the scratch by an event.
+ * NFLHIP_ERR_INVALID, nothing enqueued: a NULL context, a NULL pointer with batch != 0 (except c0, a key with k = 1 mod 2 degree and a
+ * weight), n1 or n2 of 0 or above 16, an even k, a NULL key with another k, a giant step without a weight, k_special, alpha or level out
+ * of range, unknown flag bits or two plan flags, a size that overflows, out0 overlapping out1, an output overlapping c0, c1, the live
+ * digits of a key or a weight, a cyclic row context, a repeated modulus inside a digit or among the special rows.
+ * batch == 0 returns NFLHIP_OK and touches nothing.  The host variant stages c0, c1, the live digits of every key, every weight and
+ * both outputs. */
+#define NFLHIP_BSGS_MAX_BABY 16
+#define NFLHIP_BSGS_MAX_GIANT 16
+#define NFLHIP_BSGS_CENTERED 0x100
+#define NFLHIP_BSGS_FLOOR 0x200
+#define NFLHIP_BSGS_SEQUENCE 0x1000
+#define NFLHIP_BSGS_HOISTED 0x2000
+int nflhip_bsgs_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_c0, const void *d_c1, const void *const *d_bkeys,
+                        const uint64_t *bks, size_t n1, const void *const *d_gkeys, const uint64_t *gks, size_t n2,
+                        const void *const *d_weights, size_t batch, size_t k_special, size_t alpha, size_t level, int flags,
+                        void *stream);
+int nflhip_bsgs_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_c0, const void *h_c1, const void *const *h_bkeys,
+                    const uint64_t *bks, size_t n1, const void *const *h_gkeys, const uint64_t *gks, size_t n2,
+                    const void *const *h_weights, size_t batch, size_t k_special, size_t alpha, size_t level,
+                    int flags);   /* staged host variant */
+
 /* ---- element-wise ops: poly::operator=(expr) core.hpp:24-37 ------------------
  * op in NFLHIP_OP_*; b is ignored for COMPUTE_SHOUP, bprime only used by
  * MUL_SHOUP.  Input contract as the reference's (operands < p; ops.hpp:131,148,211). */

@@ -34,6 +34,9 @@ ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_SEQUENCE, ROTATE_HOISTED = 0x100, 0x200, 0
 MAC_MAX_TERMS, MAC_DOUBLE_BUFFER = 16, 0x1
 LINTRANS_MAX_TERMS = 16
 LINTRANS_CENTERED, LINTRANS_FLOOR, LINTRANS_SEQUENCE, LINTRANS_HOISTED = 0x100, 0x200, 0x1000, 0x2000
+MAC_MULTI_MAX_OUTPUTS = 16
+BSGS_MAX_BABY, BSGS_MAX_GIANT = 16, 16
+BSGS_CENTERED, BSGS_FLOOR, BSGS_SEQUENCE, BSGS_HOISTED = 0x100, 0x200, 0x1000, 0x2000
 MULRELIN_CENTERED, MULRELIN_FLOOR, MULRELIN_RESCALE, MULRELIN_FUSED, MULRELIN_SEQUENCE, MULRELIN_MERGED = 0x100, 0x200, 0x400, 0x800, 0x1000, 0x2000
 
 
@@ -104,6 +107,10 @@ SYMBOLS = [
     ("nflhip_rotate_hoisted_level_ntt", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _sz, _i]),
     ("nflhip_lintrans_level_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _sz, _i, _vp]),
     ("nflhip_lintrans_level_ntt", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _sz, _i]),
+    ("nflhip_automorphism_mac_multi_dev", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_automorphism_mac_multi", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i]),
+    ("nflhip_bsgs_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, C.POINTER(_vp), C.POINTER(_u64), _sz, C.POINTER(_vp), _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_bsgs_ntt", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, C.POINTER(_vp), C.POINTER(_u64), _sz, C.POINTER(_vp), _sz, _sz, _sz, _sz, _i]),
     ("nflhip_gadget_mul_dev", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("nflhip_pointwise_dev", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     ("nflhip_pointwise", _i, [_vp, _i, _vp, _vp, _vp, _vp, _sz]),

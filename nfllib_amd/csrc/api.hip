@@ -544,7 +544,7 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   for (Workspace *w : {&ctx->resc_ws, &ctx->bcn_ws[0], &ctx->bcn_ws[1]}) ws_free(*w);
   for (auto &kv : ctx->bconv) (void)hipFree(kv.second);
   ctx->bconv.clear();
-  for (Workspace *w : {&ctx->rot_ws, &ctx->lt_ws, &ctx->mr_ws}) ws_free(*w);
+  for (Workspace *w : {&ctx->rot_ws, &ctx->lt_ws, &ctx->bsgs_ws, &ctx->mr_ws}) ws_free(*w);
   for (auto &kv : ctx->mr_pi) (void)hipFree(kv.second);
   ctx->mr_pi.clear();
   ws_free(ctx->ks_ws);
@@ -1430,6 +1430,22 @@ int nflhip_automorphism_mac_dev(nflhip_ctx *ctx, void *d_out, const void *d_adde
   if (e != hipSuccess) return hipfail(ctx, e, "automorphism_mac");
   return NFLHIP_OK;
 }
+// The same for several outputs that share the inputs (kernels_bsgs.hip; include/nflhip.h "weighted sums of automorphisms into several
+// outputs"): one launch per kMacMultiJB outputs, the pointers in the kernel arguments, nothing allocated.
+int nflhip_automorphism_mac_multi_dev(nflhip_ctx *ctx, void *const *d_outs, const void *const *d_addends, const void *const *d_ins,
+                                      const void *const *d_weights, const uint64_t *ks, size_t outputs, size_t terms, size_t batch, size_t rows,
+                                      int flags, void *stream) {
+  int rc = mac_multi_check(ctx, d_outs, d_addends, d_ins, d_weights, ks, outputs, terms, batch, rows, flags);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_permute_mac_multi_ntt<T>(ctx->shape, ctx->tabs, (T *const *)d_outs, (const T *const *)d_addends, (const T *const *)d_ins,
+                                           (const T *const *)d_weights, ks, (int)outputs, (int)terms, batch, rows, 1, 0, 0, (hipStream_t)stream);
+  });
+  if (e != hipSuccess) return hipfail(ctx, e, "automorphism_mac_multi");
+  return NFLHIP_OK;
+}
 
 // Slot linear transforms (kernels_lintrans.hip; include/nflhip.h "slot linear transforms"): the key-switch sums of one c1 against up to
 // 16 keys, each permuted, multiplied by its plaintext diagonal and added up WHILE STILL ON ALL nm ROWS, then ONE mod-down of the two
@@ -1818,6 +1834,303 @@ int nflhip_lintrans_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, c
   if ((rc = level_context(ctx, k_special, level, (hipStream_t)stream, &run, &kl))) return rc;
   return lintrans_run(run, d_out0, d_out1, d_c0, d_c1, d_keys, d_weights, ks, count, batch, k_special, std::min(alpha, level), flags,
                       (hipStream_t)stream, run == ctx ? nullptr : &kl);
+}
+
+// BSGS slot linear transforms (kernels_bsgs.hip; include/nflhip.h "BSGS slot linear transforms", which states the map): n1 baby steps
+// whose key-switch sums S are formed ONCE, n2 giant steps whose inner sums V_j are weighted sums of the permuted S on all rows, the
+// giant step's key switch on mod-down(V_{j,1}) + W_{j,1}, its permutation accumulated into A on all rows, ONE mod-down of A.  ctx is
+// the context the call runs on: the level context below the top, with the keys and the weights in its parent's layout (kl), as
+// lintrans_run.  Two plans with the same words:
+//   sequence  per giant step, through public entries only: the per-digit mod-up, dot_key, nflhip_automorphism_dev + a one-term dot per
+//             (i, c) for V, nflhip_automorphism_mac_dev on the kept rows for W, nflhip_moddown_ntt_dev, nflhip_pointwise_dev for the
+//             sums, also Y_c + O_c in the scratch, from where out_c is a device copy (the outputs may have any alignment, which
+//             nflhip_pointwise_dev does not serve)
+//   hoisted   the mod-up of c1 and k_dot_multi once; giants of one kind (keyed, then unkeyed) in groups of kBsgsGroup:
+//             k_permute_mac_multi_ntt into V = [2][cnt][batch] (blockIdx.y the component), one mod-down of V_1 into v = [cnt][batch],
+//             k_permute_mac_multi_ntt on the kept rows adds W_{.,1} in place, one modup_run over cnt * batch polynomials, dot_key per
+//             (j, c) in place of V (V_{j,0} the addend of T_{j,0}), k_permute_sum_ntt into A; then moddown_pair and the passes on the
+//             kept rows: k_permute_mac_multi_ntt on c0 for every W_{j,0}, k_permute_sum_ntt into out0, k_permute_mac_ntt of the unkeyed
+//             giants' W_{j,1} into out1
+// Default: hoisted.  Lock order: bsgs_mu, then ks_mu, then bcn_mu.
+static constexpr size_t kBsgsGroup = 4;
+static int bsgs_run(nflhip_ctx *ctx, void *out0, void *out1, const void *c0, const void *c1, const void *const *bkeys, const uint64_t *bks, size_t n1,
+                    const void *const *gkeys, const uint64_t *gks, size_t n2, const void *const *weights, size_t batch, size_t K, size_t alpha,
+                    int flags, hipStream_t st, const KeyLevel *kl) {
+  std::lock_guard<std::mutex> lk(ctx->bsgs_mu);
+  const size_t nm = ctx->shape.nm, L = nm - K, dnum = (L + alpha - 1) / alpha, row = ctx->shape.n * ctx->word, pb = nm * row, qb = L * row;
+  const size_t pw = pb / ctx->word;  // words of a polynomial of nm rows
+  const bool centred = (flags & NFLHIP_BSGS_CENTERED) != 0, floor = (flags & NFLHIP_BSGS_FLOOR) != 0, cap = is_capturing(st);
+  const int mdflags = floor ? NFLHIP_MODDOWN_FLOOR : 0;
+  const uint64_t *const *recs = nullptr;
+  int rc;
+  {  // the tables first: a repeated modulus is refused with the builder's message before anything is enqueued
+    std::lock_guard<std::mutex> l2(ctx->ks_mu);
+    rc = keyswitch_records(ctx, K, alpha, st, &recs);
+  }
+  if (rc) return rc;
+  // the steps by kind, in order
+  size_t kbi[NFLHIP_BSGS_MAX_BABY], ubi[NFLHIP_BSGS_MAX_BABY], kgj[NFLHIP_BSGS_MAX_GIANT], ugj[NFLHIP_BSGS_MAX_GIANT];
+  size_t kb = 0, ub = 0, kg = 0, ug = 0;
+  for (size_t i = 0; i < n1; ++i) (bkeys[i] ? kbi[kb++] : ubi[ub++]) = i;
+  for (size_t j = 0; j < n2; ++j) (gkeys[j] ? kgj[kg++] : ugj[ug++]) = j;
+  int plan = flags & (NFLHIP_BSGS_SEQUENCE | NFLHIP_BSGS_HOISTED);
+  if (!plan) plan = NFLHIP_BSGS_HOISTED;
+  const bool seq = plan == NFLHIP_BSGS_SEQUENCE, sums = kb || kg;  // sums: something lives on all rows and is modded down at the end
+  // (the sequence adds with nflhip_pointwise_dev, which serves whole 16-byte groups: every scratch region is then 16-byte aligned too)
+  if (seq && ((batch * pb) | (batch * qb)) % 16)
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "bsgs: the sequence plan adds element-wise on whole 16-byte groups; this batch of rows this short is served by the hoisted plan");
+  const int modes = flags & (NFLHIP_BSGS_CENTERED | NFLHIP_BSGS_FLOOR);
+  const size_t G = seq ? 1 : std::min(kBsgsGroup, std::max(kg, kb ? ug : (size_t)0)), Gk = seq ? (kg ? 1 : 0) : std::min(kBsgsGroup, kg);
+  const size_t down = !sums ? 0 : seq || moddown_pair_adjacent(ctx, out0, out1, batch, K) ? 2 * batch : batch;
+  // what a call while capturing may do: repeat a (k_special, alpha, plan, modes, kinds of steps) already served at these sizes or larger
+  const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes | (kb ? 1 : 0) | (kg ? 2 : 0) | (c0 ? 4 : 0))},
+                              wsizes = {batch, std::max(Gk, (size_t)1) * batch, down};
+  if (cap && !warm_covers(ctx->bsgs_warm, wkey, wsizes))
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "bsgs: the first call for a (k_special, alpha, level, plan), or for larger sizes, allocates, which a stream capture cannot do");
+  const ModupRoute route = seq ? kModupPerDigit : modup_default_route(ctx);
+  // the regions, in order: X U S A V v X2 U2 W, then (sequence) P T Pq O0 O1 Y
+  const size_t xb = kb ? modup_x_bytes(ctx, route, batch, L) : 0, ub_ = kb ? batch * dnum * pb : 0, sb = 2 * kb * batch * pb;
+  const size_t ab = sums ? 2 * batch * pb : 0, vb = kb || !seq ? 2 * G * batch * pb : 0, vq = Gk * batch * qb;
+  const size_t x2b = Gk ? modup_x_bytes(ctx, route, Gk * batch, L) : 0, u2b = Gk * batch * dnum * pb, wqb = c0 ? (seq ? 1 : n2) * batch * qb : 0;
+  const size_t seqb = seq ? 3 * batch * pb + 5 * batch * qb : 0;
+  if ((rc = set_device(ctx))) return rc;
+  nflhip_ctx *child = nullptr;
+  if ((rc = kept_rows_child(ctx, L, cap, &child)) ||
+      (rc = ws_begin(ctx, ctx->bsgs_ws, xb + ub_ + sb + ab + vb + vq + x2b + u2b + wqb + seqb, cap, st, "bsgs: the")))
+    return rc;
+  char *X = (char *)ctx->bsgs_ws.buf, *U = X + xb, *S = U + ub_, *A = S + sb, *V = A + ab, *v = V + vb, *X2 = v + vq, *U2 = X2 + x2b, *W = U2 + u2b;
+  auto wt = [&](size_t j, size_t i) { return weights[j * n1 + i]; };
+  nflhip_dot_operand u;  // the digits of c1
+  if (kb) {
+    if ((rc = modup_copy_in(ctx, route, X, c1, batch, L, st))) return rc;
+    if ((rc = modup_run(ctx, child, route, U, X, recs, batch, L, alpha, centred, "bsgs", st, &u))) return rc;
+  }
+  bool a_init = false, o0_init = false, o1_init = false;
+  if (seq) {
+    char *P = W + wqb, *T = P + batch * pb, *Pq = T + 2 * batch * pb, *O0 = Pq + batch * qb, *O1 = O0 + batch * qb, *Y = O1 + batch * qb;
+    const void *cin[NFLHIP_BSGS_MAX_BABY], *cw[NFLHIP_BSGS_MAX_BABY];
+    uint64_t cks[NFLHIP_BSGS_MAX_BABY];
+    for (size_t m = 0; m < kb; ++m)
+      for (size_t c = 0; c < 2; ++c)
+        if ((rc = dot_key(ctx, S + (2 * m + c) * batch * pb, &u, bkeys[kbi[m]], c, nullptr, batch, dnum, kl, st))) return rc;
+    // acc = x the first time (the automorphism with k = 1), acc += x after it; on ctx (nm rows) or child (L rows).  Scratch regions are
+    // whole rows from a hipMalloc base, so 16-byte aligned: what nflhip_pointwise_dev serves
+    auto accumulate = [&](nflhip_ctx *on, void *acc, const void *x, bool first) {
+      return first ? nflhip_automorphism_dev(on, acc, x, batch, 1, NFLHIP_FORM_NTT, st) : nflhip_pointwise_dev(on, NFLHIP_OP_ADD, acc, acc, x, nullptr, batch, st);
+    };
+    for (size_t j = 0; j < n2; ++j) {
+      const bool keyed = gkeys[j] != nullptr;
+      if (kb)  // V_{j,c} into V = [2][batch]
+        for (size_t c = 0; c < 2; ++c) {
+          char *Vc = V + c * batch * pb;
+          bool first = true;
+          const nflhip_dot_operand pa = {P, 1, 0};
+          for (size_t m = 0; m < kb; ++m) {
+            if (!wt(j, kbi[m])) continue;
+            if ((rc = nflhip_automorphism_dev(ctx, P, S + (2 * m + c) * batch * pb, batch, bks[kbi[m]], NFLHIP_FORM_NTT, st))) return rc;
+            if (kl) {  // the diagonal lies in the parent's layout as a key component does: the level-key operand, one term
+              if ((rc = dot_key(ctx, Vc, &pa, wt(j, kbi[m]), 0, first ? nullptr : Vc, batch, 1, kl, st))) return rc;
+            } else {
+              const nflhip_dot_operand w = {wt(j, kbi[m]), 0, 0};
+              if ((rc = nflhip_dot_dev(ctx, Vc, &pa, &w, first ? nullptr : Vc, batch, 1, 0, st))) return rc;
+            }
+            first = false;
+          }
+          if (first) HIPCHK(ctx, hipMemsetAsync(Vc, 0, batch * pb, st));
+        }
+      size_t nw = 0;  // W_{j,0} into W
+      for (size_t i = 0; i < n1 && c0; ++i)
+        if (wt(j, i)) cin[nw] = c0, cw[nw] = wt(j, i), cks[nw++] = bks[i];
+      if (c0 && (rc = nflhip_automorphism_mac_dev(ctx, W, nullptr, cin, cw, cks, nw, batch, L, 0, st))) return rc;
+      nw = 0;  // the terms of W_{j,1}
+      for (size_t m = 0; m < ub; ++m)
+        if (wt(j, ubi[m])) cin[nw] = c1, cw[nw] = wt(j, ubi[m]), cks[nw++] = 1;
+      if (keyed) {
+        if (kb && (rc = nflhip_moddown_ntt_dev(ctx, v, V + batch * pb, batch, K, mdflags, st))) return rc;
+        if (nw) {
+          if ((rc = nflhip_automorphism_mac_dev(ctx, v, kb ? v : nullptr, cin, cw, cks, nw, batch, L, 0, st))) return rc;
+        } else if (!kb) {
+          HIPCHK(ctx, hipMemsetAsync(v, 0, batch * qb, st));
+        }
+        nflhip_dot_operand u2;
+        if ((rc = modup_copy_in(ctx, route, X2, v, batch, L, st))) return rc;
+        if ((rc = modup_run(ctx, child, route, U2, X2, recs, batch, L, alpha, centred, "bsgs", st, &u2))) return rc;
+        for (size_t c = 0; c < 2; ++c) {
+          char *Tc = T + c * batch * pb, *Ac = A + c * batch * pb;
+          if ((rc = dot_key(ctx, Tc, &u2, gkeys[j], c, c == 0 && kb ? V : nullptr, batch, dnum, kl, st))) return rc;
+          if (a_init) {
+            if ((rc = nflhip_automorphism_dev(ctx, P, Tc, batch, gks[j], NFLHIP_FORM_NTT, st)) || (rc = accumulate(ctx, Ac, P, false))) return rc;
+          } else if ((rc = nflhip_automorphism_dev(ctx, Ac, Tc, batch, gks[j], NFLHIP_FORM_NTT, st))) {
+            return rc;
+          }
+        }
+        a_init = true;
+        if (c0) {
+          if (o0_init) {
+            if ((rc = nflhip_automorphism_dev(child, Pq, W, batch, gks[j], NFLHIP_FORM_NTT, st)) || (rc = accumulate(child, O0, Pq, false))) return rc;
+          } else if ((rc = nflhip_automorphism_dev(child, O0, W, batch, gks[j], NFLHIP_FORM_NTT, st))) {
+            return rc;
+          }
+          o0_init = true;
+        }
+      } else {
+        if (kb) {
+          for (size_t c = 0; c < 2; ++c)
+            if ((rc = accumulate(ctx, A + c * batch * pb, V + c * batch * pb, !a_init))) return rc;
+          a_init = true;
+        }
+        if (c0) {
+          if ((rc = accumulate(child, O0, W, !o0_init))) return rc;
+          o0_init = true;
+        }
+        if (nw) {
+          if ((rc = nflhip_automorphism_mac_dev(ctx, O1, o1_init ? O1 : nullptr, cin, cw, cks, nw, batch, L, 0, st))) return rc;
+          o1_init = true;
+        }
+      }
+    }
+    if (a_init && (rc = nflhip_moddown_ntt_dev(ctx, Y, A, 2 * batch, K, mdflags, st))) return rc;
+    // out_c = Y_c + O_c, added in the scratch; the copy out serves any alignment of the outputs
+    for (size_t c = 0; c < 2; ++c) {
+      char *Yc = Y + c * batch * qb, *Oc = c ? O1 : O0;
+      const bool o_init = c ? o1_init : o0_init;
+      void *out = c ? out1 : out0;
+      if (a_init && o_init && (rc = accumulate(child, Yc, Oc, false))) return rc;
+      if ((a_init || o_init) && (rc = set_device(ctx))) return rc;
+      if (a_init || o_init) HIPCHK(ctx, hipMemcpyAsync(out, a_init ? Yc : Oc, batch * qb, hipMemcpyDeviceToDevice, st));
+      else HIPCHK(ctx, hipMemsetAsync(out, 0, batch * qb, st));
+    }
+    if ((rc = set_device(ctx))) return rc;
+  } else {
+    void *douts[2 * NFLHIP_BSGS_MAX_BABY], *vouts[NFLHIP_BSGS_MAX_GIANT];
+    const void *dbs[2 * NFLHIP_BSGS_MAX_BABY], *sins[NFLHIP_BSGS_MAX_BABY], *pins[NFLHIP_BSGS_MAX_GIANT];
+    const void *gw[NFLHIP_BSGS_MAX_GIANT * NFLHIP_BSGS_MAX_BABY];
+    uint64_t kks[NFLHIP_BSGS_MAX_BABY], pks[NFLHIP_BSGS_MAX_GIANT], ones_k[NFLHIP_BSGS_MAX_BABY];
+    const void *c1s[NFLHIP_BSGS_MAX_BABY], *c0s[NFLHIP_BSGS_MAX_BABY];
+    for (size_t i = 0; i < NFLHIP_BSGS_MAX_BABY; ++i) c1s[i] = c1, c0s[i] = c0, ones_k[i] = 1;
+    if (kb) {
+      for (size_t m = 0; m < kb; ++m) {
+        for (size_t c = 0; c < 2; ++c) {
+          douts[2 * m + c] = S + (2 * m + c) * batch * pb;
+          dbs[2 * m + c] = (const char *)bkeys[kbi[m]] + c * (kl ? kl->knm * row : pb);
+        }
+        sins[m] = douts[2 * m];  // component c of baby m lies c batch polynomials behind
+        kks[m] = bks[kbi[m]];
+      }
+      hipError_t e = with_limb(ctx, [&](auto z) {
+        typedef decltype(z) T;
+        return kl ? launch_dot_multi_level<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, u.group_stride, u.term_stride,
+                                              (const T *const *)dbs, 2 * kb, batch, dnum, 1, *kl, st)
+                  : launch_dot_multi<T>(ctx->shape, ctx->tabs, (T *const *)douts, (const T *)U, u.group_stride, u.term_stride, (const T *const *)dbs, 2,
+                                        2 * kb, batch, dnum, 1, st);
+      });
+      if (e != hipSuccess) return hipfail(ctx, e, "bsgs: the babies' inner products");
+    }
+    // the giants of one kind in groups: V = [2][cnt][batch] on all rows
+    for (int kind = 0; kind < 2; ++kind) {
+      const bool keyed = kind == 0;
+      const size_t total = keyed ? kg : kb ? ug : 0;  // (an unkeyed giant with no keyed baby has nothing on all rows)
+      const size_t *js = keyed ? kgj : ugj;
+      for (size_t g0 = 0; g0 < total; g0 += kBsgsGroup) {
+        const size_t cnt = std::min(kBsgsGroup, total - g0);
+        char *V1 = V + cnt * batch * pb;
+        for (size_t s = 0; s < cnt; ++s) {
+          vouts[s] = V + s * batch * pb;
+          pins[s] = vouts[s];
+          pks[s] = keyed ? gks[js[g0 + s]] : 1;
+          for (size_t m = 0; m < kb; ++m) gw[s * kb + m] = wt(js[g0 + s], kbi[m]);
+        }
+        if (kb) {
+          hipError_t e = with_limb(ctx, [&](auto z) {
+            typedef decltype(z) T;
+            if (kl)
+              return launch_permute_mac_multi_ntt_level<T>(ctx->shape, ctx->tabs, (T *const *)vouts, nullptr, (const T *const *)sins, (const T *const *)gw,
+                                                           kks, (int)cnt, (int)kb, batch, 2, batch * pw, cnt * batch * pw, *kl, st);
+            return launch_permute_mac_multi_ntt<T>(ctx->shape, ctx->tabs, (T *const *)vouts, nullptr, (const T *const *)sins, (const T *const *)gw, kks,
+                                                   (int)cnt, (int)kb, batch, nm, 2, batch * pw, cnt * batch * pw, st);
+          });
+          if (e != hipSuccess) return hipfail(ctx, e, "bsgs: the inner sums");
+        }
+        if (keyed) {
+          if (kb && ((rc = nflhip_moddown_ntt_dev(ctx, v, V1, cnt * batch, K, mdflags, st)) || (rc = set_device(ctx)))) return rc;
+          if (ub) {  // W_{j,1} on the kept rows, onto the mod-down's result
+            for (size_t s = 0; s < cnt; ++s) {
+              vouts[s] = v + s * batch * qb;
+              for (size_t m = 0; m < ub; ++m) gw[s * ub + m] = wt(js[g0 + s], ubi[m]);
+            }
+            hipError_t e = with_limb(ctx, [&](auto z) {
+              typedef decltype(z) T;
+              return launch_permute_mac_multi_ntt<T>(ctx->shape, ctx->tabs, (T *const *)vouts, kb ? (const T *const *)vouts : nullptr,
+                                                     (const T *const *)c1s, (const T *const *)gw, ones_k, (int)cnt, (int)ub, batch, L, 1, 0, 0, st);
+            });
+            if (e != hipSuccess) return hipfail(ctx, e, "bsgs: the unrotated babies");
+          }
+          nflhip_dot_operand u2;
+          if ((rc = modup_copy_in(ctx, route, X2, v, cnt * batch, L, st))) return rc;
+          if ((rc = modup_run(ctx, child, route, U2, X2, recs, cnt * batch, L, alpha, centred, "bsgs", st, &u2))) return rc;
+          for (size_t s = 0; s < cnt; ++s)
+            for (size_t c = 0; c < 2; ++c) {
+              const nflhip_dot_operand a = {U2 + s * batch * u2.group_stride * pb, u2.group_stride, u2.term_stride};
+              char *o = (c ? V1 : V) + s * batch * pb;  // T_{j,c} in place of V_{j,c}
+              if ((rc = dot_key(ctx, o, &a, gkeys[js[g0 + s]], c, c == 0 && kb ? o : nullptr, batch, dnum, kl, st))) return rc;
+            }
+          if ((rc = set_device(ctx))) return rc;
+        }
+        hipError_t e = with_limb(ctx, [&](auto z) {
+          typedef decltype(z) T;
+          return launch_permute_sum_ntt<T>(ctx->shape, ctx->tabs, (T *)A, a_init ? (const T *)A : nullptr, (const T *const *)pins, pks, (int)cnt, batch, nm,
+                                           2, cnt * batch * pw, batch * pw, st);
+        });
+        if (e != hipSuccess) return hipfail(ctx, e, "bsgs: the giant steps' permutation");
+        a_init = true;
+      }
+    }
+    if (a_init) {
+      if ((rc = moddown_pair(ctx, out0, out1, A, batch, K, floor, st))) return rc;
+      o0_init = o1_init = true;
+    }
+    // the passes on the kept rows
+    hipError_t e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      hipError_t r = hipSuccess;
+      if (c0) {
+        for (size_t j = 0; j < n2; ++j) vouts[j] = W + j * batch * qb, pins[j] = vouts[j];
+        r = launch_permute_mac_multi_ntt<T>(ctx->shape, ctx->tabs, (T *const *)vouts, nullptr, (const T *const *)c0s, (const T *const *)weights, bks, (int)n2,
+                                            (int)n1, batch, L, 1, 0, 0, st);
+        if (r == hipSuccess)
+          r = launch_permute_sum_ntt<T>(ctx->shape, ctx->tabs, (T *)out0, o0_init ? (const T *)out0 : nullptr, (const T *const *)pins, gks, (int)n2, batch, L,
+                                        1, 0, 0, st);
+        o0_init = true;
+      }
+      for (size_t s = 0; s < ug && ub && r == hipSuccess; ++s) {  // the unkeyed giants' W_{j,1}
+        int nw = 0;
+        for (size_t m = 0; m < ub; ++m)
+          if (wt(ugj[s], ubi[m])) gw[nw++] = wt(ugj[s], ubi[m]);
+        if (!nw) continue;
+        r = launch_permute_mac_ntt<T>(ctx->shape, ctx->tabs, (T *)out1, o1_init ? (const T *)out1 : nullptr, (const T *const *)c1s, (const T *const *)gw,
+                                      ones_k, nw, batch, L, 1, 0, 0, 0, st);
+        o1_init = true;
+      }
+      return r;
+    });
+    if (e != hipSuccess) return hipfail(ctx, e, "bsgs: the terms on the kept rows");
+    if (!o0_init) HIPCHK(ctx, hipMemsetAsync(out0, 0, batch * qb, st));
+    if (!o1_init) HIPCHK(ctx, hipMemsetAsync(out1, 0, batch * qb, st));
+  }
+  if ((rc = ws_end(ctx, ctx->bsgs_ws, cap, st))) return rc;
+  if (!cap) warm_note(ctx->bsgs_warm, wkey, wsizes);
+  return NFLHIP_OK;
+}
+int nflhip_bsgs_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const void *d_c0, const void *d_c1, const void *const *d_bkeys, const uint64_t *bks,
+                        size_t n1, const void *const *d_gkeys, const uint64_t *gks, size_t n2, const void *const *d_weights, size_t batch,
+                        size_t k_special, size_t alpha, size_t level, int flags, void *stream) {
+  int rc = bsgs_check(ctx, d_out0, d_out1, d_c0, d_c1, d_bkeys, bks, n1, d_gkeys, gks, n2, d_weights, batch, k_special, alpha, level, flags);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  nflhip_ctx *run = nullptr;
+  KeyLevel kl;
+  if ((rc = level_context(ctx, k_special, level, (hipStream_t)stream, &run, &kl))) return rc;
+  return bsgs_run(run, d_out0, d_out1, d_c0, d_c1, d_bkeys, bks, n1, d_gkeys, gks, n2, d_weights, batch, k_special, std::min(alpha, level), flags,
+                  (hipStream_t)stream, run == ctx ? nullptr : &kl);
 }
 
 int nflhip_pointwise_dev(nflhip_ctx *ctx, int op, void *o, const void *a, const void *b, const void *bp, size_t batch,

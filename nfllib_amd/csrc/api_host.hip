@@ -599,6 +599,86 @@ int nflhip_lintrans_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const
   return lintrans_host(ctx, h_out0, h_out1, h_c0, h_c1, h_keys, h_weights, ks, count, batch, k_special, alpha, level, flags);
 }
 
+// weighted sums of automorphisms into several outputs: every input, every non-NULL weight and the outputs (an addend copied into its
+// output) are staged whole
+int nflhip_automorphism_mac_multi(nflhip_ctx *ctx, void *const *h_outs, const void *const *h_addends, const void *const *h_ins,
+                                  const void *const *h_weights, const uint64_t *ks, size_t outputs, size_t terms, size_t batch, size_t rows, int flags) {
+  int rc = mac_multi_check(ctx, h_outs, h_addends, h_ins, h_weights, ks, outputs, terms, batch, rows, flags);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t wb = rows * ctx->shape.n * ctx->word, ob = batch * wb;
+  Staged s(ctx);
+  if ((rc = s.in(0, nullptr, terms * ob)) || (rc = s.in(1, nullptr, outputs * terms * wb)) || (rc = s.in(2, nullptr, outputs * ob))) return rc;
+  char *i = (char *)ctx->stage[0], *w = (char *)ctx->stage[1], *o = (char *)ctx->stage[2];
+  auto put = [&](int slot, void *d, const void *h, size_t bytes) {
+    if (ctx->stage_host[slot]) std::memcpy(d, h, bytes);
+    else HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->hstream));
+    return (int)NFLHIP_OK;
+  };
+  const void *ins[NFLHIP_MAC_MAX_TERMS], *ws[NFLHIP_MAC_MULTI_MAX_OUTPUTS * NFLHIP_MAC_MAX_TERMS], *adds[NFLHIP_MAC_MULTI_MAX_OUTPUTS];
+  void *outs[NFLHIP_MAC_MULTI_MAX_OUTPUTS];
+  for (size_t t = 0; t < terms; ++t) {
+    if ((rc = put(0, i + t * ob, h_ins[t], ob))) return rc;
+    ins[t] = i + t * ob;
+  }
+  for (size_t q = 0; q < outputs * terms; ++q) {
+    if (h_weights[q] && (rc = put(1, w + q * wb, h_weights[q], wb))) return rc;
+    ws[q] = h_weights[q] ? w + q * wb : nullptr;
+  }
+  for (size_t q = 0; q < outputs; ++q) {
+    const bool add = h_addends && h_addends[q];
+    if (add && (rc = put(2, o + q * ob, h_addends[q], ob))) return rc;
+    outs[q] = o + q * ob;
+    adds[q] = add ? outs[q] : nullptr;
+  }
+  if ((rc = nflhip_automorphism_mac_multi_dev(ctx, outs, adds, ins, ws, ks, outputs, terms, batch, rows, flags, (void *)ctx->hstream))) return rc;
+  return s.outs(h_outs, outputs, 2, ob);
+}
+
+// BSGS slot linear transforms: c1 (and c0 behind it), the live digits of every key, every non-NULL weight and both outputs are staged
+// whole (the outputs share one slot, out1 behind out0, so that the last mod-down runs as one batch), as lintrans_host
+int nflhip_bsgs_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_c0, const void *h_c1, const void *const *h_bkeys, const uint64_t *bks,
+                    size_t n1, const void *const *h_gkeys, const uint64_t *gks, size_t n2, const void *const *h_weights, size_t batch, size_t k_special,
+                    size_t alpha, size_t level, int flags) {
+  int rc = bsgs_check(ctx, h_out0, h_out1, h_c0, h_c1, h_bkeys, bks, n1, h_gkeys, gks, n2, h_weights, batch, k_special, alpha, level, flags);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, ob = batch * level * row, wb = nm * row;
+  const size_t kb = 2 * keyswitch_level_digits(ctx, k_special, alpha, level) * wb;
+  size_t nk = 0, nw = 0;  // the slot holds what is there: a NULL key or weight takes no room
+  for (size_t m = 0; m < n1 + n2; ++m) nk += (m < n1 ? h_bkeys[m] : h_gkeys[m - n1]) != nullptr;
+  for (size_t q = 0; q < n1 * n2; ++q) nw += h_weights[q] != nullptr;
+  Staged s(ctx);
+  if ((rc = s.in(0, nullptr, 2 * ob)) || (rc = s.in(1, nullptr, nk * kb + nw * wb)) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
+  char *c = (char *)ctx->stage[0], *k = (char *)ctx->stage[1], *o = (char *)ctx->stage[2], *w = k + nk * kb;
+  auto put = [&](int slot, void *d, const void *h, size_t bytes) {
+    if (ctx->stage_host[slot]) std::memcpy(d, h, bytes);
+    else HIPCHK(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->hstream));
+    return (int)NFLHIP_OK;
+  };
+  if ((rc = put(0, c, h_c1, ob)) || (h_c0 && (rc = put(0, c + ob, h_c0, ob)))) return rc;
+  const void *keys[NFLHIP_BSGS_MAX_BABY + NFLHIP_BSGS_MAX_GIANT], *ws[NFLHIP_BSGS_MAX_BABY * NFLHIP_BSGS_MAX_GIANT];
+  for (size_t m = 0; m < n1 + n2; ++m) {
+    const void *h = m < n1 ? h_bkeys[m] : h_gkeys[m - n1];
+    keys[m] = nullptr;
+    if (!h) continue;
+    if ((rc = put(1, k, h, kb))) return rc;
+    keys[m] = k;
+    k += kb;
+  }
+  for (size_t q = 0; q < n1 * n2; ++q) {
+    ws[q] = nullptr;
+    if (!h_weights[q]) continue;
+    if ((rc = put(1, w, h_weights[q], wb))) return rc;
+    ws[q] = w;
+    w += wb;
+  }
+  if ((rc = nflhip_bsgs_ntt_dev(ctx, o, o + ob, h_c0 ? c + ob : nullptr, c, keys, bks, n1, keys + n1, gks, n2, ws, batch, k_special, alpha, level, flags,
+                                (void *)ctx->hstream)))
+    return rc;
+  return s.out2(h_out0, h_out1, 2, ob);
+}
+
 // the tensor product: the inputs share one slot (a0, a1, then b0, b1 unless it is the square), the three outputs another
 int nflhip_tensor_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, void *h_out2, const void *h_a0, const void *h_a1, const void *h_b0,
                       const void *h_b1, size_t batch, size_t rows, int flags) {

@@ -115,6 +115,15 @@ struct nflhip_ctx {
   std::mutex lt_mu;
   WarmMap lt_warm;
   Workspace lt_ws;
+  // BSGS slot linear transforms (api.hip bsgs_run): the warm map's key carries, next to (k_special, alpha), the plan, the modes and the
+  // kinds of steps (keyed babies or none, keyed giants or none, c0 or none); its sizes are the batch, the polynomials of a group's
+  // mod-down and mod-up (min(4, keyed giants) * batch; the sequence: batch) and the polynomials of the last mod-down call -- what the
+  // calls underneath allocate by.  More keyed babies or giant steps than before only grow the workspace, which ws_begin refuses
+  // while capturing, before anything is enqueued.  One workspace for both mod-ups, the babies' key-switch sums, a group of giant
+  // steps and the two accumulated sums.  All under bsgs_mu, which is taken BEFORE ks_mu and bcn_mu.
+  std::mutex bsgs_mu;
+  WarmMap bsgs_warm;
+  Workspace bsgs_ws;
   // ciphertext multiplication (api.hip mulrelin_run): per k_special one device block -- nm pairs (pi_j = P mod p_j, its Shoup
   // companion; zeros on the special rows), then the constant polynomial [nm][n] that holds pi_j in every word of row j (the
   // sequence's one-term dot) -- built on the host at the first call for that k_special; the warm map's size is the batch; one
@@ -460,6 +469,86 @@ inline int lintrans_check(const nflhip_ctx *ctx, const void *out0, const void *o
       if (keys[m] && ranges_overlap(o, ob, keys[m], kb)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: an output overlaps a key");
       if (ranges_overlap(o, ob, weights[m], wb)) return fail(ctx, NFLHIP_ERR_INVALID, "lintrans: an output overlaps a weight");
     }
+  }
+  return NFLHIP_OK;
+}
+// nflhip_automorphism_mac_multi_dev / nflhip_automorphism_mac_multi: every argument check, before any device use.  weights =
+// [outputs][terms], a NULL entry the zero weight; every overlap of an output with an input, a weight or another output is refused
+inline int mac_multi_check(const nflhip_ctx *ctx, void *const *outs, const void *const *addends, const void *const *ins, const void *const *weights,
+                           const uint64_t *ks, size_t outputs, size_t terms, size_t batch, size_t rows, int flags) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: not on a cyclic row context");
+  if (flags) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: unknown flag bits");
+  if (outputs == 0 || outputs > NFLHIP_MAC_MULTI_MAX_OUTPUTS) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: the number of outputs is out of range (1 to 16)");
+  if (terms == 0 || terms > NFLHIP_MAC_MAX_TERMS) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: the number of terms is out of range (1 to 16)");
+  if (rows == 0 || rows > ctx->shape.nm) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: rows is out of range (1 to nmoduli)");
+  if (batch == 0) return NFLHIP_OK;
+  if (!ks) return fail(ctx, NFLHIP_ERR_INVALID, "NULL multiplier array");
+  for (size_t t = 0; t < terms; ++t)
+    if ((ks[t] & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: the exponent k must be odd");
+  if (!outs || !ins || !weights) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  for (size_t t = 0; t < terms; ++t)
+    if (!ins[t]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  for (size_t o = 0; o < outputs; ++o) {
+    if (!outs[o]) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+    if (addends && addends[o] && addends[o] != outs[o])
+      return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: an addend is NULL or exactly its output");
+  }
+  const size_t row = ctx->shape.n * ctx->word, wb = rows * row;
+  size_t ob;
+  if (__builtin_mul_overflow(batch, wb, &ob)) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: the size overflows");
+  for (size_t o = 0; o < outputs; ++o) {
+    for (size_t t = 0; t < terms; ++t)
+      if (ranges_overlap(outs[o], ob, ins[t], ob)) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: an output overlaps an input");
+    for (size_t q = 0; q < outputs * terms; ++q)
+      if (weights[q] && ranges_overlap(outs[o], ob, weights[q], wb)) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: an output overlaps a weight");
+    for (size_t q = 0; q < o; ++q)
+      if (ranges_overlap(outs[o], ob, outs[q], ob)) return fail(ctx, NFLHIP_ERR_INVALID, "automorphism_mac_multi: two outputs overlap");
+  }
+  return NFLHIP_OK;
+}
+// nflhip_bsgs_ntt_dev / nflhip_bsgs_ntt: every argument check short of the tables, before any device use.  weights = [n2][n1], a NULL
+// entry the zero diagonal; every giant step has a weight.  The operands have `level` rows, a weight is a whole polynomial of this
+// context, and of a key the first ceil(level / alpha) digits are read.
+inline int bsgs_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *c0, const void *c1, const void *const *bkeys,
+                      const uint64_t *bks, size_t n1, const void *const *gkeys, const uint64_t *gks, size_t n2, const void *const *weights,
+                      size_t batch, size_t k_special, size_t alpha, size_t level, int flags) {
+  int rc = keyswitch_family_check(ctx, "bsgs", flags, NFLHIP_BSGS_SEQUENCE | NFLHIP_BSGS_HOISTED, NFLHIP_BSGS_CENTERED | NFLHIP_BSGS_FLOOR,
+                                  n1 == 0 || n1 > NFLHIP_BSGS_MAX_BABY   ? "bsgs: the number of baby steps is out of range (1 to 16)"
+                                  : n2 == 0 || n2 > NFLHIP_BSGS_MAX_GIANT ? "bsgs: the number of giant steps is out of range (1 to 16)"
+                                                                          : nullptr,
+                                  k_special, alpha);
+  if (!rc) rc = level_check(ctx, k_special, level, "bsgs");
+  if (rc || batch == 0) return rc;
+  const size_t nm = ctx->shape.nm, two_n = 2 * ctx->shape.n;
+  if (!bks || !gks) return fail(ctx, NFLHIP_ERR_INVALID, "NULL multiplier array");
+  if (!out0 || !out1 || !c1 || !bkeys || !gkeys || !weights) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  for (size_t m = 0; m < n1 + n2; ++m) {
+    const uint64_t k = m < n1 ? bks[m] : gks[m - n1];
+    const void *key = m < n1 ? bkeys[m] : gkeys[m - n1];
+    if ((k & 1) == 0) return fail(ctx, NFLHIP_ERR_INVALID, "bsgs: the exponent k must be odd");
+    if (!key && (k & (two_n - 1)) != 1) return fail(ctx, NFLHIP_ERR_INVALID, "bsgs: a NULL key goes with k = 1 mod 2 degree only (the unrotated step)");
+  }
+  for (size_t j = 0; j < n2; ++j) {
+    bool any = false;
+    for (size_t i = 0; i < n1; ++i) any = any || weights[j * n1 + i];
+    if (!any) return fail(ctx, NFLHIP_ERR_INVALID, "bsgs: a giant step has no diagonal");
+  }
+  const size_t row = ctx->shape.n * ctx->word, wb = nm * row, kd = (level + alpha - 1) / alpha, dnum = keyswitch_digits(ctx, k_special, alpha);
+  size_t ob, sb, kb, polys;
+  // (sb: beyond the largest scratch of either plan, in polynomials of nmoduli rows; kb: the digits that are read)
+  if (__builtin_mul_overflow(batch, level * row, &ob) || __builtin_mul_overflow(batch, 8 * (dnum + 8) + 2 * n1 + n2, &polys) ||
+      __builtin_mul_overflow(polys, wb, &sb) || __builtin_mul_overflow(2 * kd, wb, &kb))
+    return fail(ctx, NFLHIP_ERR_INVALID, "bsgs: the size overflows");
+  if (ranges_overlap(out0, ob, out1, ob)) return fail(ctx, NFLHIP_ERR_INVALID, "bsgs: the two outputs overlap");
+  for (const void *o : {out0, out1}) {
+    if ((c0 && ranges_overlap(o, ob, c0, ob)) || ranges_overlap(o, ob, c1, ob)) return fail(ctx, NFLHIP_ERR_INVALID, "bsgs: an output overlaps c0 or c1");
+    for (size_t m = 0; m < n1 + n2; ++m) {
+      const void *key = m < n1 ? bkeys[m] : gkeys[m - n1];
+      if (key && ranges_overlap(o, ob, key, kb)) return fail(ctx, NFLHIP_ERR_INVALID, "bsgs: an output overlaps a key");
+    }
+    for (size_t q = 0; q < n1 * n2; ++q)
+      if (weights[q] && ranges_overlap(o, ob, weights[q], wb)) return fail(ctx, NFLHIP_ERR_INVALID, "bsgs: an output overlaps a weight");
   }
   return NFLHIP_OK;
 }

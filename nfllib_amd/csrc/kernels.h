@@ -235,6 +235,22 @@ template <typename T>
 hipError_t launch_permute_mac_ntt_level(const Shape &s, const DevTables &t, T *out, const T *addend, const T *const *ins, const T *const *weights,
                                         const uint64_t *ks, int terms, size_t batch, size_t comps, size_t in_cs, size_t out_cs, const KeyLevel &kl,
                                         hipStream_t st);
+// the kernels of the BSGS slot linear transform (kernels_bsgs.hip; include/nflhip.h "weighted sums of automorphisms into several
+// outputs", "BSGS slot linear transforms").  launch_permute_mac_multi_ntt: launch_permute_mac_ntt for `outputs` outputs that share ins
+// and ks -- outs[o] = addends[o] + sum_t weights[o terms + t] (.) sigma^NTT_{ks[t]}(ins[t]), a NULL weight skipped, addends NULL or
+// addends[o] NULL or outs[o] --, one launch per kMacMultiJB outputs; _level: on all rows of a level context with the weights in the
+// parent's layout.  launch_permute_sum_ntt: out = addend + sum_t sigma^NTT_{ks[t]}(ins[t]), no weights.  HOST arrays of device pointers.
+template <typename T>
+hipError_t launch_permute_mac_multi_ntt(const Shape &s, const DevTables &t, T *const *outs, const T *const *addends, const T *const *ins,
+                                        const T *const *weights, const uint64_t *ks, int outputs, int terms, size_t batch, size_t R, size_t comps,
+                                        size_t in_cs, size_t out_cs, hipStream_t st);
+template <typename T>
+hipError_t launch_permute_mac_multi_ntt_level(const Shape &s, const DevTables &t, T *const *outs, const T *const *addends, const T *const *ins,
+                                              const T *const *weights, const uint64_t *ks, int outputs, int terms, size_t batch, size_t comps,
+                                              size_t in_cs, size_t out_cs, const KeyLevel &kl, hipStream_t st);
+template <typename T>
+hipError_t launch_permute_sum_ntt(const Shape &s, const DevTables &t, T *out, const T *addend, const T *const *ins, const uint64_t *ks, int terms,
+                                  size_t batch, size_t R, size_t comps, size_t in_cs, size_t out_cs, hipStream_t st);
 // in-place bit reversal of every row (permut.hpp:86-117), and `count` copies of one polynomial
 template <typename T> hipError_t launch_bitrev_rows(const Shape &s, T *d, size_t rows, hipStream_t st);
 hipError_t launch_broadcast(void *dst, const void *one, size_t bytes_per_poly, size_t count, hipStream_t st);

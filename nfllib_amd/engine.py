@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MULRELIN_CENTERED, MULRELIN_FLOOR, MULRELIN_FUSED, MULRELIN_MERGED, MULRELIN_RESCALE, MULRELIN_SEQUENCE, LINTRANS_CENTERED, LINTRANS_FLOOR, LINTRANS_HOISTED, LINTRANS_MAX_TERMS, LINTRANS_SEQUENCE, MAC_MAX_TERMS, MAC_DOUBLE_BUFFER, DOT_MULTI_MAX_OUTPUTS, ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_HOISTED, ROTATE_MAX_OUTPUTS, ROTATE_SEQUENCE, KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
+from ._lib import (MULRELIN_CENTERED, MULRELIN_FLOOR, MULRELIN_FUSED, MULRELIN_MERGED, MULRELIN_RESCALE, MULRELIN_SEQUENCE, LINTRANS_CENTERED, LINTRANS_FLOOR, LINTRANS_HOISTED, LINTRANS_MAX_TERMS, LINTRANS_SEQUENCE, MAC_MAX_TERMS, MAC_DOUBLE_BUFFER, MAC_MULTI_MAX_OUTPUTS, BSGS_CENTERED, BSGS_FLOOR, BSGS_HOISTED, BSGS_MAX_BABY, BSGS_MAX_GIANT, BSGS_SEQUENCE, DOT_MULTI_MAX_OUTPUTS, ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_HOISTED, ROTATE_MAX_OUTPUTS, ROTATE_SEQUENCE, KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -688,6 +688,129 @@ class Engine:
             return out0, out1
         self._chk(self.lib.nflhip_lintrans_ntt(self.ctx, _vp(out0), _vp(out1), _vp(c0), _vp(c1), pk, pw, kv, len(ks), batch, k_special, alpha,
                                                self._lt_flags(centered, floor, plan)))
+        return out0, out1
+
+    # ---- several-output weighted sums and BSGS slot linear transforms (include/nflhip.h "weighted sums of automorphisms into several
+    # outputs", "BSGS slot linear transforms") ----
+    def _mac_multi_args(self, ins, weights, ks, addends, rows, size, contiguous):
+        ins, ks = list(ins), [self._k(k) for k in ks]
+        weights = [list(w) for w in weights]
+        rows = self.nmoduli if rows is None else int(rows)
+        if len(ins) != len(ks) or not 1 <= len(ks) <= MAC_MAX_TERMS or not 1 <= len(weights) <= MAC_MULTI_MAX_OUTPUTS or \
+                any(len(w) != len(ks) for w in weights):
+            raise ValueError("one input per multiplier (1 to 16 terms), one list of weights (or None) per output (1 to 16 outputs)")
+        if not 1 <= rows <= self.nmoduli or any(size(x) != size(ins[0]) or size(x) % (rows * self.degree) or not contiguous(x) for x in ins):
+            raise ValueError("every input is a contiguous [batch, rows, n] tensor, 1 <= rows <= nm")
+        if any(w is not None and (size(w) < rows * self.degree or not contiguous(w)) for ws in weights for w in ws):
+            raise ValueError("every weight is None or a contiguous tensor of at least rows * n words")
+        addends = [None] * len(weights) if addends is None else list(addends)
+        if len(addends) != len(weights):
+            raise ValueError("one addend (or None) per output")
+        return ins, weights, ks, addends, rows, size(ins[0]) // (rows * self.degree)
+
+    def automorphism_mac_multi(self, ins, weights, ks, addends=None, outs=None, rows=None, stream=None):
+        """[addends[o] + sum_t weights[o][t] * sigma_ks[t](ins[t]) for o] on NTT-form data: automorphism_mac for up to 16 outputs that
+        share ins and ks, with every term's source staged and permuted once for the outputs of a launch.  weights[o][t] = [>= rows, n]
+        or None (the zero weight); addends[o] = None or outs[o] itself; no output may overlap an input, a weight or another output.
+        Returns the list of outputs, each [batch, rows, n]."""
+        ins, weights, ks, addends, rows, batch = self._mac_multi_args(ins, weights, ks, addends, rows, lambda x: x.numel(), lambda x: x.is_contiguous())
+        no = len(weights)
+        if outs is None:
+            if any(a is not None for a in addends):
+                raise ValueError("an addend is its output: pass outs")
+            block = _torch().empty((no, batch, rows, self.degree), dtype=self.torch_dtype, device=ins[0].device)
+            outs = [block[o] for o in range(no)]
+        outs = list(outs)
+        if len(outs) != no:
+            raise ValueError("one output per list of weights")
+        po = (C.c_void_p * no)(*[o.data_ptr() for o in outs])
+        pa = (C.c_void_p * no)(*[None if a is None else a.data_ptr() for a in addends])
+        pi = (C.c_void_p * len(ks))(*[x.data_ptr() for x in ins])
+        pw = (C.c_void_p * (no * len(ks)))(*[None if w is None else w.data_ptr() for ws in weights for w in ws])
+        kv = (C.c_uint64 * len(ks))(*ks)
+        self._chk(self.lib.nflhip_automorphism_mac_multi_dev(self.ctx, po, pa, pi, pw, kv, no, len(ks), batch, rows, 0, self._stream(stream)))
+        return outs
+
+    def h_automorphism_mac_multi(self, ins, weights, ks, addends=None, rows=None):
+        """host-pointer variant: numpy ins[t] = [batch, rows, n], weights[o][t] = [>= rows, n] or None, addends[o] = [batch, rows, n] or
+        None -> list of [batch, rows, n]"""
+        ins = [np.ascontiguousarray(x, dtype=self.np_dtype) for x in ins]
+        weights = [[None if w is None else np.ascontiguousarray(w, dtype=self.np_dtype) for w in ws] for ws in weights]
+        ins, weights, ks, addends, rows, batch = self._mac_multi_args(ins, weights, ks, addends, rows, lambda x: x.size, lambda x: True)
+        no = len(weights)
+        outs = [np.empty((batch, rows, self.degree), dtype=self.np_dtype) if a is None else np.array(a, dtype=self.np_dtype).reshape(batch, rows, self.degree)
+                for a in addends]
+        po = (C.c_void_p * no)(*[o.ctypes.data for o in outs])
+        pa = (C.c_void_p * no)(*[None if a is None else o.ctypes.data for a, o in zip(addends, outs)])
+        pi = (C.c_void_p * len(ks))(*[x.ctypes.data for x in ins])
+        pw = (C.c_void_p * (no * len(ks)))(*[None if w is None else w.ctypes.data for ws in weights for w in ws])
+        kv = (C.c_uint64 * len(ks))(*ks)
+        self._chk(self.lib.nflhip_automorphism_mac_multi(self.ctx, po, pa, pi, pw, kv, no, len(ks), batch, rows, 0))
+        return outs
+
+    _BSGS_PLAN = {None: 0, "sequence": BSGS_SEQUENCE, "hoisted": BSGS_HOISTED}
+
+    def _bsgs_args(self, c0, c1, baby_keys, baby_ks, giant_keys, giant_ks, weights, k_special, alpha, level, size, contiguous):
+        L = self.nmoduli - k_special
+        lv = L if level is None else int(level)
+        self.level_rows(lv, k_special)
+        bkeys, gkeys = list(baby_keys), list(giant_keys)
+        bks, gks = [self._k(k) for k in baby_ks], [self._k(k) for k in giant_ks]
+        weights = [list(w) for w in weights]
+        if len(bkeys) != len(bks) or len(gkeys) != len(gks) or not 1 <= len(bks) <= BSGS_MAX_BABY or not 1 <= len(gks) <= BSGS_MAX_GIANT:
+            raise ValueError("one key (or None) per step, 1 to 16 baby steps and 1 to 16 giant steps")
+        if len(weights) != len(gks) or any(len(w) != len(bks) for w in weights):
+            raise ValueError("weights is a list of n2 lists of n1 tensors or None")
+        if size(c1) % (lv * self.degree) or not contiguous(c1) or (c0 is not None and (c0.shape != c1.shape or not contiguous(c0))):
+            raise ValueError("c0 and c1 are contiguous [batch, level, n] tensors")
+        if not self._level_keys(bkeys + gkeys, size, k_special, alpha, level) or \
+                any(k is not None and not contiguous(k) for k in bkeys + gkeys):
+            raise ValueError("every key holds dnum * 2 polynomials of this context")
+        if any(w is not None and (size(w) != self.words_per_poly or not contiguous(w)) for ws in weights for w in ws):
+            raise ValueError("every weight is None or one polynomial of this context")
+        return bkeys, bks, gkeys, gks, weights, lv, size(c1) // (lv * self.degree)
+
+    def bsgs_linear_transform_ntt(self, c0, c1, baby_keys, baby_ks, giant_keys, giant_ks, weights, k_special, alpha, centered=False, floor=False,
+                                  out=None, plan=None, stream=None, level=None):
+        """sum_j sigma_giant_ks[j]( sum_i weights[j][i] * sigma_baby_ks[i](ciphertext) ) in one call with ONE mod-down of two polynomials:
+        a matrix-vector product by n1 n2 diagonals with n1 + n2 Galois keys.  (c0, c1) NTT-form [batch, l, n] batches, l = level or
+        nm - k_special (c0 may be None); baby_keys[i] / giant_keys[j] = the top-level Galois key [dnum, 2, nm, n] by the convention of
+        rotate_hoisted_ntt, or None for the unrotated step (k = 1); weights[j][i] = the top-level diagonal [nm, n] in NTT form,
+        pre-rotated by sigma_giant_ks[j]^-1, or None for the zero diagonal (every j has one at least).  At most 16 baby and 16 giant
+        steps.  Returns (out0, out1), each [batch, l, n]; `out` = a pair of such tensors, else both are views of one new
+        [2, batch, l, n] tensor.  plan "sequence" / "hoisted" forces a plan.  The first call for a (k_special, alpha, level, plan), or
+        for larger sizes, allocates: make it before a graph capture."""
+        bkeys, bks, gkeys, gks, weights, lv, batch = self._bsgs_args(c0, c1, baby_keys, baby_ks, giant_keys, giant_ks, weights, k_special, alpha, level,
+                                                                     lambda x: x.numel(), lambda x: x.is_contiguous())
+        if out is None:
+            both = _torch().empty((2, batch, lv, self.degree), dtype=self.torch_dtype, device=c1.device)
+            out = (both[0], both[1])
+        pb = (C.c_void_p * len(bks))(*[None if k is None else k.data_ptr() for k in bkeys])
+        pg = (C.c_void_p * len(gks))(*[None if k is None else k.data_ptr() for k in gkeys])
+        pw = (C.c_void_p * (len(bks) * len(gks)))(*[None if w is None else w.data_ptr() for ws in weights for w in ws])
+        kb, kg = (C.c_uint64 * len(bks))(*bks), (C.c_uint64 * len(gks))(*gks)
+        flags = (BSGS_CENTERED if centered else 0) | (BSGS_FLOOR if floor else 0) | self._BSGS_PLAN[plan]
+        self._chk(self.lib.nflhip_bsgs_ntt_dev(self.ctx, _vp(out[0]), _vp(out[1]), _vp(c0), _vp(c1), pb, kb, len(bks), pg, kg, len(gks), pw, batch,
+                                               k_special, alpha, lv, flags, self._stream(stream)))
+        return out
+
+    def h_bsgs_linear_transform_ntt(self, c0, c1, baby_keys, baby_ks, giant_keys, giant_ks, weights, k_special, alpha, centered=False, floor=False,
+                                    plan=None, level=None):
+        """host-pointer variant: numpy operands as bsgs_linear_transform_ntt -> (out0, out1)"""
+        def arr(x):
+            return None if x is None else np.ascontiguousarray(x, dtype=self.np_dtype)
+        c0, c1 = arr(c0), arr(c1)
+        bkeys, bks, gkeys, gks, weights, lv, batch = self._bsgs_args(c0, c1, [arr(k) for k in baby_keys], baby_ks, [arr(k) for k in giant_keys], giant_ks,
+                                                                     [[arr(w) for w in ws] for ws in weights], k_special, alpha, level,
+                                                                     lambda x: x.size, lambda x: True)
+        out0, out1 = (np.empty((batch, lv, self.degree), dtype=self.np_dtype) for _ in range(2))
+        pb = (C.c_void_p * len(bks))(*[None if k is None else k.ctypes.data for k in bkeys])
+        pg = (C.c_void_p * len(gks))(*[None if k is None else k.ctypes.data for k in gkeys])
+        pw = (C.c_void_p * (len(bks) * len(gks)))(*[None if w is None else w.ctypes.data for ws in weights for w in ws])
+        kb, kg = (C.c_uint64 * len(bks))(*bks), (C.c_uint64 * len(gks))(*gks)
+        flags = (BSGS_CENTERED if centered else 0) | (BSGS_FLOOR if floor else 0) | self._BSGS_PLAN[plan]
+        self._chk(self.lib.nflhip_bsgs_ntt(self.ctx, _vp(out0), _vp(out1), _vp(c0), _vp(c1), pb, kb, len(bks), pg, kg, len(gks), pw, batch, k_special, alpha,
+                                           lv, flags))
         return out0, out1
 
     # ---- ciphertext multiplication (include/nflhip.h "ciphertext multiplication") ----
