@@ -757,6 +757,51 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out2._p = d2;
   }
 
+  // Scale-and-round by t/Q (nfl::scale_round / nfl::scale_round_ntt below): this ring type is the input's, out lives in the ring over
+  // its first KS moduli, Q their product.  Queues and streams are ordered exactly as mod_down_into orders them.
+  template <size_t KS> static void scale_round_into(poly_p<T, Degree, KS> &out, poly_p const &in, uint64_t t, bool floor, bool ntt_form) {
+    static_assert(KS >= 1 && KS < NbModuli, "nfl::scale_round: the output's ring is over the first KS moduli, 1 <= KS < the input's");
+    typedef poly_p<T, Degree, KS> out_t;
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    ptr_type src = in._p;  // (holds the input while the launch is enqueued)
+    typename out_t::ptr_type dst = out_t::fresh();
+    const void *s = src->dev_ro();
+    void *d = dst->dev_wo();
+    detail::check(out_t::ctx_t::get(), nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue()), "scale_round");
+    const int flags = floor ? NFLHIP_SCALE_ROUND_FLOOR : 0;
+    if (ntt_form) detail::check(ctx_t::get(), nflhip_scale_round_ntt_dev(ctx_t::get(), d, s, 1, KS, t, flags, ctx_t::queue()), "scale_round_ntt");
+    else detail::check(ctx_t::get(), nflhip_scale_round_dev(ctx_t::get(), d, s, 1, KS, t, flags, ctx_t::queue()), "scale_round");
+    detail::check(ctx_t::get(), nflhip_stream_sync(ctx_t::get(), ctx_t::queue()), "scale_round");
+    out._p = dst;
+  }
+
+  // The BFV tensor product (nfl::bfv_tensor_ntt below).  This ring type is the EXTENDED one (NbModuli = L + KB moduli); the inputs and
+  // the outputs live in the ring with L moduli.  The ordering is that of key_switch_into: both rings' queues run first, the other
+  // ring's stream is awaited, the launches go on THIS ring's stream and the call returns once they have finished there.  The results
+  // get payloads of their own: an output may be an input.
+  template <size_t L> static void bfv_tensor_into(poly_p<T, Degree, L> &out0, poly_p<T, Degree, L> &out1, poly_p<T, Degree, L> &out2,
+                                                  poly_p<T, Degree, L> const &a0, poly_p<T, Degree, L> const &a1, poly_p<T, Degree, L> const *b0,
+                                                  poly_p<T, Degree, L> const *b1, uint64_t t, bool floor) {
+    static_assert(L >= 1 && L < NbModuli, "nfl::bfv_tensor_ntt: the extended ring has at least one modulus more than the ciphertexts'");
+    typedef poly_p<T, Degree, L> out_t;
+    if (!b0 != !b1) throw std::runtime_error("nfl(hip): bfv_tensor_ntt: b0 and b1 are both given, or both NULL for the square");
+    lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    typedef typename out_t::ptr_type optr;
+    optr s0 = a0._p, s1 = a1._p, t0 = b0 ? b0->_p : optr(), t1 = b1 ? b1->_p : optr();  // (hold the inputs while the launches are enqueued)
+    optr d0 = out_t::fresh(), d1 = out_t::fresh(), d2 = out_t::fresh();
+    const void *p_a0 = s0->dev_ro(), *p_a1 = s1->dev_ro(), *p_b0 = b0 ? t0->dev_ro() : nullptr, *p_b1 = b1 ? t1->dev_ro() : nullptr;
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo(), *o2 = d2->dev_wo();
+    detail::check(out_t::ctx_t::get(), nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue()), "bfv_tensor_ntt");
+    detail::check(ctx_t::get(), nflhip_bfv_tensor_ntt_dev(ctx_t::get(), o0, o1, o2, p_a0, p_a1, p_b0, p_b1, 1, L, t, floor ? NFLHIP_SCALE_ROUND_FLOOR : 0,
+                                                          ctx_t::queue()), "bfv_tensor_ntt");
+    detail::check(ctx_t::get(), nflhip_stream_sync(ctx_t::get(), ctx_t::queue()), "bfv_tensor_ntt");
+    out0._p = d0;
+    out1._p = d1;
+    out2._p = d2;
+  }
+
   // Sum of products (nfl::dot / nfl::dot_add below): the deferred queue of this ring type runs first (on the caller), then the
   // pointer form of the entry on the queue's stream, 16 terms per launch, chained through the addend.  The result gets a
   // payload of its own, so `out` may be one of the inputs and copy-on-write sharers of out's old value keep it.
@@ -1049,6 +1094,67 @@ template <class T, size_t D, size_t M>
 void tensor_ntt(poly_p<T, D, M> &out0, poly_p<T, D, M> &out1, poly_p<T, D, M> &out2, poly_p<T, D, M> const &a0, poly_p<T, D, M> const &a1,
                 poly_p<T, D, M> const *b0 = nullptr, poly_p<T, D, M> const *b1 = nullptr) {
   poly_p<T, D, M>::tensor_into(out0, out1, out2, a0, a1, b0, b1);
+}
+
+/* BFV multiplication (include/nflhip.h "BFV multiplication").  scale_round: out = round(t in / Q) carried back onto the first KS
+ * moduli of in's ring, Q their product, KS deduced from the two types (floor: floor(t in / Q) - u); scale_round_ntt: the same on
+ * NTT-form values.  bfv_tensor_ntt<KB>: the scale-invariant tensor product of the BFV ciphertexts (a0, a1) and (b0, b1) in the ring
+ * with L moduli, through the ring with L + KB moduli: (d0, d1, d2) = round(t (a0 b0, a0 b1 + a1 b0, a1 b1) / Q), NTT form; an output
+ * may be an input.  bfv_square_ntt<KB>: the same of (a0, a1) with itself.  The relinearisation is an ordinary key_switch_ntt of d2.  On
+ * poly the staged host entries; on poly_p the queues and streams of the two ring types are ordered as nfl::mod_down and
+ * nfl::tensor_ntt order theirs.  Never fused into a queue's rewrites. */
+template <class T, size_t D, size_t KS, size_t M> void scale_round(poly<T, D, KS> &out, poly<T, D, M> const &in, uint64_t t, bool floor = false) {
+  static_assert(KS >= 1 && KS < M, "nfl::scale_round: the output's ring is over the first KS moduli, 1 <= KS < the input's");
+  typedef poly<T, D, M> P;
+  detail::check(P::ctx(), nflhip_scale_round(P::ctx(), out.data(), in.cdata(), 1, KS, t, floor ? NFLHIP_SCALE_ROUND_FLOOR : 0), "scale_round");
+}
+template <class T, size_t D, size_t KS, size_t M> void scale_round(poly_p<T, D, KS> &out, poly_p<T, D, M> const &in, uint64_t t, bool floor = false) {
+  poly_p<T, D, M>::template scale_round_into<KS>(out, in, t, floor, false);
+}
+template <class T, size_t D, size_t KS, size_t M> void scale_round_ntt(poly<T, D, KS> &out, poly<T, D, M> const &in, uint64_t t, bool floor = false) {
+  static_assert(KS >= 1 && KS < M, "nfl::scale_round_ntt: the output's ring is over the first KS moduli, 1 <= KS < the input's");
+  typedef poly<T, D, M> P;
+  detail::check(P::ctx(), nflhip_scale_round_ntt(P::ctx(), out.data(), in.cdata(), 1, KS, t, floor ? NFLHIP_SCALE_ROUND_FLOOR : 0), "scale_round_ntt");
+}
+template <class T, size_t D, size_t KS, size_t M> void scale_round_ntt(poly_p<T, D, KS> &out, poly_p<T, D, M> const &in, uint64_t t, bool floor = false) {
+  poly_p<T, D, M>::template scale_round_into<KS>(out, in, t, floor, true);
+}
+namespace detail {
+template <size_t KB, class T, size_t D, size_t L>
+void bfv_tensor_host(poly<T, D, L> &out0, poly<T, D, L> &out1, poly<T, D, L> &out2, poly<T, D, L> const &a0, poly<T, D, L> const &a1,
+                     poly<T, D, L> const *b0, poly<T, D, L> const *b1, uint64_t t, bool floor) {
+  static_assert(KB >= 1, "nfl::bfv_tensor_ntt: the extended ring has at least one modulus more than the ciphertexts'");
+  typedef poly<T, D, L> S;
+  typedef poly<T, D, L + KB> P;
+  S *tmp[3] = {S::make_temp(), S::make_temp(), S::make_temp()};  // (an output may be an input)
+  const int rc = nflhip_bfv_tensor_ntt(P::ctx(), tmp[0]->data(), tmp[1]->data(), tmp[2]->data(), a0.cdata(), a1.cdata(), b0 ? b0->cdata() : nullptr,
+                                       b1 ? b1->cdata() : nullptr, 1, L, t, floor ? NFLHIP_SCALE_ROUND_FLOOR : 0);
+  S *const outs[3] = {&out0, &out1, &out2};
+  for (int k = 0; k < 3; ++k) {
+    if (rc == 0) std::memcpy(static_cast<void *>(outs[k]->data()), tmp[k]->cdata(), sizeof(S));
+    S::drop_temp(tmp[k]);
+  }
+  check(P::ctx(), rc, "bfv_tensor_ntt");
+}
+}  // namespace detail
+template <size_t KB, class T, size_t D, size_t L>
+void bfv_tensor_ntt(poly<T, D, L> &d0, poly<T, D, L> &d1, poly<T, D, L> &d2, poly<T, D, L> const &a0, poly<T, D, L> const &a1, poly<T, D, L> const &b0,
+                    poly<T, D, L> const &b1, uint64_t t, bool floor = false) {
+  detail::bfv_tensor_host<KB>(d0, d1, d2, a0, a1, &b0, &b1, t, floor);
+}
+template <size_t KB, class T, size_t D, size_t L>
+void bfv_tensor_ntt(poly_p<T, D, L> &d0, poly_p<T, D, L> &d1, poly_p<T, D, L> &d2, poly_p<T, D, L> const &a0, poly_p<T, D, L> const &a1,
+                    poly_p<T, D, L> const &b0, poly_p<T, D, L> const &b1, uint64_t t, bool floor = false) {
+  poly_p<T, D, L + KB>::template bfv_tensor_into<L>(d0, d1, d2, a0, a1, &b0, &b1, t, floor);
+}
+template <size_t KB, class T, size_t D, size_t L>
+void bfv_square_ntt(poly<T, D, L> &d0, poly<T, D, L> &d1, poly<T, D, L> &d2, poly<T, D, L> const &a0, poly<T, D, L> const &a1, uint64_t t, bool floor = false) {
+  detail::bfv_tensor_host<KB, T, D, L>(d0, d1, d2, a0, a1, nullptr, nullptr, t, floor);
+}
+template <size_t KB, class T, size_t D, size_t L>
+void bfv_square_ntt(poly_p<T, D, L> &d0, poly_p<T, D, L> &d1, poly_p<T, D, L> &d2, poly_p<T, D, L> const &a0, poly_p<T, D, L> const &a1, uint64_t t,
+                    bool floor = false) {
+  poly_p<T, D, L + KB>::template bfv_tensor_into<L>(d0, d1, d2, a0, a1, nullptr, nullptr, t, floor);
 }
 template <class T, size_t D, size_t L, size_t M>
 void mul_relin_ntt(poly<T, D, L> &out0, poly<T, D, L> &out1, poly<T, D, L> const &a0, poly<T, D, L> const &a1, poly<T, D, L> const &b0,

@@ -613,6 +613,62 @@ int nflhip_mulrelin_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const v
 int nflhip_mulrelin_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0,
                         const void *h_b1, const void *h_key, size_t batch, size_t k_special, size_t alpha, int flags);   /* staged host variant */
 
+/* ---- BFV multiplication: RNS scale-and-round by t/Q, the scale-invariant tensor product ---------
+ * The scale-invariant product of BFV needs Y = round(t X / Q) carried from the rows Q u B onto the rows Q without forming the
+ * integer (Halevi-Polyakov-Shoup).  The mod-down above cannot stand in: it divides by the LAST k rows and returns the leading ones;
+ * here the leading rows are divided out, the value is multiplied by t first, and the result comes back onto the rows divided out.
+ * The context has nm moduli p_0 ... p_{nm-1}, pairwise distinct over the rows used (anything else is NFLHIP_ERR_INVALID, as
+ * nflhip_baseconv_dev refuses a repeated source modulus).  1 <= ks <= nm - 1.  S = [0, ks), Q = prod_S p_i.  D = [ks, nm),
+ * kd = nm - ks, B = prod_D p_j.  t is a uint64_t with 1 <= t < 2^(limb_bits - 3): it is below every modulus, so coprime to all.
+ * Per coefficient position, from canonical words x_r:
+ *     z_r  = t * x_r mod p_r                                   every row r
+ *     r_j  = conv_{S->j}(z)          the CENTRED conversion of nflhip_baseconv_dev (same f_i, same v, same band), j in D
+ *                                   with NFLHIP_SCALE_ROUND_FLOOR the fast conversion (x + uQ) instead
+ *     Y_j  = (z_j - r_j) * Q^-1 mod p_j                        j in D
+ *     out_i = conv_{D->i}(Y)         the CENTRED conversion again, i in S      -> dense [batch][ks][degree]
+ *     NFLHIP_SCALE_ROUND_KEEP:      stop at Y: output the kd rows Y_j, dense [batch][kd][degree]
+ * With X_c the centred integer behind all nm rows, Y = round(t X_c / Q) mod B, whatever representative the rows hold (t B m = 0 on
+ * D); a fraction inside [1/2, 1/2 + ks e / 2^60) may round down, and under FLOOR it is floor(t X / Q) - u.  out is the centred
+ * representative of Y mod B reduced mod p_i, with the band of the second conversion at |Y| ~ B/2.  A BFV caller keeps
+ * n Q^2 / 2 < Q B / 2 and t n Q / 2 + 1 < B / 2: then neither representation wraps and the second band is never reached (with
+ * kd = L + 1 moduli of one width, roughly 2^(limb_bits - 3 - L) > t n).  The entries do not check the bound: they are defined for
+ * every input.
+ *   nflhip_scale_round_dev      coefficient form.  in [batch][nm][degree]; the output never overlaps the input.
+ *   nflhip_scale_round_ntt_dev  NTT form in and out: out = NTT_S(scale_round(INTT(in))), under KEEP NTT_D of Y, the transforms of the
+ *                               contexts over those moduli.  A composed plan: the input is copied into context-owned scratch and
+ *                               inverse-transformed, the result is forward-transformed by the child context over the rows written.
+ * Plans, same words: by default ONE kernel reads the nm rows, keeps the kd words Y in registers and writes the ks rows, where
+ * ks <= 8 and kd <= 9; NFLHIP_SCALE_ROUND_TWO_PASS -- and every larger shape -- writes Y into context-owned scratch and converts it
+ * with the kernel of nflhip_baseconv_dev (the cross-check).  With KEEP the flag changes nothing.
+ * The tables of a (ks, t) are built and uploaded on the FIRST call that names it (that call allocates and synchronises: make it
+ * before capturing into a hipGraph; while capturing it is NFLHIP_ERR_UNSUPPORTED); the scratch of the two-pass plan and of the NTT
+ * form, and the NTT form's child contexts, are allocated on first use and whenever the batch grows, likewise refused while
+ * capturing.  A replaying graph must not run concurrently with other such calls of the context.  batch == 0 returns NFLHIP_OK and
+ * touches nothing.  NFLHIP_ERR_INVALID, before the device is touched: a NULL context or pointer, ks or t out of range, unknown
+ * flag bits, a repeated modulus, the output overlapping the input, a size that overflows size_t, a cyclic row context.
+ *
+ * nflhip_bfv_tensor_ntt_dev on the context over the first L + kb moduli, ks = L: the scale-invariant tensor product of two BFV
+ * ciphertexts.  a0, a1, b0, b1 and out0, out1, out2 are [batch][L][degree], NTT form; b0 == b1 == NULL is the square.  Definition,
+ * word for word:
+ *     1. each input embedded in nm rows;  2. nflhip_baseconv_ntt_dev(S = [0, L), D = [0, nm), NFLHIP_BASECONV_CENTERED);
+ *     3. nflhip_tensor_ntt_dev on nm rows;  4. nflhip_scale_round_ntt_dev on each component.
+ * The four (or two) inputs go through the base extension as ONE batch, the three components through the scale-round as ONE batch of
+ * 3 batch, in scratch the context owns.  An output may be exactly an input; flags are NFLHIP_SCALE_ROUND_FLOOR and
+ * NFLHIP_SCALE_ROUND_TWO_PASS, passed through; the overlap and argument rules are those of nflhip_tensor_ntt_dev, every argument is
+ * checked before the device is touched.  The relinearisation is an ordinary nflhip_keyswitch_ntt_dev of out2 on the context over
+ * the first L + k_special moduli.  The host variants stage both sides. */
+#define NFLHIP_SCALE_ROUND_FLOOR 0x100
+#define NFLHIP_SCALE_ROUND_KEEP 0x200
+#define NFLHIP_SCALE_ROUND_TWO_PASS 0x400
+int nflhip_scale_round_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t ks, uint64_t t, int flags, void *stream);
+int nflhip_scale_round(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t ks, uint64_t t, int flags);   /* staged host variant */
+int nflhip_scale_round_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t ks, uint64_t t, int flags, void *stream);
+int nflhip_scale_round_ntt(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t ks, uint64_t t, int flags);   /* staged host variant */
+int nflhip_bfv_tensor_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, void *d_out2, const void *d_a0, const void *d_a1,
+                              const void *d_b0, const void *d_b1, size_t batch, size_t ks, uint64_t t, int flags, void *stream);
+int nflhip_bfv_tensor_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, void *h_out2, const void *h_a0, const void *h_a1,
+                          const void *h_b0, const void *h_b1, size_t batch, size_t ks, uint64_t t, int flags);   /* staged host variant */
+
 /* ---- leveled key switching and multiplication: one key for every level --------------------------
  * The two entries above on a ciphertext BELOW the context's top level -- what nflhip_mulrelin_ntt_dev with NFLHIP_MULRELIN_RESCALE
  * returns -- with the ONE top-level key: no context and no copy of the keys per level.  The context has nm = nmoduli moduli, the

@@ -38,6 +38,7 @@ MAC_MULTI_MAX_OUTPUTS = 16
 BSGS_MAX_BABY, BSGS_MAX_GIANT = 16, 16
 BSGS_CENTERED, BSGS_FLOOR, BSGS_SEQUENCE, BSGS_HOISTED = 0x100, 0x200, 0x1000, 0x2000
 MULRELIN_CENTERED, MULRELIN_FLOOR, MULRELIN_RESCALE, MULRELIN_FUSED, MULRELIN_SEQUENCE, MULRELIN_MERGED = 0x100, 0x200, 0x400, 0x800, 0x1000, 0x2000
+SCALE_ROUND_FLOOR, SCALE_ROUND_KEEP, SCALE_ROUND_TWO_PASS = 0x100, 0x200, 0x400
 
 
 class DotOperand(C.Structure):
@@ -96,6 +97,12 @@ SYMBOLS = [
     ("nflhip_lintrans_ntt", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _i]),
     ("nflhip_tensor_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _vp]),
     ("nflhip_tensor_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i]),
+    ("nflhip_scale_round_dev", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _i, _vp]),
+    ("nflhip_scale_round", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _i]),
+    ("nflhip_scale_round_ntt_dev", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _i, _vp]),
+    ("nflhip_scale_round_ntt", _i, [_vp, _vp, _vp, _sz, _sz, _u64, _i]),
+    ("nflhip_bfv_tensor_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _u64, _i, _vp]),
+    ("nflhip_bfv_tensor_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _u64, _i]),
     ("nflhip_mulrelin_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _vp]),
     ("nflhip_mulrelin_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i]),
     ("nflhip_keyswitch_level_digits", _sz, [_vp, _sz, _sz, _sz]),

@@ -436,7 +436,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch, nflhip::warm_dot_multi, nflhip::warm_rotate, nflhip::warm_lintrans, nflhip::warm_mulrelin};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch, nflhip::warm_dot_multi, nflhip::warm_rotate, nflhip::warm_lintrans, nflhip::warm_mulrelin, nflhip::warm_scale_round};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -550,6 +550,9 @@ int nflhip_ctx_destroy(nflhip_ctx *ctx) {
   ws_free(ctx->ks_ws);
   for (auto &kv : ctx->ks_recs) (void)hipFree(kv.second);
   ctx->ks_recs.clear();
+  for (Workspace *w : {&ctx->sr_ws[0], &ctx->sr_ws[1], &ctx->bfv_ws}) ws_free(*w);
+  for (auto &kv : ctx->srec) (void)hipFree(kv.second);
+  ctx->srec.clear();
   if (ctx->hstream) (void)hipStreamDestroy(ctx->hstream);
   for (int k = 0; k < 2; ++k) {
     if (ctx->aux[k]) { (void)hipStreamSynchronize(ctx->aux[k]); (void)hipStreamDestroy(ctx->aux[k]); }
@@ -1611,6 +1614,142 @@ int nflhip_tensor_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, void *d_o
                                 (const T *)d_b1, batch, rows, rows, rows * ctx->shape.n, rows * ctx->shape.n, nullptr, (hipStream_t)stream);
   });
   return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "tensor");
+}
+
+// RNS scale-and-round by t/Q (kernels_scale_round.hip; include/nflhip.h "BFV multiplication").  The record of a (ks, t)
+// (host_tables.cpp build_scale_round_record) is built and uploaded by the first call that names it, under the rules of
+// baseconv_record.
+static int scale_round_record(nflhip_ctx *ctx, size_t ks, uint64_t t, hipStream_t st, const uint64_t **rec) {
+  std::lock_guard<std::mutex> lk(ctx->srec_mu);
+  const std::array<uint64_t, 2> key = {(uint64_t)ks, t};
+  auto it = ctx->srec.find(key);
+  if (it != ctx->srec.end()) {
+    *rec = (const uint64_t *)it->second;
+    return NFLHIP_OK;
+  }
+  std::vector<uint64_t> h;
+  std::string err;
+  int rc;
+  try {
+    rc = build_scale_round_record(ctx->shape.limb_bits, ctx->h_P, ks, t, &h, &err);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory while building the scale-round tables");
+  }
+  if (rc) return fail(ctx, rc, err);  // (host arithmetic only: a repeated modulus is refused before any device use)
+  if (is_capturing(st))
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "scale_round: the first call for a (ks, t) uploads its tables, which a stream capture cannot do");
+  if ((rc = set_device(ctx))) return rc;
+  void *d = nullptr;
+  HIPCHK(ctx, hipMalloc(&d, h.size() * sizeof(uint64_t)));
+  hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return hipfail(ctx, e, "scale_round: table upload");
+  }
+  try {
+    ctx->srec[key] = d;
+  } catch (const std::bad_alloc &) {
+    (void)hipFree(d);
+    return fail(ctx, NFLHIP_ERR_NOMEM, "out of host memory");
+  }
+  *rec = (const uint64_t *)d;
+  return NFLHIP_OK;
+}
+// Plans of the coefficient form: the one-pass kernel where its register plans hold the rows; two passes -- Y into workspace 1, then
+// k_baseconv from there with the second record -- for larger shapes and under NFLHIP_SCALE_ROUND_TWO_PASS.  KEEP is one pass always.
+// The NTT form composes around it as baseconv_ntt_composed does: the input copied into workspace 0 and inverse-transformed by this
+// context, the result forward-transformed by the child context over the rows written.
+static int scale_round_run(nflhip_ctx *ctx, void *out, const void *in, size_t batch, size_t ks, uint64_t t, int flags, bool ntt, hipStream_t st) {
+  if (batch == 0) return NFLHIP_OK;  // (touches nothing: no record is built for an empty batch)
+  const uint64_t *rec = nullptr;
+  int rc = scale_round_record(ctx, ks, t, st, &rec);
+  if (rc || (rc = set_device(ctx))) return rc;
+  const size_t nm = ctx->shape.nm, kd = nm - ks, row = ctx->shape.n * ctx->word;
+  const bool centred = !(flags & NFLHIP_SCALE_ROUND_FLOOR), keep = (flags & NFLHIP_SCALE_ROUND_KEEP) != 0, regs = scale_round_in_registers(ks, kd);
+  const bool two = !keep && (!regs || (flags & NFLHIP_SCALE_ROUND_TWO_PASS));
+  auto pass = [&](void *o, const void *i, bool kp) {
+    return with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_scale_round<T>(ctx->shape, ctx->tabs, (T *)o, (const T *)i, rec, batch, ks, centred, kp, !regs, st);
+    });
+  };
+  hipError_t e;
+  if (!ntt && !two) {  // one launch, nothing allocated
+    e = pass(out, in, keep);
+    return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "scale_round");
+  }
+  std::lock_guard<std::mutex> lk(ctx->sr_mu);
+  const bool cap = is_capturing(st);
+  const char *what = "scale_round: the";
+  nflhip_ctx *child = nullptr;
+  if (ntt) {
+    std::lock_guard<std::mutex> lc(ctx->bcn_mu);
+    if ((rc = keep ? bcn_child(ctx, ks, kd, cap, &child) : bcn_child(ctx, 0, ks, cap, &child))) return rc;
+  }
+  if ((rc = set_device(ctx))) return rc;
+  if (two && (rc = ws_grow(ctx, ctx->sr_ws[1], batch * kd * row, cap, what))) return rc;
+  if ((rc = ws_begin(ctx, ctx->sr_ws[0], ntt ? batch * nm * row : 0, cap, st, what))) return rc;
+  const void *src = in;
+  if (ntt) {
+    HIPCHK(ctx, hipMemcpyAsync(ctx->sr_ws[0].buf, in, batch * nm * row, hipMemcpyDefault, st));
+    if ((rc = nflhip_ntt_inv_dev(ctx, ctx->sr_ws[0].buf, batch, st)) || (rc = set_device(ctx))) return rc;
+    src = ctx->sr_ws[0].buf;
+  }
+  if (two) {
+    void *Y = ctx->sr_ws[1].buf;
+    if ((e = pass(Y, src, true)) != hipSuccess) return hipfail(ctx, e, "scale_round: first pass");
+    e = with_limb(ctx, [&](auto z) {
+      typedef decltype(z) T;
+      return launch_baseconv_rows<T>(ctx->shape, ctx->tabs, (T *)out, ks, (const T *)Y, kd, rec + scale_round_back_offset(ks, kd), batch, kd, 0, ks, 1, st);
+    });
+    if (e != hipSuccess) return hipfail(ctx, e, "scale_round: second pass");
+  } else if ((e = pass(out, src, keep)) != hipSuccess) {
+    return hipfail(ctx, e, "scale_round");
+  }
+  if (ntt && ((rc = nflhip_ntt_fwd_dev(child, out, batch, st)) || (rc = set_device(ctx)))) return rc;
+  return ws_end(ctx, ctx->sr_ws[0], cap, st);
+}
+int nflhip_scale_round_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t ks, uint64_t t, int flags, void *stream) {
+  int rc = scale_round_check(ctx, d_out, d_in, batch, ks, t, flags, nullptr);  // in full, before any device use
+  if (rc) return rc;
+  return scale_round_run(ctx, d_out, d_in, batch, ks, t, flags, false, (hipStream_t)stream);
+}
+int nflhip_scale_round_ntt_dev(nflhip_ctx *ctx, void *d_out, const void *d_in, size_t batch, size_t ks, uint64_t t, int flags, void *stream) {
+  int rc = scale_round_check(ctx, d_out, d_in, batch, ks, t, flags, nullptr);  // in full, before any device use
+  if (rc) return rc;
+  return scale_round_run(ctx, d_out, d_in, batch, ks, t, flags, true, (hipStream_t)stream);
+}
+
+// The scale-invariant tensor product of BFV (include/nflhip.h "BFV multiplication"), the four steps of its definition through the
+// entries above: the inputs embedded in E = [4 or 2][batch][nm][n] and base-extended as ONE batch in place; the tensor product into
+// T = [3][batch][nm][n]; the scale-round of T as ONE batch of 3 batch, straight into the outputs where they follow each other in
+// memory, else into R = [3][batch][L][n] and copied out.  Both records are built BEFORE anything is enqueued; every read of the
+// inputs precedes every write of an output, so an output may be an input.
+int nflhip_bfv_tensor_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, void *d_out2, const void *d_a0, const void *d_a1, const void *d_b0,
+                              const void *d_b1, size_t batch, size_t ks, uint64_t t, int flags, void *stream) {
+  int rc = bfv_tensor_check(ctx, d_out0, d_out1, d_out2, d_a0, d_a1, d_b0, d_b1, batch, ks, t, flags);  // in full, before any device use
+  if (rc || batch == 0) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t *rec = nullptr;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, pb = nm * row, ob = batch * ks * row, nin = d_b0 ? 4 : 2;
+  if ((rc = scale_round_record(ctx, ks, t, st, &rec)) || (rc = baseconv_record(ctx, 0, ks, 0, nm, false, st, &rec)) || (rc = set_device(ctx))) return rc;
+  std::lock_guard<std::mutex> lk(ctx->bfv_mu);
+  const bool cap = is_capturing(st), dense = (char *)d_out1 == (char *)d_out0 + ob && (char *)d_out2 == (char *)d_out1 + ob;
+  if ((rc = ws_begin(ctx, ctx->bfv_ws, (nin + 3) * batch * pb + (dense ? 0 : 3 * ob), cap, st, "bfv_tensor: the"))) return rc;
+  char *E = (char *)ctx->bfv_ws.buf, *T = E + nin * batch * pb, *R = dense ? (char *)d_out0 : T + 3 * batch * pb;
+  const void *const ins[4] = {d_a0, d_a1, d_b0, d_b1};
+  for (size_t k = 0; k < nin; ++k)
+    HIPCHK(ctx, hipMemcpy2DAsync(E + k * batch * pb, pb, ins[k], ks * row, ks * row, batch, hipMemcpyDefault, st));  // (a caller's buffer may be pinned host memory)
+  if ((rc = nflhip_baseconv_ntt_dev(ctx, E, E, nin * batch, 0, ks, 0, nm, NFLHIP_BASECONV_CENTERED, st))) return rc;
+  if ((rc = nflhip_tensor_ntt_dev(ctx, T, T + batch * pb, T + 2 * batch * pb, E, E + batch * pb, d_b0 ? E + 2 * batch * pb : nullptr,
+                                  d_b0 ? E + 3 * batch * pb : nullptr, batch, nm, 0, st)))
+    return rc;
+  if ((rc = scale_round_run(ctx, R, T, 3 * batch, ks, t, flags, true, st)) || (rc = set_device(ctx))) return rc;
+  if (!dense) {
+    void *const outs[3] = {d_out0, d_out1, d_out2};
+    for (size_t k = 0; k < 3; ++k) HIPCHK(ctx, hipMemcpyAsync(outs[k], R + k * ob, ob, hipMemcpyDefault, st));
+  }
+  return ws_end(ctx, ctx->bfv_ws, cap, st);
 }
 
 // Ciphertext multiplication with relinearisation (kernels_mulrelin.hip; include/nflhip.h "ciphertext multiplication"): the tensor

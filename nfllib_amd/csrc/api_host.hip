@@ -701,6 +701,46 @@ int nflhip_tensor_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, void *h_out2,
   return s.outs(hout, 3, 2, ob);
 }
 
+// scale-and-round by t/Q: the result has fewer rows per polynomial than the input, so the call is staged whole
+static int scale_round_host(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t ks, uint64_t t, int flags, bool ntt) {
+  size_t obytes = 0;
+  int rc = scale_round_check(ctx, h_out, h_in, batch, ks, t, flags, &obytes);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const HostIn ins[] = {{0, h_in, poly_bytes(ctx, batch)}};
+  return staged_call(ctx, batch, false, ins, 1, {1, h_out, obytes}, [&](const void *const *d, void *o, size_t cnt, void *st) {
+    return ntt ? nflhip_scale_round_ntt_dev(ctx, o, d[0], cnt, ks, t, flags, st) : nflhip_scale_round_dev(ctx, o, d[0], cnt, ks, t, flags, st);
+  });
+}
+int nflhip_scale_round(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t ks, uint64_t t, int flags) {
+  return scale_round_host(ctx, h_out, h_in, batch, ks, t, flags, false);
+}
+int nflhip_scale_round_ntt(nflhip_ctx *ctx, void *h_out, const void *h_in, size_t batch, size_t ks, uint64_t t, int flags) {
+  return scale_round_host(ctx, h_out, h_in, batch, ks, t, flags, true);
+}
+
+// the BFV tensor product: staged as the tensor product above
+int nflhip_bfv_tensor_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, void *h_out2, const void *h_a0, const void *h_a1, const void *h_b0,
+                          const void *h_b1, size_t batch, size_t ks, uint64_t t, int flags) {
+  int rc = bfv_tensor_check(ctx, h_out0, h_out1, h_out2, h_a0, h_a1, h_b0, h_b1, batch, ks, t, flags);
+  if (rc || batch == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t ob = batch * ks * ctx->shape.n * ctx->word, nin = h_b0 ? 4 : 2;
+  Staged s(ctx);
+  if ((rc = s.in(0, nullptr, nin * ob)) || (rc = s.in(2, nullptr, 3 * ob))) return rc;
+  char *i = (char *)ctx->stage[0], *o = (char *)ctx->stage[2];
+  const void *const hin[4] = {h_a0, h_a1, h_b0, h_b1};
+  for (size_t k = 0; k < nin; ++k) {
+    if (ctx->stage_host[0]) std::memcpy(i + k * ob, hin[k], ob);
+    else HIPCHK(ctx, hipMemcpyAsync(i + k * ob, hin[k], ob, hipMemcpyHostToDevice, ctx->hstream));
+  }
+  if ((rc = nflhip_bfv_tensor_ntt_dev(ctx, o, o + ob, o + 2 * ob, i, i + ob, h_b0 ? i + 2 * ob : nullptr, h_b0 ? i + 3 * ob : nullptr, batch, ks, t, flags,
+                                      (void *)ctx->hstream)))
+    return rc;
+  void *const hout[3] = {h_out0, h_out1, h_out2};
+  return s.outs(hout, 3, 2, ob);
+}
+
 // ciphertext multiplication: the inputs (one slot), the key and both outputs are staged whole (the outputs share one slot, out1
 // behind out0, so that the mod-down runs as one batch).  The body of both entries, the arguments checked: the operands have `level`
 // rows (the top-level entry: all nmoduli - k_special, where the level entry on the device forwards), and of the key the digits that

@@ -133,6 +133,18 @@ struct nflhip_ctx {
   std::map<size_t, void *> mr_pi;
   WarmMap mr_warm;
   Workspace mr_ws;
+  // scale-and-round by t/Q (api.hip scale_round_record / scale_round_run): the device record of every (ks, t) used so far, built and
+  // uploaded on first use under srec_mu, freed with the context; workspace 0 holds the inverse-transformed copy of an NTT-form input,
+  // workspace 1 the words Y of the two-pass plan; calls are ordered on both by the event of workspace 0.  The workspaces under sr_mu,
+  // which is taken BEFORE srec_mu and bcn_mu.
+  std::mutex srec_mu, sr_mu;
+  std::map<std::array<uint64_t, 2>, void *> srec;
+  Workspace sr_ws[2];
+  // BFV tensor product (api.hip nflhip_bfv_tensor_ntt_dev): one workspace for the embedded inputs, the tensor's three components on
+  // nmoduli rows and, where the outputs do not follow each other in memory, the scaled components.  Under bfv_mu, which is taken
+  // BEFORE sr_mu.
+  std::mutex bfv_mu;
+  Workspace bfv_ws;
 };
 
 void pipe_destroy(nflhip_ctx *ctx);  // api_host.hip: frees the context's host-pointer pipeline
@@ -607,6 +619,40 @@ inline int mulrelin_check(const nflhip_ctx *ctx, const void *out0, const void *o
         return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin: an output overlaps an input without being that input");
   }
   return NFLHIP_OK;
+}
+// nflhip_scale_round_dev / _ntt_dev / nflhip_scale_round / _ntt: every argument check short of the tables (a repeated modulus is found by
+// their builder, api.hip scale_round_record), before any device use.  *obytes: the size of the output.
+inline int scale_round_args(const nflhip_ctx *ctx, const char *what, size_t ks, uint64_t t, int flags, int allowed) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  const std::string w(what);
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, w + ": a cyclic row context has no modulus chain");
+  if (flags & ~allowed) return fail(ctx, NFLHIP_ERR_INVALID, w + ": unknown flag bits");
+  if (ks == 0 || ks >= ctx->shape.nm) return fail(ctx, NFLHIP_ERR_INVALID, w + ": ks is out of range (1 to nmoduli - 1)");
+  if (t == 0 || t >> (ctx->shape.limb_bits - 3)) return fail(ctx, NFLHIP_ERR_INVALID, w + ": t is out of range (1 to 2^(limb_bits - 3) - 1)");
+  if (ctx->shape.nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, w + ": more than 65535 rows");
+  return NFLHIP_OK;
+}
+inline int scale_round_check(const nflhip_ctx *ctx, const void *out, const void *in, size_t batch, size_t ks, uint64_t t, int flags, size_t *obytes) {
+  int rc = scale_round_args(ctx, "scale_round", ks, t, flags, NFLHIP_SCALE_ROUND_FLOOR | NFLHIP_SCALE_ROUND_KEEP | NFLHIP_SCALE_ROUND_TWO_PASS);
+  if (rc || batch == 0) return rc;
+  if (!out || !in) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, orows = (flags & NFLHIP_SCALE_ROUND_KEEP) ? nm - ks : ks;
+  size_t ib, ob;
+  if (__builtin_mul_overflow(batch, nm * row, &ib) || __builtin_mul_overflow(batch, orows * row, &ob))
+    return fail(ctx, NFLHIP_ERR_INVALID, "scale_round: the size overflows");
+  if (ranges_overlap(out, ob, in, ib)) return fail(ctx, NFLHIP_ERR_INVALID, "scale_round: the output overlaps the input (the strides differ: never in place)");
+  if (obytes) *obytes = ob;
+  return NFLHIP_OK;
+}
+// nflhip_bfv_tensor_ntt_dev / nflhip_bfv_tensor_ntt: the scale-round's own arguments, then the tensor product's on ks rows
+inline int bfv_tensor_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *out2, const void *a0, const void *a1,
+                            const void *b0, const void *b1, size_t batch, size_t ks, uint64_t t, int flags) {
+  int rc = scale_round_args(ctx, "bfv_tensor", ks, t, flags, NFLHIP_SCALE_ROUND_FLOOR | NFLHIP_SCALE_ROUND_TWO_PASS);
+  if (rc) return rc;
+  size_t polys, sb;  // (the scratch: [4 + 3][batch] polynomials of nmoduli rows and the scaled components)
+  if (__builtin_mul_overflow(batch, (size_t)10, &polys) || __builtin_mul_overflow(polys, poly_bytes(ctx, 1), &sb))
+    return fail(ctx, NFLHIP_ERR_INVALID, "bfv_tensor: the size overflows");
+  return tensor_check(ctx, out0, out1, out2, a0, a1, b0, b1, batch, ks, 0);
 }
 constexpr size_t kStageHostMax = (size_t)1 << 20;
 inline void free_stage(nflhip_ctx *ctx, int slot) {

@@ -476,6 +476,37 @@ int build_baseconv_record(int limb_bits, const std::vector<uint64_t> &P, size_t 
   return NFLHIP_OK;
 }
 
+// Scale-and-round by t/Q: the two conversion records one behind the other (host_tables.h), the first one carrying t.
+int build_scale_round_record(int limb_bits, const std::vector<uint64_t> &P, size_t ks, uint64_t t, std::vector<uint64_t> *out, std::string *err) {
+  const size_t nm = P.size();
+  if (ks == 0 || ks >= nm) return invalid(err, "scale_round: ks is out of range (1 to nmoduli - 1)");
+  if (t == 0 || t >> (limb_bits - 3)) return invalid(err, "scale_round: t is out of range (1 to 2^(limb_bits - 3) - 1)");
+  const size_t kd = nm - ks;
+  std::vector<uint64_t> fwd, back;
+  int rc = build_baseconv_record(limb_bits, P, 0, ks, ks, kd, false, &fwd, err);
+  if (!rc) rc = build_baseconv_record(limb_bits, P, ks, kd, 0, ks, false, &back, err);
+  if (rc) return rc;
+  uint64_t *src = fwd.data(), *dst = src + 4 * ks;
+  for (size_t i = 0; i < ks; ++i) {  // y_i = x_i (t (Q/p_i)^-1) mod p_i: t folded into the constant, the same words
+    const uint64_t p = P[i], w = mulmod_h(src[4 * i], t % p, p);
+    src[4 * i] = w;
+    src[4 * i + 1] = shoup_h(w, p, limb_bits);
+  }
+  for (size_t j = 0; j < kd; ++j) {
+    const uint64_t p = dst[8 * j], Qj = dst[8 * j + 1];
+    if (Qj == 0) return invalid(err, "scale_round: a modulus of the rows D repeats one of the rows S");
+    const uint64_t inv = powmod_h(Qj, p - 2, p);
+    dst[8 * j + 3] = inv;
+    dst[8 * j + 4] = shoup_h(inv, p, limb_bits);
+    dst[8 * j + 5] = t % p;
+    dst[8 * j + 6] = shoup_h(t % p, p, limb_bits);
+  }
+  *out = fwd;
+  out->resize(scale_round_back_offset(ks, kd), 0);  // (the second record starts on 32 bytes, as a record of its own does)
+  out->insert(out->end(), back.begin(), back.end());
+  return NFLHIP_OK;
+}
+
 // the reference's own table layouts (poly.hpp:228-237), rebuilt on the host from phi: what a caller holding
 // core::base sees.  Host arithmetic, once per request; the device never reads these.
 std::vector<uint64_t> reference_table(uint64_t p, uint64_t phi, uint64_t invk, int kmax_log2, size_t n, int wb, int which) {

@@ -47,6 +47,16 @@ int build_baseconv_record(int limb_bits, const std::vector<uint64_t> &P, size_t 
                           std::vector<uint64_t> *out, std::string *err);
 inline size_t baseconv_record_words(size_t ks, size_t kd) { return 4 * ks + 8 * kd + ks * kd; }
 
+// Scale-and-round by t/Q (kernels_scale_round.hip; include/nflhip.h "BFV multiplication"): S = [0, ks), D = [ks, nm), kd = nm - ks.
+// Two records of the layout above, one behind the other:
+//   first   (S -> D), baseconv_record_words(ks, kd) words, with t folded in: a source row's constant is t (Q/p_i)^-1 mod p_i and its
+//           Shoup companion; a destination row's words 3, 4 hold Q^-1 mod p_j and its companion, words 5, 6 t and its companion
+//   second  (D -> S), from word scale_round_back_offset(ks, kd) on (the first record padded to 32 bytes), baseconv_record_words(kd, ks)
+//           words, exactly build_baseconv_record(ks, kd, 0, ks, false): k_baseconv reads it
+// Returns NFLHIP_OK, or NFLHIP_ERR_INVALID with *err set: ks outside [1, nm - 1], t outside [1, 2^(limb_bits - 3)), a repeated modulus.
+inline size_t scale_round_back_offset(size_t ks, size_t kd) { return (baseconv_record_words(ks, kd) + 3) & ~(size_t)3; }
+int build_scale_round_record(int limb_bits, const std::vector<uint64_t> &P, size_t ks, uint64_t t, std::vector<uint64_t> *out, std::string *err);
+
 // nflhip_get_table, NFLHIP_TAB_PHIS .. NFLHIP_TAB_INVOMEGAS: one modulus's table in the reference's own layout (n words, 2 n for
 // the two omega tables), each word below 2^limb_bits
 std::vector<uint64_t> reference_table(uint64_t p, uint64_t phi, uint64_t invk, int kmax_log2, size_t n, int limb_bits, int which);

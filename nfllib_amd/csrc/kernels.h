@@ -164,6 +164,15 @@ hipError_t launch_baseconv(const Shape &s, const DevTables &t, T *out, const T *
 template <typename T>
 hipError_t launch_baseconv_rows(const Shape &s, const DevTables &t, T *out, size_t onm, const T *in, size_t inm, const uint64_t *rec, size_t batch,
                                 size_t ks, size_t d0, size_t kd, int centred, hipStream_t st);
+// RNS scale-and-round by t/Q (kernels_scale_round.hip; include/nflhip.h "BFV multiplication"): in = [batch][nm][n] coefficient form, S
+// the first ks rows; out = the dense [batch][ks][n], or with `keep` the dense [batch][nm - ks][n] of the words Y.  rec: the device copy
+// of build_scale_round_record (host_tables.h).  centred: the first conversion (the second always is).  chunked = 0: the register
+// plans, hipErrorNotSupported where neither holds the rows (scale_round_in_registers); chunked = 1: keep only, any shape.  out never
+// overlaps in (api.hip checks).
+inline bool scale_round_in_registers(size_t ks, size_t kd) { return ks <= 8 && kd <= 9; }
+template <typename T>
+hipError_t launch_scale_round(const Shape &s, const DevTables &t, T *out, const T *in, const uint64_t *rec, size_t batch, size_t ks, int centred,
+                              int keep, int chunked, hipStream_t st);
 // NTT-form base conversion and mod-down (kernels_baseconv_ntt.hip; include/nflhip.h "RNS base conversion, NTT form").  _fused: ONE
 // launch, a workgroup per polynomial with ks + 1 rows in LDS, one more in centred mode; hipErrorNotSupported when that exceeds 64 KiB
 // or n < 4.  Operands as launch_baseconv.  _combine: the last pass of the composed mod-down, out row j = (in row j - out row j) P^-1
@@ -406,6 +415,7 @@ hipError_t warm_mulrelin(hipStream_t st);
 hipError_t warm_decompose(hipStream_t st);
 hipError_t warm_baseconv(hipStream_t st);
 hipError_t warm_baseconv_ntt(hipStream_t st);
+hipError_t warm_scale_round(hipStream_t st);
 hipError_t warm_keyswitch(hipStream_t st);
 int polymul_level();   // 0 / 1 / 2: transforms of the coefficient-form products complete / incomplete (asm_launch.hip, nflhip_debug_polymul_level)
 hipError_t launch_polymul_pipe64k_u64(const Shape &s, const DevTables &t, uint64_t *c_v, const uint64_t *a_v,

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MULRELIN_CENTERED, MULRELIN_FLOOR, MULRELIN_FUSED, MULRELIN_MERGED, MULRELIN_RESCALE, MULRELIN_SEQUENCE, LINTRANS_CENTERED, LINTRANS_FLOOR, LINTRANS_HOISTED, LINTRANS_MAX_TERMS, LINTRANS_SEQUENCE, MAC_MAX_TERMS, MAC_DOUBLE_BUFFER, MAC_MULTI_MAX_OUTPUTS, BSGS_CENTERED, BSGS_FLOOR, BSGS_HOISTED, BSGS_MAX_BABY, BSGS_MAX_GIANT, BSGS_SEQUENCE, DOT_MULTI_MAX_OUTPUTS, ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_HOISTED, ROTATE_MAX_OUTPUTS, ROTATE_SEQUENCE, KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
+from ._lib import (SCALE_ROUND_FLOOR, SCALE_ROUND_KEEP, SCALE_ROUND_TWO_PASS, MULRELIN_CENTERED, MULRELIN_FLOOR, MULRELIN_FUSED, MULRELIN_MERGED, MULRELIN_RESCALE, MULRELIN_SEQUENCE, LINTRANS_CENTERED, LINTRANS_FLOOR, LINTRANS_HOISTED, LINTRANS_MAX_TERMS, LINTRANS_SEQUENCE, MAC_MAX_TERMS, MAC_DOUBLE_BUFFER, MAC_MULTI_MAX_OUTPUTS, BSGS_CENTERED, BSGS_FLOOR, BSGS_HOISTED, BSGS_MAX_BABY, BSGS_MAX_GIANT, BSGS_SEQUENCE, DOT_MULTI_MAX_OUTPUTS, ROTATE_CENTERED, ROTATE_FLOOR, ROTATE_HOISTED, ROTATE_MAX_OUTPUTS, ROTATE_SEQUENCE, KEYSWITCH_CENTERED, KEYSWITCH_COMPOSED, KEYSWITCH_FLOOR, KEYSWITCH_FUSED, KEYSWITCH_SEQUENCE, AUTOMORPHISM_MAX_OUTPUTS, BASECONV_CENTERED, BASECONV_NTT_COMPOSED, BASECONV_NTT_FUSED, MODDOWN_FLOOR, DECOMP_COMPOSED, DECOMP_FUSED, DECOMP_SIGNED, DOT_MAX_POINTERS, DOT_UNTILED, FORM_COEFF, FORM_NTT, RESCALE_COMPOSED, RESCALE_FUSED,  # noqa: F401
                    FMT_I8, FMT_I16, FMT_I32, FMT_WORDS, NflHipError, OP_ADD, OP_COMPUTE_SHOUP, OP_MUL, OP_MUL_SHOUP, OP_SUB,  # noqa: F401
                    DIST_REFERENCE_WORDS, ROW_BITREV_IO, ROW_INVERSE_TABLES, TAB_INVDEGREE, TAB_INVOMEGAS,
                    TAB_INVPOLY_INVPHIS, TAB_MODULUS, TAB_OMEGAS, TAB_PHIS, TAB_PSI, TAB_SHOUPINVPOLY_INVPHIS,
@@ -70,6 +70,9 @@ class Engine:
         self.bytes_per_poly = self.words_per_poly * self.np_dtype.itemsize
 
     def close(self):
+        kept = self.__dict__.pop("_bfv_kept", None)   # (bfv_mul_relin_ntt's engine over the first L moduli)
+        if kept is not None:
+            kept.close()
         if getattr(self, "ctx", None):
             self.lib.nflhip_ctx_destroy(self.ctx)
             self.ctx = None
@@ -849,6 +852,72 @@ class Engine:
         outs = tuple(np.empty((batch, rows, self.degree), dtype=self.np_dtype) for _ in range(3))
         self._chk(self.lib.nflhip_tensor_ntt(self.ctx, _vp(outs[0]), _vp(outs[1]), _vp(outs[2]), _vp(a0), _vp(a1), _vp(b0), _vp(b1), batch, rows, 0))
         return outs
+
+    # ---- BFV multiplication (include/nflhip.h "BFV multiplication") ----
+    _SR_PLAN = {None: 0, "two_pass": SCALE_ROUND_TWO_PASS}
+
+    def _sr_flags(self, floor, keep, plan):
+        return (SCALE_ROUND_FLOOR if floor else 0) | (SCALE_ROUND_KEEP if keep else 0) | self._SR_PLAN[plan]
+
+    def scale_round(self, a, ks, t, floor=False, keep=False, ntt=False, out=None, plan=None, stream=None):
+        """round(t X / Q) of the batch a = [batch, nm, n], Q the product of the first ks moduli, carried back onto those rows: a new
+        [batch, ks, n] tensor in the layout of Engine(limb_bits, degree, ks) (or `out`, which must not overlap a).  keep=True stops
+        at the words Y on the other rows: [batch, nm - ks, n].  floor=True: the fast first conversion, floor(t X / Q) - u.  ntt=True:
+        NTT form in and out.  plan="two_pass" forces the two-pass plan.  The first call for a (ks, t) uploads its tables (and the
+        two-pass plan and the NTT form allocate scratch): make it before a graph capture."""
+        batch = self._batch(a)
+        if out is None:
+            rows = self.nmoduli - ks if keep else ks
+            out = _torch().empty((batch, max(rows, 0), self.degree), dtype=self.torch_dtype, device=a.device)
+        fn = self.lib.nflhip_scale_round_ntt_dev if ntt else self.lib.nflhip_scale_round_dev
+        self._chk(fn(self.ctx, _vp(out), _vp(a), batch, ks, t, self._sr_flags(floor, keep, plan), self._stream(stream)))
+        return out
+
+    def h_scale_round(self, a, ks, t, floor=False, keep=False, ntt=False, plan=None):
+        """host-pointer variant: a numpy [batch, nm, n] batch -> [batch, ks, n] ([batch, nm - ks, n] with keep)"""
+        a = np.ascontiguousarray(a, dtype=self.np_dtype)
+        batch = self._hb(a)
+        out = np.empty((batch, max(self.nmoduli - ks if keep else ks, 0), self.degree), dtype=self.np_dtype)
+        fn = self.lib.nflhip_scale_round_ntt if ntt else self.lib.nflhip_scale_round
+        self._chk(fn(self.ctx, _vp(out), _vp(a), batch, ks, t, self._sr_flags(floor, keep, plan)))
+        return out
+
+    def bfv_tensor_ntt(self, a0, a1, b0, b1, L, t, floor=False, outs=None, plan=None, stream=None):
+        """the scale-invariant tensor product of the BFV ciphertexts (a0, a1) and (b0, b1), NTT-form [batch, L, n] blocks over the first
+        L moduli of this context (the other nm - L are the extension B): base extension, tensor product on nm rows, round(t . / Q)
+        back onto the L rows.  b0 = b1 = None: the square.  `outs` = three [batch, L, n] tensors (any may be one of the inputs), else
+        views of one new [3, batch, L, n] tensor.  The first call for an (L, t), or a larger batch, allocates."""
+        rows, batch = self._tensor_rows(a0, a1, b0, b1, L, lambda x: x.numel(), lambda x: x.is_contiguous())
+        if outs is None:
+            o = _torch().empty((3, batch, rows, self.degree), dtype=self.torch_dtype, device=a0.device)
+            outs = (o[0], o[1], o[2])
+        elif len(outs) != 3 or any(o.numel() != a0.numel() or not o.is_contiguous() for o in outs):
+            raise ValueError("outs are three contiguous [batch, L, n] tensors")
+        self._chk(self.lib.nflhip_bfv_tensor_ntt_dev(self.ctx, _vp(outs[0]), _vp(outs[1]), _vp(outs[2]), _vp(a0), _vp(a1), _vp(b0), _vp(b1), batch, rows,
+                                                     t, self._sr_flags(floor, False, plan), self._stream(stream)))
+        return outs
+
+    def h_bfv_tensor_ntt(self, a0, a1, b0, b1, L, t, floor=False, plan=None):
+        """host-pointer variant: numpy blocks [batch, L, n] -> (out0, out1, out2)"""
+        a0, a1, b0, b1 = (None if x is None else np.ascontiguousarray(x, dtype=self.np_dtype) for x in (a0, a1, b0, b1))
+        rows, batch = self._tensor_rows(a0, a1, b0, b1, L, lambda x: x.size, lambda x: True)
+        outs = tuple(np.empty((batch, rows, self.degree), dtype=self.np_dtype) for _ in range(3))
+        self._chk(self.lib.nflhip_bfv_tensor_ntt(self.ctx, _vp(outs[0]), _vp(outs[1]), _vp(outs[2]), _vp(a0), _vp(a1), _vp(b0), _vp(b1), batch, rows, t,
+                                                 self._sr_flags(floor, False, plan)))
+        return outs
+
+    def bfv_mul_relin_ntt(self, ks_engine, a0, a1, b0, b1, key, L, t, K, alpha, floor=False, plan=None, stream=None):
+        """the product of two BFV ciphertexts with relinearisation: bfv_tensor_ntt on this context (the first L + kb moduli), the key
+        switch of its third component by ks_engine -- the engine over the first L + K moduli, key = [dnum, 2, L + K, n] from s^2 to s
+        as key_switch_ntt takes it -- and the two sums.  A thin composition, no entry of its own.  Returns (out0, out1), [batch, L, n]."""
+        if ks_engine.nmoduli != L + K or ks_engine.limb_bits != self.limb_bits or ks_engine.degree != self.degree:
+            raise ValueError("ks_engine is the engine over the first L + K moduli")
+        d0, d1, d2 = self.bfv_tensor_ntt(a0, a1, b0, b1, L, t, floor=floor, plan=plan, stream=stream)
+        k0, k1 = ks_engine.key_switch_ntt(d2, key, K, alpha, stream=stream)
+        kept = getattr(self, "_bfv_kept", None)
+        if kept is None or kept.nmoduli != L:
+            kept = self._bfv_kept = Engine(self.limb_bits, self.degree, L, device=self.device)
+        return kept.pointwise(OP_ADD, d0, k0, out=d0, stream=stream), kept.pointwise(OP_ADD, d1, k1, out=d1, stream=stream)
 
     def mul_relin_ntt(self, a0, a1, b0, b1, key, k_special, alpha, rescale=False, centered=False, floor=False, out=None, plan=None, stream=None,
                       level=None):
