@@ -351,6 +351,43 @@ template <class P> class device_batch {
                                                            P::nmoduli, flags, key.queue()), "mul_relin_level_ntt");
     key.sync();
   }
+  // Sums of ciphertext products at a level (include/nflhip.h "sums of ciphertext products"): a0, a1 hold groups * terms polynomials,
+  // [group][term]; b0, b1 alike, or `terms` polynomials shared by every group with b_shared (both NULL: the sums of squares); the
+  // outputs hold `groups` polynomials and their ring decides the rescale, as in assign_mul_relin.  The key, K and the level as in
+  // assign_mul_relin_level; Lv = M - K is the top level.  Streams as in assign_key_switch.
+  template <size_t K, class O, class Q>
+  static void assign_mul_relin_dot_level(device_batch<O> &out0, device_batch<O> &out1, const device_batch &a0, const device_batch &a1,
+                                         const device_batch *b0, const device_batch *b1, size_t terms, const device_batch<Q> &key, size_t alpha,
+                                         bool b_shared = false, bool centered = false, bool floor = false) {
+    static_assert(std::is_same<typename Q::value_type, value_type>::value && Q::degree == P::degree && K >= 1 && K < Q::nmoduli &&
+                      P::nmoduli <= Q::nmoduli - K,
+                  "assign_mul_relin_dot_level: the key's ring has the same limbs and degree, K special moduli and at least Lv others");
+    static_assert(std::is_same<typename O::value_type, value_type>::value && O::degree == P::degree &&
+                      (O::nmoduli == P::nmoduli || O::nmoduli + 1 == P::nmoduli),
+                  "assign_mul_relin_dot_level: the outputs live in the inputs' ring, or in the ring with one modulus less (the rescale)");
+    if (alpha == 0 || alpha > Q::nmoduli - K) throw std::runtime_error("nfl(hip): mul_relin_dot_level: alpha is out of range (1 to the key's ordinary moduli)");
+    if (!b0 != !b1) throw std::runtime_error("nfl(hip): mul_relin_dot_level: b0 and b1 are both given, or both NULL for the squares");
+    if (terms == 0 || a0.size() % terms) throw std::runtime_error("nfl(hip): mul_relin_dot_level: a0 holds groups * terms polynomials");
+    const size_t groups = a0.size() / terms;
+    if (out0.size() != groups || out1.size() != groups || a1.size() != a0.size() ||
+        (b0 && (b0->size() != (b_shared ? terms : a0.size()) || b1->size() != b0->size())))
+      throw std::runtime_error("nfl(hip): batch sizes differ");
+    if (key.size() != 2 * ((Q::nmoduli - K + alpha - 1) / alpha)) throw std::runtime_error("nfl(hip): the key batch holds the 2 * dnum polynomials of the top level");
+    if (out0.device() != key.device() || out1.device() != key.device() || a0.device() != key.device() || a1.device() != key.device() ||
+        (b0 && (b0->device() != key.device() || b1->device() != key.device())))
+      throw std::runtime_error("nfl(hip): mul_relin_dot_level operands on different devices");
+    a0.sync();
+    out0.sync();
+    a0.strict("mul_relin_dot_level"), a1.strict("mul_relin_dot_level"), key.strict("mul_relin_dot_level");
+    if (b0) b0->strict("mul_relin_dot_level"), b1->strict("mul_relin_dot_level");
+    const int rescale = O::nmoduli != P::nmoduli ? NFLHIP_MULRELIN_RESCALE : 0;
+    const int flags = (centered ? NFLHIP_MULRELIN_CENTERED : 0) | (floor ? NFLHIP_MULRELIN_FLOOR : 0) | rescale;
+    const nflhip_dot_operand x0 = {a0.d_, terms, 1}, x1 = {a1.d_, terms, 1};
+    const nflhip_dot_operand y0 = {b0 ? b0->d_ : nullptr, b_shared ? 0 : terms, 1}, y1 = {b1 ? b1->d_ : nullptr, b_shared ? 0 : terms, 1};
+    detail::check(key.ctx(), nflhip_mulrelin_dot_ntt_dev(key.ctx(), out0.data(), out1.data(), &x0, &x1, b0 ? &y0 : nullptr, b1 ? &y1 : nullptr, key.data(),
+                                                         groups, terms, K, alpha, P::nmoduli, flags, key.queue()), "mul_relin_dot_level_ntt");
+    key.sync();
+  }
   // Hoisted rotations and slot linear transforms at a level (include/nflhip.h "rotations and linear transforms at a level"): this
   // ring's moduli count is the level Lv; key_batches[m] is a batch of the ring with M moduli holding the 2 dnum_L polynomials of the ONE
   // top-level Galois key of rotation m (NULL: the unrotated diagonal of a linear transform), weight_batches[m] one holding the ONE

@@ -579,6 +579,105 @@ template <class T, size_t Degree, size_t NbModuli> class poly_p {
     out1._p = d1;
   }
 
+  // Sums of ciphertext products (nfl::tensor_dot_ntt / mul_relin_dot_level_ntt<K> / square_relin_dot_level_ntt<K> below; include/nflhip.h
+  // "sums of ciphertext products").  Every operand is an ARRAY of `terms` polynomials; the arrays are gathered into one device buffer,
+  // [operand][term], the way mul_relin_level_into gathers the key, and read as one group of `terms` terms.  tensor_dot_into: this ring
+  // type is the operands' and the outputs'.  mul_relin_dot_level_into: this ring type is the KEY's, K and the level LO as in
+  // mul_relin_level_into, of which it has the ordering, the payloads and the errors.  Never fused into a queue's rewrites.
+  static void tensor_dot_into(poly_p &out0, poly_p &out1, poly_p &out2, poly_p const *a0, poly_p const *a1, poly_p const *b0, poly_p const *b1,
+                              size_t terms) {
+    if (!b0 != !b1) throw std::runtime_error("nfl(hip): tensor_dot_ntt: b0 and b1 are both given, or both NULL for the squares");
+    if (terms == 0) throw std::runtime_error("nfl(hip): tensor_dot_ntt: at least one term");
+    const size_t nin = b0 ? 4 : 2, pb = sizeof(T) * Degree * NbModuli;
+    lazy_t::inst().flush();
+    poly_p const *const ops[4] = {a0, a1, b0, b1};
+    std::vector<ptr_type> kept;
+    for (size_t k = 0; k < nin; ++k)
+      for (size_t j = 0; j < terms; ++j) {
+        if (!ops[k][j]._p) throw std::runtime_error("nfl(hip): an operand polynomial is empty (moved from)");
+        kept.push_back(ops[k][j]._p);
+      }
+    ptr_type d0 = fresh(), d1 = fresh(), d2 = fresh();
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo(), *o2 = d2->dev_wo(), *gat = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &gat, nin * terms * pb), "tensor_dot_ntt");
+    int rc = NFLHIP_OK;
+    for (size_t i = 0; i < kept.size() && rc == NFLHIP_OK; ++i)
+      rc = nflhip_memcpy_d2d(ctx_t::get(), static_cast<char *>(gat) + i * pb, kept[i]->dev_ro(), pb, ctx_t::queue());
+    nflhip_dot_operand op[4];
+    for (size_t k = 0; k < 4; ++k) op[k].ptr = static_cast<char *>(gat) + (k < nin ? k : 0) * terms * pb, op[k].group_stride = terms, op[k].term_stride = 1;
+    if (rc == NFLHIP_OK)
+      rc = nflhip_tensor_dot_ntt_dev(ctx_t::get(), o0, o1, o2, &op[0], &op[1], b0 ? &op[2] : nullptr, b0 ? &op[3] : nullptr, 1, terms, NbModuli, 0,
+                                     ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered operands go)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), gat);
+      throw std::runtime_error("nfl(hip): tensor_dot_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), gat);
+    detail::check(ctx_t::get(), rs, "tensor_dot_ntt");
+    out0._p = d0;
+    out1._p = d1;
+    out2._p = d2;
+  }
+  template <size_t K, size_t LO, size_t OO> static void mul_relin_dot_level_into(poly_p<T, Degree, OO> &out0, poly_p<T, Degree, OO> &out1,
+                                                                                 poly_p<T, Degree, LO> const *a0, poly_p<T, Degree, LO> const *a1,
+                                                                                 poly_p<T, Degree, LO> const *b0, poly_p<T, Degree, LO> const *b1,
+                                                                                 size_t terms, poly_p const *key, size_t alpha, bool centered,
+                                                                                 bool floor) {
+    static_assert(K >= 1 && K < NbModuli && LO >= 1 && LO <= NbModuli - K, "nfl::mul_relin_dot_level_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+    static_assert(OO == LO || OO + 1 == LO, "nfl::mul_relin_dot_level_ntt<K>: the outputs live in the inputs' ring, or in the ring with one modulus less");
+    typedef poly_p<T, Degree, LO> in_t;
+    typedef poly_p<T, Degree, OO> out_t;
+    if (alpha == 0 || alpha > NbModuli - K) throw std::runtime_error("nfl(hip): mul_relin_dot_level_ntt: alpha is out of range (1 to the key ring's ordinary moduli)");
+    if (!b0 != !b1) throw std::runtime_error("nfl(hip): mul_relin_dot_level_ntt: b0 and b1 are both given, or both NULL for the squares");
+    if (terms == 0) throw std::runtime_error("nfl(hip): mul_relin_dot_level_ntt: at least one term");
+    const size_t pb = sizeof(T) * Degree * NbModuli, qb = sizeof(T) * Degree * LO, nin = b0 ? 4 : 2, live = 2 * ((LO + alpha - 1) / alpha);
+    lazy_t::inst().flush();
+    in_t::lazy_t::inst().flush();
+    out_t::lazy_t::inst().flush();
+    in_t const *const ops[4] = {a0, a1, b0, b1};
+    std::vector<typename in_t::ptr_type> ins;
+    for (size_t k = 0; k < nin; ++k)
+      for (size_t j = 0; j < terms; ++j) {
+        if (!ops[k][j]._p) throw std::runtime_error("nfl(hip): an operand polynomial is empty (moved from)");
+        ins.push_back(ops[k][j]._p);
+      }
+    typename out_t::ptr_type d0 = out_t::fresh(), d1 = out_t::fresh();
+    std::vector<ptr_type> kept;
+    for (size_t t = 0; t < live; ++t) {  // (the live polynomials only: the rest of the key may be anything, even moved from)
+      if (!key[t]._p) throw std::runtime_error("nfl(hip): a live key polynomial is empty (moved from)");
+      kept.push_back(key[t]._p);
+    }
+    std::vector<const void *> src;
+    for (size_t i = 0; i < ins.size(); ++i) src.push_back(ins[i]->dev_ro());
+    void *o0 = d0->dev_wo(), *o1 = d1->dev_wo(), *kgat = nullptr;
+    detail::check(ctx_t::get(), nflhip_malloc(ctx_t::get(), &kgat, live * pb + nin * terms * qb), "mul_relin_dot_level_ntt");
+    char *const kpos = static_cast<char *>(kgat), *const gat = kpos + live * pb;  // the operands behind the key: [operand][term], LO rows each
+    int rc = NFLHIP_OK;
+    for (size_t t = 0; t < live && rc == NFLHIP_OK; ++t) rc = nflhip_memcpy_d2d(ctx_t::get(), kpos + t * pb, kept[t]->dev_ro(), pb, ctx_t::queue());
+    if (rc == NFLHIP_OK) rc = nflhip_stream_sync(in_t::ctx_t::get(), in_t::ctx_t::queue());
+    if (rc == NFLHIP_OK && OO != LO) rc = nflhip_stream_sync(out_t::ctx_t::get(), out_t::ctx_t::queue());
+    for (size_t i = 0; i < src.size() && rc == NFLHIP_OK; ++i) rc = nflhip_memcpy_d2d(ctx_t::get(), gat + i * qb, src[i], qb, ctx_t::queue());
+    nflhip_dot_operand op[4];
+    for (size_t k = 0; k < 4; ++k) op[k].ptr = gat + (k < nin ? k : 0) * terms * qb, op[k].group_stride = terms, op[k].term_stride = 1;
+    int flags = (centered ? NFLHIP_MULRELIN_CENTERED : 0) | (floor ? NFLHIP_MULRELIN_FLOOR : 0);
+    if (OO != LO) flags |= NFLHIP_MULRELIN_RESCALE;
+    if (rc == NFLHIP_OK)
+      rc = nflhip_mulrelin_dot_ntt_dev(ctx_t::get(), o0, o1, &op[0], &op[1], b0 ? &op[2] : nullptr, b0 ? &op[3] : nullptr, kgat, 1, terms, K, alpha, LO, flags,
+                                       ctx_t::queue());
+    const int rs = nflhip_stream_sync(ctx_t::get(), ctx_t::queue());  // (before the gathered key and operands go)
+    if (rc != NFLHIP_OK) {
+      const std::string why = nflhip_last_error(ctx_t::get());  // (before nflhip_free replaces the text)
+      nflhip_free(ctx_t::get(), kgat);
+      throw std::runtime_error("nfl(hip): mul_relin_dot_level_ntt: " + why);
+    }
+    nflhip_free(ctx_t::get(), kgat);
+    detail::check(ctx_t::get(), rs, "mul_relin_dot_level_ntt");
+    out0._p = d0;
+    out1._p = d1;
+  }
+
   // Hoisted rotations and slot linear transforms at a level (nfl::rotate_hoisted_level_ntt<K> / linear_transform_level_ntt<K> below;
   // include/nflhip.h "rotations and linear transforms at a level").  This ring type is the KEYS' and the diagonals': NbModuli moduli,
   // the last K special -- explicit, as in key_switch_level_into.  c0, c1 and the outputs live in the ring with LO <= NbModuli - K
@@ -1277,6 +1376,78 @@ void mul_relin_rescale_level_ntt(poly_p<T, D, Lv - 1> &out0, poly_p<T, D, Lv - 1
                                  bool centered = false, bool floor = false) {
   static_assert(Lv >= 2, "nfl::mul_relin_rescale_level_ntt drops the last live modulus: the level is at least two");
   poly_p<T, D, M>::template mul_relin_level_into<K, Lv, Lv - 1>(out0, out1, a0, a1, &b0, &b1, key, alpha, centered, floor);
+}
+
+/* Sums of ciphertext products (include/nflhip.h "sums of ciphertext products").  a0, a1, b0, b1 are ARRAYS of `terms` polynomials, term j
+ * the ciphertexts (a0[j], a1[j]) and (b0[j], b1[j]).  tensor_dot_ntt: (d0, d1, d2) = sum_j (a0 b0, a0 b1 + a1 b0, a1 b1)(j), in the operands'
+ * ring; b0 = b1 = nullptr: the sums of squares.  mul_relin_dot_level_ntt<K>: sum_j ct_a[j] ct_b[j] relinearised ONCE -- the words of
+ * (d0, d1) + key_switch_level_ntt<K>(d2) -- with the key, K and the level Lv as in mul_relin_level_ntt<K>; Lv = M - K is the top level.
+ * The outputs' ring decides the rescale: poly<T, D, Lv>, or poly<T, D, Lv - 1> for the division by the last live modulus in the same
+ * rounding.  square_relin_dot_level_ntt<K>: the sum of squares.  Never fused into a queue's rewrites. */
+namespace detail {
+template <size_t K, class T, size_t D, size_t Lv, size_t O, size_t M>
+void mul_relin_dot_level_host(poly<T, D, O> &out0, poly<T, D, O> &out1, poly<T, D, Lv> const *a0, poly<T, D, Lv> const *a1, poly<T, D, Lv> const *b0,
+                              poly<T, D, Lv> const *b1, size_t terms, poly<T, D, M> const *key, size_t alpha, bool centered, bool floor) {
+  static_assert(K >= 1 && K < M && Lv >= 1 && Lv <= M - K, "nfl::mul_relin_dot_level_ntt<K>: the level is 1 to the key ring's ordinary moduli");
+  static_assert(O == Lv || O + 1 == Lv, "nfl::mul_relin_dot_level_ntt<K>: the outputs live in the inputs' ring, or in the ring with one modulus less");
+  typedef poly<T, D, O> S;
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T) && sizeof(poly<T, D, Lv>) == D * Lv * sizeof(T), "dense poly arrays");
+  S *t0 = S::make_temp(), *t1 = S::make_temp();  // (an output may be an input)
+  int flags = (centered ? NFLHIP_MULRELIN_CENTERED : 0) | (floor ? NFLHIP_MULRELIN_FLOOR : 0);
+  if (O != Lv) flags |= NFLHIP_MULRELIN_RESCALE;
+  const int rc = nflhip_mulrelin_dot_ntt(P::ctx(), t0->data(), t1->data(), a0->cdata(), a1->cdata(), b0 ? b0->cdata() : nullptr, b1 ? b1->cdata() : nullptr,
+                                         key->cdata(), 1, terms, 0, K, alpha, Lv, flags);
+  if (rc == 0) {
+    std::memcpy(static_cast<void *>(out0.data()), t0->cdata(), sizeof(S));
+    std::memcpy(static_cast<void *>(out1.data()), t1->cdata(), sizeof(S));
+  }
+  S::drop_temp(t0);
+  S::drop_temp(t1);
+  check(P::ctx(), rc, "mul_relin_dot_level_ntt");
+}
+}  // namespace detail
+template <class T, size_t D, size_t M>
+void tensor_dot_ntt(poly<T, D, M> &d0, poly<T, D, M> &d1, poly<T, D, M> &d2, poly<T, D, M> const *a0, poly<T, D, M> const *a1, poly<T, D, M> const *b0,
+                    poly<T, D, M> const *b1, size_t terms) {
+  typedef poly<T, D, M> P;
+  static_assert(sizeof(P) == D * M * sizeof(T), "dense poly array");
+  P *t[3] = {P::make_temp(), P::make_temp(), P::make_temp()};  // (an output may be an input)
+  const int rc = nflhip_tensor_dot_ntt(P::ctx(), t[0]->data(), t[1]->data(), t[2]->data(), a0->cdata(), a1->cdata(), b0 ? b0->cdata() : nullptr,
+                                       b1 ? b1->cdata() : nullptr, 1, terms, 0, M, 0);
+  P *const outs[3] = {&d0, &d1, &d2};
+  for (int k = 0; k < 3; ++k) {
+    if (rc == 0) std::memcpy(static_cast<void *>(outs[k]->data()), t[k]->cdata(), sizeof(P));
+    P::drop_temp(t[k]);
+  }
+  detail::check(P::ctx(), rc, "tensor_dot_ntt");
+}
+template <class T, size_t D, size_t M>
+void tensor_dot_ntt(poly_p<T, D, M> &d0, poly_p<T, D, M> &d1, poly_p<T, D, M> &d2, poly_p<T, D, M> const *a0, poly_p<T, D, M> const *a1,
+                    poly_p<T, D, M> const *b0, poly_p<T, D, M> const *b1, size_t terms) {
+  poly_p<T, D, M>::tensor_dot_into(d0, d1, d2, a0, a1, b0, b1, terms);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t O, size_t M>
+void mul_relin_dot_level_ntt(poly<T, D, O> &out0, poly<T, D, O> &out1, poly<T, D, Lv> const *a0, poly<T, D, Lv> const *a1, poly<T, D, Lv> const *b0,
+                             poly<T, D, Lv> const *b1, size_t terms, poly<T, D, M> const *key, size_t alpha, bool centered = false, bool floor = false) {
+  detail::mul_relin_dot_level_host<K, T, D, Lv, O, M>(out0, out1, a0, a1, b0, b1, terms, key, alpha, centered, floor);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t O, size_t M>
+void mul_relin_dot_level_ntt(poly_p<T, D, O> &out0, poly_p<T, D, O> &out1, poly_p<T, D, Lv> const *a0, poly_p<T, D, Lv> const *a1,
+                             poly_p<T, D, Lv> const *b0, poly_p<T, D, Lv> const *b1, size_t terms, poly_p<T, D, M> const *key, size_t alpha,
+                             bool centered = false, bool floor = false) {
+  poly_p<T, D, M>::template mul_relin_dot_level_into<K, Lv, O>(out0, out1, a0, a1, b0, b1, terms, key, alpha, centered, floor);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t O, size_t M>
+void square_relin_dot_level_ntt(poly<T, D, O> &out0, poly<T, D, O> &out1, poly<T, D, Lv> const *a0, poly<T, D, Lv> const *a1, size_t terms,
+                                poly<T, D, M> const *key, size_t alpha, bool centered = false, bool floor = false) {
+  detail::mul_relin_dot_level_host<K, T, D, Lv, O, M>(out0, out1, a0, a1, nullptr, nullptr, terms, key, alpha, centered, floor);
+}
+template <size_t K, class T, size_t D, size_t Lv, size_t O, size_t M>
+void square_relin_dot_level_ntt(poly_p<T, D, O> &out0, poly_p<T, D, O> &out1, poly_p<T, D, Lv> const *a0, poly_p<T, D, Lv> const *a1, size_t terms,
+                                poly_p<T, D, M> const *key, size_t alpha, bool centered = false, bool floor = false) {
+  poly_p<T, D, M>::template mul_relin_dot_level_into<K, Lv, O>(out0, out1, a0, a1, static_cast<poly_p<T, D, Lv> const *>(nullptr),
+                                                                static_cast<poly_p<T, D, Lv> const *>(nullptr), terms, key, alpha, centered, floor);
 }
 
 /* Hoisted rotations (include/nflhip.h "hoisted rotations"): the ciphertext (c0, c1) in the ring with L moduli rotated by ks[m], m <

@@ -706,6 +706,59 @@ int nflhip_mulrelin_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const
                               const void *h_b1, const void *h_key, size_t batch, size_t k_special, size_t alpha, size_t level,
                               int flags);   /* staged host variant */
 
+/* ---- sums of ciphertext products: one relinearisation for many products --------------------------
+ * sum_j ct_a[j] * ct_b[j] per group -- an encrypted matrix times an encrypted vector, an inner product, a sum of squares -- with
+ * the tensor products summed BEFORE the one key switch (lazy relinearisation): one mod-up, one key-switch inner product, one
+ * mod-down and one key-switch noise term for `terms` products.
+ *
+ * nflhip_tensor_dot_ntt_dev: for every group g < groups, on the first `rows` moduli, row by row mod p_m,
+ *     D0[g] = sum_{j < terms} a0(g,j) (.) b0(g,j)
+ *     D1[g] = sum_{j < terms} (a0(g,j) (.) b1(g,j) + a1(g,j) (.) b0(g,j))
+ *     D2[g] = sum_{j < terms} a1(g,j) (.) b1(g,j)                                  b0 == b1 == NULL: the squares, b = a
+ *   a0, a1, b0, b1   nflhip_dot_operand, exactly as nflhip_dot_dev reads them, EXCEPT that a polynomial has `rows` rows: polynomial
+ *                    (g, j) lies (g group_stride + j term_stride) * rows * degree words after ptr; group_stride 0: shared by all groups.
+ *                    Canonical words; the form is not looked at (callers pass NTT form)
+ *   d_out0..2        dense [groups][rows][degree], canonical
+ *   One launch: the three sums stay unreduced in registers, D1 reduced every 8 terms, D0 and D2 every 16; the words
+ *   are the canonical residues of the exact sums.  Allocates nothing, uses no scratch, does not synchronise, can be captured.
+ *   NFLHIP_ERR_INVALID, before the device is touched: a NULL pointer; exactly one of b0 / b1 NULL; terms == 0 or above 2^31; rows
+ *   outside [1, nmoduli]; flag bits; an extent that overflows size_t; an output that overlaps another output or any byte of an
+ *   operand's extent (the (groups - 1) group_stride + (terms - 1) term_stride + 1 polynomials from its ptr); a cyclic row context.
+ *   groups == 0: NFLHIP_OK, nothing touched.
+ *   The host variant takes a0, a1 dense [groups][terms][rows][degree] and b0, b1 alike, or [terms][rows][degree] with b_shared.
+ *
+ * nflhip_mulrelin_dot_ntt_dev: nflhip_mulrelin_level_ntt_dev with (d0, d1, d2) replaced by (D0, D1, D2) and the batch by `groups`:
+ *     A_c = E(pi (.) D_c) + sum_d U_d (.) key[d][c],  U_d the mod-up of D2;   out_c = the mod-down of A_c (RESCALE: one row more)
+ *   operands         polynomials of `level` rows, strides in such polynomials; level == nmoduli - k_special is the top level
+ *   d_key            the ONE top-level key [dnum_L][2][nmoduli][degree], read as at a level
+ *   d_out0, d_out1   [groups][level][degree]; with NFLHIP_MULRELIN_RESCALE [groups][level - 1][degree]
+ *   Without the rescale the words are D_c + nflhip_keyswitch_level_ntt_dev(D2)_c, in both mod-up modes and both roundings.
+ *   Plans: NFLHIP_MULRELIN_SEQUENCE -- existing entries only (nflhip_dot_dev on the kept rows: D0 = dot(a0, b0), D1 = dot(a0, b1)
+ *   then dot(a1, b0) with D1 as the addend, D2 = dot(a1, b1); the rest as the multiplication's sequence); NFLHIP_MULRELIN_MERGED,
+ *   the default -- one launch of the kernel above in the scaled layout, then as the multiplication's merged plan;
+ *   NFLHIP_MULRELIN_FUSED -- NFLHIP_ERR_UNSUPPORTED: the one-launch kernel re-forms a1 (.) b1 per digit from global memory.
+ *   terms == 1 with every operand dense over the groups (group_stride 1, or groups == 1) IS nflhip_mulrelin_level_ntt_dev: the call
+ *   forwards, every plan included.
+ *   Scratch, tables, the level context, the first-call, larger-batch and while-capturing rules are the multiplication's, with
+ *   `groups` as the batch (the terms size no scratch).
+ *   NFLHIP_ERR_INVALID, nothing enqueued: what nflhip_mulrelin_level_ntt_dev refuses, terms == 0 or above 2^31, an extent that
+ *   overflows, and an output that overlaps an operand's extent without beginning at that operand's first byte (every read is
+ *   enqueued before the mod-down writes), the other output, or the key.
+ *   The host variant stages a0, a1 dense [groups][terms], b0, b1 alike or [terms] with b_shared, and the key's digits that are read. */
+int nflhip_tensor_dot_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, void *d_out2, const nflhip_dot_operand *a0,
+                              const nflhip_dot_operand *a1, const nflhip_dot_operand *b0, const nflhip_dot_operand *b1, size_t groups,
+                              size_t terms, size_t rows, int flags /* 0 */, void *stream);
+int nflhip_tensor_dot_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, void *h_out2, const void *h_a0, const void *h_a1,
+                          const void *h_b0, const void *h_b1, size_t groups, size_t terms, int b_shared, size_t rows,
+                          int flags);   /* staged host variant */
+int nflhip_mulrelin_dot_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const nflhip_dot_operand *a0, const nflhip_dot_operand *a1,
+                                const nflhip_dot_operand *b0, const nflhip_dot_operand *b1, const void *d_key, size_t groups,
+                                size_t terms, size_t k_special, size_t alpha, size_t level, int flags /* NFLHIP_MULRELIN_* */,
+                                void *stream);
+int nflhip_mulrelin_dot_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0,
+                            const void *h_b1, const void *h_key, size_t groups, size_t terms, int b_shared, size_t k_special,
+                            size_t alpha, size_t level, int flags);   /* staged host variant */
+
 /* ---- rotations and linear transforms at a level: one Galois key and one diagonal for every level ----
  * nflhip_rotate_hoisted_ntt_dev and nflhip_lintrans_ntt_dev on a ciphertext below the context's top level, with the ONE top-level
  * Galois key per rotation and the ONE top-level diagonal per term.  Levels, live rows A_l, phys(r) and the digits are those of

@@ -110,6 +110,12 @@ SYMBOLS = [
     ("nflhip_keyswitch_level_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _i]),
     ("nflhip_mulrelin_level_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _i, _vp]),
     ("nflhip_mulrelin_level_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _i]),
+    ("nflhip_tensor_dot_ntt_dev", _i, [_vp, _vp, _vp, _vp, C.POINTER(DotOperand), C.POINTER(DotOperand), C.POINTER(DotOperand), C.POINTER(DotOperand),
+                                       _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_tensor_dot_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _sz, _i]),
+    ("nflhip_mulrelin_dot_ntt_dev", _i, [_vp, _vp, _vp, C.POINTER(DotOperand), C.POINTER(DotOperand), C.POINTER(DotOperand), C.POINTER(DotOperand),
+                                         _vp, _sz, _sz, _sz, _sz, _sz, _i, _vp]),
+    ("nflhip_mulrelin_dot_ntt", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _sz, _sz, _sz, _i]),
     ("nflhip_rotate_hoisted_level_ntt_dev", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _sz, _i, _vp]),
     ("nflhip_rotate_hoisted_level_ntt", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _sz, _i]),
     ("nflhip_lintrans_level_ntt_dev", _i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), _sz, _sz, _sz, _sz, _sz, _i, _vp]),

@@ -436,7 +436,7 @@ static int warm_up_device(nflhip_ctx *c) {
     std::call_once(once[c->device], [&] {
       hipStream_t st = c->hstream;
       hipError_t (*const tus[])(hipStream_t) = {nflhip::warm_generic, nflhip::warm_fast, nflhip::warm_crt, nflhip::warm_crt_mfma,
-                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch, nflhip::warm_dot_multi, nflhip::warm_rotate, nflhip::warm_lintrans, nflhip::warm_mulrelin, nflhip::warm_scale_round};
+                                                nflhip::warm_sample, nflhip::warm_wave, nflhip::warm_automorph, nflhip::warm_rescale, nflhip::warm_dot, nflhip::warm_decompose, nflhip::warm_baseconv, nflhip::warm_baseconv_ntt, nflhip::warm_keyswitch, nflhip::warm_dot_multi, nflhip::warm_rotate, nflhip::warm_lintrans, nflhip::warm_mulrelin, nflhip::warm_scale_round, nflhip::warm_tensor_dot};
       for (auto f : tus)
         if (e == hipSuccess) e = f(st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1812,8 +1812,19 @@ static int mulrelin_default_plan(const nflhip_ctx *ctx, size_t L, size_t dnum, b
   if (!ctx->shape.compiled_only && keyswitch_fused_fits(L, dnum, ctx->shape.n, ctx->word, centred)) return NFLHIP_MULRELIN_FUSED;
   return NFLHIP_MULRELIN_MERGED;
 }
+// The sum over terms: the merged plan; the one-launch kernel is not built for it.
+static int mulrelin_dot_default_plan() { return NFLHIP_MULRELIN_MERGED; }
+// `dot`: the sum over terms (include/nflhip.h "sums of ciphertext products") -- the tensor stage forms (D0, D1, D2) from the four
+// operands (strides in polynomials of L rows; b0.ptr == nullptr: the squares), a0 .. b1 are not read and `batch` is the groups.
+struct MrDot {
+  nflhip_dot_operand a0, a1, b0, b1;
+  size_t terms;
+};
+static TensorDotOperand tensor_dot_operand(const nflhip_dot_operand *x) {  // (the launcher's own type: kernels.h does not see nflhip.h)
+  return x ? TensorDotOperand{x->ptr, x->group_stride, x->term_stride} : TensorDotOperand{nullptr, 0, 0};
+}
 static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0, const void *a1, const void *b0, const void *b1, const void *key,
-                        size_t batch, size_t K, size_t alpha, int flags, hipStream_t st, const KeyLevel *kl = nullptr) {
+                        size_t batch, size_t K, size_t alpha, int flags, hipStream_t st, const KeyLevel *kl = nullptr, const MrDot *dot = nullptr) {
   std::lock_guard<std::mutex> lk(ctx->mr_mu);
   const size_t nm = ctx->shape.nm, n = ctx->shape.n, L = nm - K, dnum = (L + alpha - 1) / alpha, row = n * ctx->word, pb = nm * row, qb = L * row;
   const bool centred = (flags & NFLHIP_MULRELIN_CENTERED) != 0, floor = (flags & NFLHIP_MULRELIN_FLOOR) != 0;
@@ -1841,7 +1852,9 @@ static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0,
   int plan = flags & (NFLHIP_MULRELIN_SEQUENCE | NFLHIP_MULRELIN_MERGED | NFLHIP_MULRELIN_FUSED);
   if (plan == NFLHIP_MULRELIN_FUSED && !keyswitch_fused_fits(L, dnum, n, ctx->word, centred))
     return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "mulrelin: the rows of this call do not fit the one-launch kernel's LDS");
-  if (!plan) plan = mulrelin_default_plan(ctx, L, dnum, centred);
+  if (dot && plan == NFLHIP_MULRELIN_FUSED)
+    return fail(ctx, NFLHIP_ERR_UNSUPPORTED, "mulrelin_dot: the one-launch kernel serves one product (terms == 1, dense operands)");
+  if (!plan) plan = dot ? mulrelin_dot_default_plan() : mulrelin_default_plan(ctx, L, dnum, centred);
   const int modes = flags & (NFLHIP_MULRELIN_CENTERED | NFLHIP_MULRELIN_FLOOR | NFLHIP_MULRELIN_RESCALE);
   // what a call while capturing may do: repeat a (k_special, alpha, plan, modes) already served at this batch or a larger one
   const std::array<size_t, 3> wkey = {K, alpha, (size_t)(plan | modes)}, wsizes = {batch, 0, 0};
@@ -1871,12 +1884,20 @@ static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0,
     if (e != hipSuccess) return hipfail(ctx, e, "mulrelin (fused)");
   } else if (seq) {
     char *D = S + 4 * batch * qb, *X2 = X + 2 * batch * pb;
-    const void *const src[4] = {a0, a1, b1 ? b1 : a1, b0 ? b0 : a0};  // S = [a0 a1 | b1 b0]: d1 = a0 b1 + a1 b0 term by term
-    for (int k = 0; k < 4; ++k) HIPCHK(ctx, hipMemcpyAsync(S + k * batch * qb, src[k], batch * qb, hipMemcpyDefault, st));  // (a staged caller's inputs may be pinned host memory)
-    const nflhip_dot_operand sa0 = {S, 1, batch}, sa1 = {S + batch * qb, 1, batch}, sb1 = {S + 2 * batch * qb, 1, batch}, sb0 = {S + 3 * batch * qb, 1, batch};
-    if ((rc = nflhip_dot_dev(child, D, &sa0, &sb0, nullptr, batch, 1, 0, st))) return rc;
-    if ((rc = nflhip_dot_dev(child, D + batch * qb, &sa0, &sb1, nullptr, batch, 2, 0, st))) return rc;
-    if ((rc = nflhip_dot_dev(child, D + 2 * batch * qb, &sa1, &sb1, nullptr, batch, 1, 0, st))) return rc;
+    if (dot) {  // D straight from the operands, four sums of products on the kept rows (the squares: b is a, D1 = 2 sum a0 a1)
+      const nflhip_dot_operand *y0 = dot->b0.ptr ? &dot->b0 : &dot->a0, *y1 = dot->b0.ptr ? &dot->b1 : &dot->a1;
+      if ((rc = nflhip_dot_dev(child, D, &dot->a0, y0, nullptr, batch, dot->terms, 0, st))) return rc;
+      if ((rc = nflhip_dot_dev(child, D + batch * qb, &dot->a0, y1, nullptr, batch, dot->terms, 0, st))) return rc;
+      if ((rc = nflhip_dot_dev(child, D + batch * qb, &dot->a1, y0, D + batch * qb, batch, dot->terms, 0, st))) return rc;
+      if ((rc = nflhip_dot_dev(child, D + 2 * batch * qb, &dot->a1, y1, nullptr, batch, dot->terms, 0, st))) return rc;
+    } else {
+      const void *const src[4] = {a0, a1, b1 ? b1 : a1, b0 ? b0 : a0};  // S = [a0 a1 | b1 b0]: d1 = a0 b1 + a1 b0 term by term
+      for (int k = 0; k < 4; ++k) HIPCHK(ctx, hipMemcpyAsync(S + k * batch * qb, src[k], batch * qb, hipMemcpyDefault, st));  // (a staged caller's inputs may be pinned host memory)
+      const nflhip_dot_operand sa0 = {S, 1, batch}, sa1 = {S + batch * qb, 1, batch}, sb1 = {S + 2 * batch * qb, 1, batch}, sb0 = {S + 3 * batch * qb, 1, batch};
+      if ((rc = nflhip_dot_dev(child, D, &sa0, &sb0, nullptr, batch, 1, 0, st))) return rc;
+      if ((rc = nflhip_dot_dev(child, D + batch * qb, &sa0, &sb1, nullptr, batch, 2, 0, st))) return rc;
+      if ((rc = nflhip_dot_dev(child, D + 2 * batch * qb, &sa1, &sb1, nullptr, batch, 1, 0, st))) return rc;
+    }
     if ((rc = set_device(ctx))) return rc;
     HIPCHK(ctx, hipMemsetAsync(X, 0, 3 * batch * pb, st));
     HIPCHK(ctx, hipMemcpy2DAsync(X, pb, D, qb, qb, 3 * batch, hipMemcpyDeviceToDevice, st));
@@ -1890,6 +1911,11 @@ static int mulrelin_run(nflhip_ctx *ctx, void *out0, void *out1, const void *a0,
     const size_t pw = pb / ctx->word, qw = qb / ctx->word;
     hipError_t e = with_limb(ctx, [&](auto z) {
       typedef decltype(z) T;
+      if (dot) {
+        const TensorDotOperand o[4] = {tensor_dot_operand(&dot->a0), tensor_dot_operand(&dot->a1), tensor_dot_operand(&dot->b0), tensor_dot_operand(&dot->b1)};
+        return launch_tensor_dot_ntt<T>(ctx->shape, ctx->tabs, (T *)A, (T *)(A + batch * pb), (T *)X, &o[0], &o[1], o[2].ptr ? &o[2] : nullptr,
+                                        o[2].ptr ? &o[3] : nullptr, batch, dot->terms, L, nm, pw, route == kModupPerDigit ? pw : qw, pi, st);
+      }
       return launch_tensor_ntt<T>(ctx->shape, ctx->tabs, (T *)A, (T *)(A + batch * pb), (T *)X, (const T *)a0, (const T *)a1, (const T *)b0, (const T *)b1,
                                   batch, L, nm, pw, route == kModupPerDigit ? pw : qw, pi, st);
     });
@@ -1946,6 +1972,41 @@ int nflhip_mulrelin_level_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, c
   if ((rc = level_context(ctx, k_special, level, (hipStream_t)stream, &run, &kl))) return rc;
   return mulrelin_run(run, d_out0, d_out1, d_a0, d_a1, d_b0, d_b1, d_key, batch, k_special, std::min(alpha, level), flags, (hipStream_t)stream,
                       run == ctx ? nullptr : &kl);
+}
+// Sums of ciphertext products (kernels_tensor_dot.hip; include/nflhip.h "sums of ciphertext products"): the tensor product summed
+// over terms in one launch, nothing allocated; and the multiplication over it -- mulrelin_run with the four operands for its tensor
+// stage and the groups as its batch, on the level context.  One product of dense operands IS nflhip_mulrelin_level_ntt_dev.
+int nflhip_tensor_dot_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, void *d_out2, const nflhip_dot_operand *a0, const nflhip_dot_operand *a1,
+                              const nflhip_dot_operand *b0, const nflhip_dot_operand *b1, size_t groups, size_t terms, size_t rows, int flags,
+                              void *stream) {
+  int rc = tensor_dot_check(ctx, d_out0, d_out1, d_out2, a0, a1, b0, b1, groups, terms, rows, flags);  // in full, before any device use
+  if (rc || groups == 0) return rc;
+  if ((rc = set_device(ctx))) return rc;
+  const TensorDotOperand o[4] = {tensor_dot_operand(a0), tensor_dot_operand(a1), tensor_dot_operand(b0), tensor_dot_operand(b1)};
+  hipError_t e = with_limb(ctx, [&](auto z) {
+    typedef decltype(z) T;
+    return launch_tensor_dot_ntt<T>(ctx->shape, ctx->tabs, (T *)d_out0, (T *)d_out1, (T *)d_out2, &o[0], &o[1], b0 ? &o[2] : nullptr, b0 ? &o[3] : nullptr,
+                                    groups, terms, rows, rows, rows * ctx->shape.n, rows * ctx->shape.n, nullptr, (hipStream_t)stream);
+  });
+  return e == hipSuccess ? NFLHIP_OK : hipfail(ctx, e, "tensor_dot");
+}
+int nflhip_mulrelin_dot_ntt_dev(nflhip_ctx *ctx, void *d_out0, void *d_out1, const nflhip_dot_operand *a0, const nflhip_dot_operand *a1,
+                                const nflhip_dot_operand *b0, const nflhip_dot_operand *b1, const void *d_key, size_t groups, size_t terms,
+                                size_t k_special, size_t alpha, size_t level, int flags, void *stream) {
+  int rc = level_check(ctx, k_special, level, "mulrelin_dot");  // in full, before any device use
+  if (!rc) rc = mulrelin_dot_check(ctx, d_out0, d_out1, a0, a1, b0, b1, d_key, groups, terms, k_special, alpha, level, flags);
+  if (rc || groups == 0) return rc;
+  const auto dense = [groups](const nflhip_dot_operand *x) { return !x || groups == 1 || x->group_stride == 1; };
+  if (terms == 1 && dense(a0) && dense(a1) && dense(b0) && dense(b1))
+    return nflhip_mulrelin_level_ntt_dev(ctx, d_out0, d_out1, a0->ptr, a1->ptr, b0 ? b0->ptr : nullptr, b1 ? b1->ptr : nullptr, d_key, groups, k_special,
+                                         alpha, level, flags, stream);
+  nflhip_ctx *run = nullptr;
+  KeyLevel kl;
+  if ((rc = level_context(ctx, k_special, level, (hipStream_t)stream, &run, &kl))) return rc;
+  const nflhip_dot_operand none = {nullptr, 0, 0};
+  const MrDot dot = {*a0, *a1, b0 ? *b0 : none, b1 ? *b1 : none, terms};
+  return mulrelin_run(run, d_out0, d_out1, nullptr, nullptr, nullptr, nullptr, d_key, groups, k_special, std::min(alpha, level), flags, (hipStream_t)stream,
+                      run == ctx ? nullptr : &kl, &dot);
 }
 // Hoisted rotations and linear transforms at a level (kernels_level_rotate.hip; include/nflhip.h "rotations and linear transforms at
 // a level"): rotate_run and lintrans_run on the level context, whose records, workspaces, events, warm maps and kept-rows child are

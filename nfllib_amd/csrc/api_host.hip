@@ -779,6 +779,82 @@ int nflhip_mulrelin_level_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const
   return mulrelin_host(ctx, h_out0, h_out1, h_a0, h_a1, h_b0, h_b1, h_key, batch, k_special, alpha, level, flags);
 }
 
+// sums of ciphertext products: a0, a1 dense [groups][terms] polynomials of `rows` rows, b0, b1 alike or [terms] with b_shared (both
+// NULL: the squares).  The inputs share one slot (a0, a1, then b0, b1), the outputs another, as the tensor product above.
+namespace {
+struct TensorDotHost {
+  size_t abytes, bbytes, nin;
+  nflhip_dot_operand op[4];
+};
+}  // namespace
+static int tensor_dot_host_sizes(nflhip_ctx *ctx, const char *what, const void *h_b0, size_t groups, size_t terms, int b_shared, size_t pbytes,
+                                 TensorDotHost *h) {
+  size_t polys, total;  // (the pointers are checked: the device entry's checks ran on these blocks)
+  if (__builtin_mul_overflow(groups, terms, &polys) || __builtin_mul_overflow(polys, pbytes, &h->abytes) || __builtin_mul_overflow(h->abytes, (size_t)4, &total))
+    return fail(ctx, NFLHIP_ERR_INVALID, std::string(what) + ": an operand's size overflows");
+  h->bbytes = !h_b0 ? 0 : b_shared ? terms * pbytes : h->abytes;
+  h->nin = h_b0 ? 4 : 2;
+  return NFLHIP_OK;
+}
+// stage the inputs into slot 0 and describe them as the device entries take them
+static int tensor_dot_host_stage(nflhip_ctx *ctx, Staged &s, const void *h_a0, const void *h_a1, const void *h_b0, const void *h_b1, size_t terms,
+                                 int b_shared, TensorDotHost *h) {
+  int rc = s.in(0, nullptr, 2 * h->abytes + 2 * h->bbytes);
+  if (rc) return rc;
+  char *i = (char *)ctx->stage[0];
+  const void *const hin[4] = {h_a0, h_a1, h_b0, h_b1};
+  const size_t len[4] = {h->abytes, h->abytes, h->bbytes, h->bbytes}, off[4] = {0, h->abytes, 2 * h->abytes, 2 * h->abytes + h->bbytes};
+  for (size_t k = 0; k < h->nin; ++k) {
+    if (ctx->stage_host[0]) std::memcpy(i + off[k], hin[k], len[k]);
+    else HIPCHK(ctx, hipMemcpyAsync(i + off[k], hin[k], len[k], hipMemcpyHostToDevice, ctx->hstream));
+    h->op[k] = {i + off[k], k >= 2 && b_shared ? (size_t)0 : terms, 1};
+  }
+  return NFLHIP_OK;
+}
+int nflhip_tensor_dot_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, void *h_out2, const void *h_a0, const void *h_a1, const void *h_b0,
+                          const void *h_b1, size_t groups, size_t terms, int b_shared, size_t rows, int flags) {
+  // the device entry's checks on the host blocks, which lie as dense operands do
+  const nflhip_dot_operand ha0 = {h_a0, terms, 1}, ha1 = {h_a1, terms, 1}, hb0 = {h_b0, b_shared ? (size_t)0 : terms, 1}, hb1 = {h_b1, b_shared ? (size_t)0 : terms, 1};
+  int rc = tensor_dot_check(ctx, h_out0, h_out1, h_out2, &ha0, &ha1, h_b0 ? &hb0 : nullptr, h_b1 ? &hb1 : nullptr, groups, terms, rows, flags);
+  if (rc || groups == 0) return rc;
+  const size_t pbytes = rows * ctx->shape.n * ctx->word;
+  TensorDotHost h;
+  if ((rc = tensor_dot_host_sizes(ctx, "tensor_dot", h_b0, groups, terms, b_shared, pbytes, &h)) || (rc = set_device(ctx))) return rc;
+  const size_t ob = groups * pbytes;
+  Staged s(ctx);
+  if ((rc = tensor_dot_host_stage(ctx, s, h_a0, h_a1, h_b0, h_b1, terms, b_shared, &h)) || (rc = s.in(2, nullptr, 3 * ob))) return rc;
+  char *o = (char *)ctx->stage[2];
+  if ((rc = nflhip_tensor_dot_ntt_dev(ctx, o, o + ob, o + 2 * ob, &h.op[0], &h.op[1], h_b0 ? &h.op[2] : nullptr, h_b0 ? &h.op[3] : nullptr, groups, terms, rows,
+                                      flags, (void *)ctx->hstream)))
+    return rc;
+  void *const hout[3] = {h_out0, h_out1, h_out2};
+  return s.outs(hout, 3, 2, ob);
+}
+// the multiplication over them: staged as mulrelin_host, the operands as above
+int nflhip_mulrelin_dot_ntt(nflhip_ctx *ctx, void *h_out0, void *h_out1, const void *h_a0, const void *h_a1, const void *h_b0, const void *h_b1,
+                            const void *h_key, size_t groups, size_t terms, int b_shared, size_t k_special, size_t alpha, size_t level, int flags) {
+  int rc = level_check(ctx, k_special, level, "mulrelin_dot");
+  if (rc) return rc;
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, pbytes = level * row;
+  TensorDotHost h;
+  // the device entry's checks on the host blocks, which lie as dense operands do
+  const nflhip_dot_operand ha0 = {h_a0, terms, 1}, ha1 = {h_a1, terms, 1}, hb0 = {h_b0, b_shared ? (size_t)0 : terms, 1}, hb1 = {h_b1, b_shared ? (size_t)0 : terms, 1};
+  if ((rc = mulrelin_dot_check(ctx, h_out0, h_out1, &ha0, &ha1, h_b0 ? &hb0 : nullptr, h_b1 ? &hb1 : nullptr, h_key, groups, terms, k_special, alpha, level, flags)) ||
+      groups == 0)
+    return rc;
+  if ((rc = tensor_dot_host_sizes(ctx, "mulrelin_dot", h_b0, groups, terms, b_shared, pbytes, &h))) return rc;
+  const size_t ib = groups * pbytes, ob = (flags & NFLHIP_MULRELIN_RESCALE) ? ib - groups * row : ib;
+  if ((rc = set_device(ctx))) return rc;
+  const size_t kb = 2 * keyswitch_level_digits(ctx, k_special, alpha, level) * nm * row;
+  Staged s(ctx);
+  if ((rc = tensor_dot_host_stage(ctx, s, h_a0, h_a1, h_b0, h_b1, terms, b_shared, &h)) || (rc = s.in(1, h_key, kb)) || (rc = s.in(2, nullptr, 2 * ob))) return rc;
+  char *o = (char *)ctx->stage[2];
+  if ((rc = nflhip_mulrelin_dot_ntt_dev(ctx, o, o + ob, &h.op[0], &h.op[1], h_b0 ? &h.op[2] : nullptr, h_b0 ? &h.op[3] : nullptr, ctx->stage[1], groups, terms,
+                                        k_special, alpha, level, flags, (void *)ctx->hstream)))
+    return rc;
+  return s.out2(h_out0, h_out1, 2, ob);
+}
+
 // sums of products across polynomials: the operands are `terms` times the size of the result, so the call is staged whole
 int nflhip_dot(nflhip_ctx *ctx, void *h_out, const void *h_a, const void *h_b, size_t groups, size_t terms, int b_shared) {
   if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");

@@ -620,6 +620,76 @@ inline int mulrelin_check(const nflhip_ctx *ctx, const void *out0, const void *o
   }
   return NFLHIP_OK;
 }
+// nflhip_tensor_dot_ntt_dev / nflhip_mulrelin_dot_ntt_dev: the four operands (b0 == b1 == NULL: the squares) against `nouts` outputs
+// of obytes each.  An operand's extent is that of dot_check over polynomials of pbytes.  `at_start`: an output may begin exactly at
+// an operand's first byte (the multiplication: every read is enqueued before the mod-down writes).
+inline int tensor_dot_operands_check(const nflhip_ctx *ctx, const std::string &w, const void *const *outs, int nouts, size_t obytes,
+                                     const nflhip_dot_operand *const *ops, size_t groups, size_t terms, size_t pbytes, bool at_start) {
+  for (int q = 0; q < 4; ++q) {
+    const nflhip_dot_operand *x = ops[q];
+    if (!x) continue;
+    if (!x->ptr) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+    size_t g, t, polys, bytes;
+    if (__builtin_mul_overflow(groups - 1, x->group_stride, &g) || __builtin_mul_overflow(terms - 1, x->term_stride, &t) ||
+        __builtin_add_overflow(g, t, &polys) || __builtin_add_overflow(polys, (size_t)1, &polys) || __builtin_mul_overflow(polys, pbytes, &bytes))
+      return fail(ctx, NFLHIP_ERR_INVALID, w + ": an operand's extent overflows");
+    for (int o = 0; o < nouts; ++o)
+      if (!(at_start && outs[o] == x->ptr) && ranges_overlap(outs[o], obytes, x->ptr, bytes))
+        return fail(ctx, NFLHIP_ERR_INVALID, w + (at_start ? ": an output overlaps an operand without beginning at its first byte" : ": an output overlaps an operand"));
+  }
+  return NFLHIP_OK;
+}
+// nflhip_tensor_dot_ntt_dev: every argument check, before any device use
+inline int tensor_dot_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const void *out2, const nflhip_dot_operand *a0,
+                            const nflhip_dot_operand *a1, const nflhip_dot_operand *b0, const nflhip_dot_operand *b1, size_t groups, size_t terms,
+                            size_t rows, int flags) {
+  if (!ctx) return fail(nullptr, NFLHIP_ERR_INVALID, "ctx is NULL");
+  if (ctx->cyclic) return fail(ctx, NFLHIP_ERR_INVALID, "tensor_dot: not on a cyclic row context");
+  if (flags) return fail(ctx, NFLHIP_ERR_INVALID, "tensor_dot: unknown flag bits");
+  if (terms == 0 || terms > nflhip::kDotMaxTerms) return fail(ctx, NFLHIP_ERR_INVALID, "tensor_dot: the number of terms is out of range (1 to 2^31)");
+  if (rows == 0 || rows > ctx->shape.nm) return fail(ctx, NFLHIP_ERR_INVALID, "tensor_dot: rows is out of range (1 to nmoduli)");
+  if (ctx->shape.nm > 65535) return fail(ctx, NFLHIP_ERR_INVALID, "tensor_dot: more than 65535 rows");
+  if (!a0 || !a1) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  if (!b0 != !b1) return fail(ctx, NFLHIP_ERR_INVALID, "tensor_dot: b0 and b1 are both given, or both NULL for the squares");
+  if (groups == 0) return NFLHIP_OK;
+  if (!out0 || !out1 || !out2) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t pbytes = rows * ctx->shape.n * ctx->word;
+  size_t ob;
+  if (__builtin_mul_overflow(groups, pbytes, &ob)) return fail(ctx, NFLHIP_ERR_INVALID, "tensor_dot: the output size overflows");
+  const void *const outs[3] = {out0, out1, out2};
+  for (int o = 0; o < 3; ++o)
+    for (int q = 0; q < o; ++q)
+      if (ranges_overlap(outs[o], ob, outs[q], ob)) return fail(ctx, NFLHIP_ERR_INVALID, "tensor_dot: two outputs overlap");
+  const nflhip_dot_operand *const ops[4] = {a0, a1, b0, b1};
+  return tensor_dot_operands_check(ctx, "tensor_dot", outs, 3, ob, ops, groups, terms, pbytes, false);
+}
+// nflhip_mulrelin_dot_ntt_dev: every argument check short of the tables, before any device use; after level_check (1 <= level <= L)
+inline int mulrelin_dot_check(const nflhip_ctx *ctx, const void *out0, const void *out1, const nflhip_dot_operand *a0, const nflhip_dot_operand *a1,
+                              const nflhip_dot_operand *b0, const nflhip_dot_operand *b1, const void *key, size_t groups, size_t terms,
+                              size_t k_special, size_t alpha, size_t level, int flags) {
+  int rc = keyswitch_family_check(ctx, "mulrelin_dot", flags, NFLHIP_MULRELIN_SEQUENCE | NFLHIP_MULRELIN_MERGED | NFLHIP_MULRELIN_FUSED,
+                                  NFLHIP_MULRELIN_CENTERED | NFLHIP_MULRELIN_FLOOR | NFLHIP_MULRELIN_RESCALE, nullptr, k_special, alpha);
+  if (rc) return rc;
+  if (terms == 0 || terms > nflhip::kDotMaxTerms) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin_dot: the number of terms is out of range (1 to 2^31)");
+  if ((flags & NFLHIP_MULRELIN_RESCALE) && level < 2) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin_dot: the rescale needs two kept moduli at least (level >= 2)");
+  if (!a0 || !a1) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  if (!b0 != !b1) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin_dot: b0 and b1 are both given, or both NULL for the squares");
+  if (groups == 0) return NFLHIP_OK;
+  if (!out0 || !out1 || !key) return fail(ctx, NFLHIP_ERR_INVALID, "NULL operand");
+  const size_t nm = ctx->shape.nm, row = ctx->shape.n * ctx->word, dnum = keyswitch_digits(ctx, k_special, alpha), kd = (level + alpha - 1) / alpha;
+  size_t ib, ob, sb, kb, polys;
+  // (sb: the largest scratch of either plan, as mulrelin_check)
+  if (__builtin_mul_overflow(groups, level * row, &ib) || __builtin_mul_overflow(groups, dnum + 13, &polys) || __builtin_mul_overflow(polys, nm * row, &sb) ||
+      __builtin_mul_overflow(2 * kd, nm * row, &kb))  // (kb: the digits that are read)
+    return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin_dot: the size overflows");
+  ob = (flags & NFLHIP_MULRELIN_RESCALE) ? ib - groups * row : ib;
+  if (ranges_overlap(out0, ob, out1, ob)) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin_dot: the two outputs overlap");
+  for (const void *o : {out0, out1})
+    if (ranges_overlap(o, ob, key, kb)) return fail(ctx, NFLHIP_ERR_INVALID, "mulrelin_dot: an output overlaps the key");
+  const void *const outs[2] = {out0, out1};
+  const nflhip_dot_operand *const ops[4] = {a0, a1, b0, b1};
+  return tensor_dot_operands_check(ctx, "mulrelin_dot", outs, 2, ob, ops, groups, terms, level * row, true);
+}
 // nflhip_scale_round_dev / _ntt_dev / nflhip_scale_round / _ntt: every argument check short of the tables (a repeated modulus is found by
 // their builder, api.hip scale_round_record), before any device use.  *obytes: the size of the output.
 inline int scale_round_args(const nflhip_ctx *ctx, const char *what, size_t ks, uint64_t t, int flags, int allowed) {

@@ -211,6 +211,18 @@ hipError_t launch_modup_dot_fused(const Shape &s, const DevTables &t, T *acc, co
 template <typename T>
 hipError_t launch_tensor_ntt(const Shape &s, const DevTables &t, T *out0, T *out1, T *out2, const T *a0, const T *a1, const T *b0, const T *b1,
                              size_t batch, size_t rows, size_t orows, size_t pitch01, size_t pitch2, const uint64_t *pi, hipStream_t st);
+// the tensor product summed over terms (kernels_tensor_dot.hip; include/nflhip.h "sums of ciphertext products"): D0 = sum_j a0 b0,
+// D1 = sum_j (a0 b1 + a1 b0), D2 = sum_j a1 b1 per group on the first `rows` moduli.  An operand's polynomial (g, j) lies
+// g group_stride + j term_stride polynomials OF `rows` ROWS after its ptr (nflhip_dot_operand, field for field); b0 == b1 == nullptr:
+// the squares.  The outputs must not overlap the operands (api.hip checks).  pi, orows and the pitches: as launch_tensor_ntt.
+struct TensorDotOperand {
+  const void *ptr;
+  size_t group_stride, term_stride;
+};
+template <typename T>
+hipError_t launch_tensor_dot_ntt(const Shape &s, const DevTables &t, T *out0, T *out1, T *out2, const TensorDotOperand *a0, const TensorDotOperand *a1,
+                                 const TensorDotOperand *b0, const TensorDotOperand *b1, size_t groups, size_t terms, size_t rows, size_t orows,
+                                 size_t pitch01, size_t pitch2, const uint64_t *pi, hipStream_t st);
 // the multiplication's one-launch plan up to the two sums: a*, b* = [batch][L][n] NTT form (b0 == b1 == nullptr: the square), key =
 // [dnum][2][nm][n], acc = [2][batch][nm][n] canonical, acc[c][b] = E(pi d_c) + sum_d U_d key[d][c] with U_d the mod-up of a1 (.) b1.
 // The LDS and the bounds of launch_modup_dot_fused (keyswitch_fused_lds / keyswitch_fused_fits): hipErrorNotSupported beyond them.
@@ -412,6 +424,7 @@ hipError_t warm_dot_multi(hipStream_t st);
 hipError_t warm_rotate(hipStream_t st);
 hipError_t warm_lintrans(hipStream_t st);
 hipError_t warm_mulrelin(hipStream_t st);
+hipError_t warm_tensor_dot(hipStream_t st);
 hipError_t warm_decompose(hipStream_t st);
 hipError_t warm_baseconv(hipStream_t st);
 hipError_t warm_baseconv_ntt(hipStream_t st);

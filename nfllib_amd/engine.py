@@ -984,6 +984,127 @@ class Engine:
                                                self._mr_flags(rescale, centered, floor, plan)))
         return out0, out1
 
+    # ---- sums of ciphertext products (include/nflhip.h "sums of ciphertext products") ----
+    @staticmethod
+    def _dot_operand(x, strides):
+        return _lib.DotOperand(x if isinstance(x, int) else x.data_ptr(), strides[0], strides[1])
+
+    def _dot_operands(self, a0, a1, b0, b1):
+        """four (tensor_or_address, (group_stride, term_stride)) pairs -> the ctypes operands (b0 = b1 = None: the squares)"""
+        if (b0 is None) != (b1 is None):
+            raise ValueError("b0 and b1 are both given, or both None for the squares")
+        ops = [None if x is None else self._dot_operand(*x) for x in (a0, a1, b0, b1)]
+        return ops, [None if o is None else C.byref(o) for o in ops]
+
+    def _dot_blocks(self, a0, a1, b0, b1, terms, rows, b_shared, size):
+        """dense blocks [groups * terms, rows, n] (b: [terms, rows, n] with b_shared) -> groups"""
+        if (b0 is None) != (b1 is None):
+            raise ValueError("b0 and b1 are both given, or both None for the squares")
+        poly = rows * self.degree
+        if terms <= 0 or size(a0) % (terms * poly) or size(a1) != size(a0):
+            raise ValueError("a0 and a1 hold groups * terms polynomials of `rows` rows each")
+        groups = size(a0) // (terms * poly)
+        if b0 is not None and any(size(x) != (terms * poly if b_shared else size(a0)) for x in (b0, b1)):
+            raise ValueError("b0 and b1 hold groups * terms polynomials, or terms with b_shared")
+        return groups
+
+    def tensor_dot_strided(self, a0, a1, b0, b1, groups, terms, rows=None, outs=None, stream=None):
+        """tensor_dot_ntt on operands anywhere: each of a0, a1, b0, b1 is (tensor_or_address, (group_stride, term_stride)) as
+        dot_strided takes them, the strides in polynomials of `rows` rows (b0 = b1 = None: the squares); the outputs must not
+        overlap the operands"""
+        rows = self.nmoduli if rows is None else rows
+        keep, refs = self._dot_operands(a0, a1, b0, b1)
+        if outs is None:
+            o = _torch().empty((3, groups, max(rows, 0), self.degree), dtype=self.torch_dtype, device="cuda:%d" % self.device)
+            outs = (o[0], o[1], o[2])
+        self._chk(self.lib.nflhip_tensor_dot_ntt_dev(self.ctx, _vp(outs[0]), _vp(outs[1]), _vp(outs[2]), refs[0], refs[1], refs[2], refs[3], groups, terms,
+                                                     rows, 0, self._stream(stream)))
+        return outs
+
+    def tensor_dot_ntt(self, a0, a1, b0=None, b1=None, terms=1, rows=None, b_shared=False, outs=None, stream=None):
+        """the tensor products of `terms` pairs of ciphertexts summed per group, one launch: a0, a1 = [groups * terms, rows, n] blocks
+        over the first `rows` moduli (default: all), b0, b1 alike, or [terms, rows, n] shared by every group with b_shared;
+        (D0, D1, D2)[g] = sum_j (a0 b0, a0 b1 + a1 b0, a1 b1)(g, j).  b0 = b1 = None: the sums of squares.  `outs` = three
+        [groups, rows, n] tensors apart from the operands, else views of one new [3, groups, rows, n] tensor."""
+        rows = self.nmoduli if rows is None else rows
+        if not 1 <= rows <= self.nmoduli or any(x is not None and not x.is_contiguous() for x in (a0, a1, b0, b1)):
+            raise ValueError("rows is 1 to nm; the operands are contiguous")
+        groups = self._dot_blocks(a0, a1, b0, b1, terms, rows, b_shared, lambda x: x.numel())
+        sb = (0 if b_shared else terms, 1)
+        return self.tensor_dot_strided((a0, (terms, 1)), (a1, (terms, 1)), None if b0 is None else (b0, sb), None if b1 is None else (b1, sb),
+                                       groups, terms, rows, outs, stream)
+
+    def h_tensor_dot_ntt(self, a0, a1, b0=None, b1=None, terms=1, rows=None, b_shared=False):
+        """host-pointer variant: numpy blocks as tensor_dot_ntt takes them -> (D0, D1, D2), each [groups, rows, n]"""
+        a0, a1, b0, b1 = (None if x is None else np.ascontiguousarray(x, dtype=self.np_dtype) for x in (a0, a1, b0, b1))
+        rows = self.nmoduli if rows is None else rows
+        if not 1 <= rows <= self.nmoduli:
+            raise ValueError("rows is 1 to nm")
+        groups = self._dot_blocks(a0, a1, b0, b1, terms, rows, b_shared, lambda x: x.size)
+        outs = tuple(np.empty((groups, rows, self.degree), dtype=self.np_dtype) for _ in range(3))
+        self._chk(self.lib.nflhip_tensor_dot_ntt(self.ctx, _vp(outs[0]), _vp(outs[1]), _vp(outs[2]), _vp(a0), _vp(a1), _vp(b0), _vp(b1), groups, terms,
+                                                 int(bool(b_shared)), rows, 0))
+        return outs
+
+    def _mr_dot_level(self, k_special, rescale, level):
+        L = self.nmoduli - k_special
+        if L <= 0:
+            raise ValueError("k_special is 1 to nm - 1")
+        level = L if level is None else level
+        self.level_rows(level, k_special)
+        if rescale and level < 2:
+            raise ValueError("the rescale needs level >= 2")
+        return level
+
+    def mul_relin_dot_strided(self, a0, a1, b0, b1, groups, terms, key, k_special, alpha, rescale=False, centered=False, floor=False, out=None, plan=None,
+                              stream=None, level=None):
+        """mul_relin_dot_ntt on operands anywhere: each of a0, a1, b0, b1 is (tensor_or_address, (group_stride, term_stride)), the
+        strides in polynomials of `level` rows (b0 = b1 = None: the squares).  An output is apart from an operand's extent or begins
+        at its first byte."""
+        level = self._mr_dot_level(k_special, rescale, level)
+        if not key.is_contiguous():
+            raise ValueError("key holds dnum * 2 polynomials of this context")
+        self._level_key(key.numel(), k_special, alpha, level)
+        keep, refs = self._dot_operands(a0, a1, b0, b1)
+        if out is None:
+            both = _torch().empty((2, groups, level - 1 if rescale else level, self.degree), dtype=self.torch_dtype, device=key.device)
+            out = (both[0], both[1])
+        elif len(out) != 2 or any(o.numel() != groups * (level - 1 if rescale else level) * self.degree or not o.is_contiguous() for o in out):
+            raise ValueError("out is a pair of contiguous [groups, level, n] tensors ([groups, level - 1, n] with rescale)")
+        self._chk(self.lib.nflhip_mulrelin_dot_ntt_dev(self.ctx, _vp(out[0]), _vp(out[1]), refs[0], refs[1], refs[2], refs[3], _vp(key), groups, terms,
+                                                       k_special, alpha, level, self._mr_flags(rescale, centered, floor, plan), self._stream(stream)))
+        return out
+
+    def mul_relin_dot_ntt(self, a0, a1, b0, b1, terms, key, k_special, alpha, b_shared=False, rescale=False, centered=False, floor=False, out=None,
+                          plan=None, stream=None, level=None):
+        """sum_j ct_a[g, j] * ct_b[g, j] per group with ONE relinearisation: the tensor products are summed first and the degree-2
+        component key-switched once -- one mod-up, one inner product against the key, one mod-down and one key-switch noise term for
+        `terms` products.  a0, a1 = NTT-form [groups * terms, l, n] blocks, l = level (default: the top, nm - k_special); b0, b1 alike,
+        or [terms, l, n] shared by every group with b_shared; b0 = b1 = None: the sum of squares.  key, rescale, centered, floor and
+        level as mul_relin_ntt.  Returns (out0, out1), each [groups, l or l - 1, n]: `out`, else views of one new tensor, adjacent
+        so that one mod-down serves both.  plan "sequence" / "merged"; "fused" serves terms == 1 with dense operands only, where
+        the call is mul_relin_ntt.  The first call for a (k_special, alpha), or for more groups, allocates."""
+        level = self._mr_dot_level(k_special, rescale, level)
+        if any(x is not None and not x.is_contiguous() for x in (a0, a1, b0, b1)):
+            raise ValueError("the operands are contiguous")
+        groups = self._dot_blocks(a0, a1, b0, b1, terms, level, b_shared, lambda x: x.numel())
+        sb = (0 if b_shared else terms, 1)
+        return self.mul_relin_dot_strided((a0, (terms, 1)), (a1, (terms, 1)), None if b0 is None else (b0, sb), None if b1 is None else (b1, sb),
+                                          groups, terms, key, k_special, alpha, rescale, centered, floor, out, plan, stream, level)
+
+    def h_mul_relin_dot_ntt(self, a0, a1, b0, b1, terms, key, k_special, alpha, b_shared=False, rescale=False, centered=False, floor=False, plan=None,
+                            level=None):
+        """host-pointer variant: numpy blocks as mul_relin_dot_ntt takes them, key = [dnum, 2, nm, n] -> (out0, out1)"""
+        a0, a1, b0, b1 = (None if x is None else np.ascontiguousarray(x, dtype=self.np_dtype) for x in (a0, a1, b0, b1))
+        key = np.ascontiguousarray(key, dtype=self.np_dtype)
+        level = self._mr_dot_level(k_special, rescale, level)
+        self._level_key(key.size, k_special, alpha, level)
+        groups = self._dot_blocks(a0, a1, b0, b1, terms, level, b_shared, lambda x: x.size)
+        out0, out1 = (np.empty((groups, level - 1 if rescale else level, self.degree), dtype=self.np_dtype) for _ in range(2))
+        self._chk(self.lib.nflhip_mulrelin_dot_ntt(self.ctx, _vp(out0), _vp(out1), _vp(a0), _vp(a1), _vp(b0), _vp(b1), _vp(key), groups, terms,
+                                                   int(bool(b_shared)), k_special, alpha, level, self._mr_flags(rescale, centered, floor, plan)))
+        return out0, out1
+
     def pointwise(self, op, a, b=None, bprime=None, out=None, stream=None):
         out = out if out is not None else _torch().empty_like(a)
         self._chk(self.lib.nflhip_pointwise_dev(self.ctx, op, _vp(out), _vp(a), _vp(b), _vp(bprime), self._batch(a),
